@@ -2,12 +2,16 @@
 """Throughput bench of the RPN hot path on MI355X.
 
   python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py ... --full                           (also every secondary measurement, see below)
+  python bench.py ... --dump-outputs DIR               (also write what the last timed step computed, DIR/<name>.npy)
 
 One "step" = one full training pass of the hot path over one synthetic scene per rank: 160^3 x 4 rgb-sigma grid ->
 VGG19-3D + FPN + RPN head forward, target assignment, sampled losses, backward, bucketed RCCL gradient all-reduce,
 fused clip + AdamW.  Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line with the
-BASELINE.json metric (scenes/sec), a `roofline` object for the dominant kernel and a `cpu_baseline` object (the oracle,
-timed on the host cores on a bounded sample).
+BASELINE.json metric (scenes/sec) and `ms_per_step`.  A plain run sets up, warms up, times K steps and prints that line.
+With --full it also carries a `roofline` object for the dominant kernel (HIP events inside the timed region), the host
+enqueue figures, the secondary measurements (`--no-extras` drops them), the comm-only exchange table (N > 1) and a
+`cpu_baseline` object (the oracle, timed on the host cores on a bounded sample; `--no-cpu-baseline` drops it).
 """
 import argparse
 import json
@@ -449,6 +453,32 @@ def conv_source_hash():
     return h.hexdigest()[:16]
 
 
+DUMP_SAMPLE = 1 << 21      # elements kept of an array larger than this (a fixed, seeded sample): < 64 MB for all files together
+
+
+def dump_outputs(path, last, trainer):
+    """What the last timed step handed back to its caller -> ``path/<name>.npy`` (float32): the loss and each loss term, the FPN
+    feature maps (logical NCDHW order) and the parameters after the optimiser step (logical order, ``FlatTrainer.flat_params``).
+    Arrays above DUMP_SAMPLE elements are sampled at indices drawn from a generator seeded by the array's name and size, so two
+    runs (or two builds) with the same arguments write the same elements of the same inputs."""
+    import zlib
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": last["loss"]}
+    arrays.update({k: v for k, v in last["losses"].items() if isinstance(v, torch.Tensor)})
+    feats = last["outs"][0] if isinstance(last["outs"], (list, tuple)) and last["outs"] else None
+    if isinstance(feats, (list, tuple)):
+        arrays.update({f"features_{i}": f for i, f in enumerate(feats) if isinstance(f, torch.Tensor)})
+    arrays["params"] = trainer.flat_params()
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()) + flat.numel())
+            idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(path, name + ".npy"), flat.float().cpu().numpy())
+
+
 def _compact(obj):
     """The JSON line without its prose: every "note" is dropped (DESIGN.md section 4 says what each field is; --notes keeps them) and the
     traffic note is cut to its first clause.  VERDICT r5: the driver's record of the line lost `host` / `rpn_head_cone` to the length."""
@@ -466,6 +496,12 @@ def main():
     ap.add_argument("--steps", type=int, default=100)      # ~1.2 s of timed region (10 steps were 0.12 s: invisible to a GPU-busy sampler)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
+    ap.add_argument("--full", action="store_true",
+                    help="run every measurement beyond the headline too: conv launch timing + roofline, host enqueue, secondary measurements, "
+                         "the comm-only exchange table (N > 1) and the CPU baseline (the --no-* options below drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (losses, FPN features, updated parameters; a fixed "
+                         "seeded sample of the larger arrays) as DIR/<name>.npy, float32, rank 0")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-probe", action="store_true", help="disable per-launch HIP-event timing of the conv kernels")
     ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (fp32 step, eval protocol, 2 scenes per GPU)")
@@ -479,6 +515,8 @@ def main():
     ap.add_argument("--model", default="vgg_rpn", choices=["vgg_rpn", "resnet_rpn", "swin_rpn", "swin_fcos", "vgg_fcos"],
                     help="vgg_rpn = the BASELINE.json metric (default); the others are secondary workloads for profiling")
     args = ap.parse_args()
+    if not args.full:       # a plain run measures the headline figure and nothing else
+        args.no_probe = args.no_extras = args.no_cpu_baseline = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start N ranks (one per GPU) over RCCL ourselves
@@ -556,15 +594,19 @@ def main():
     # loader does -- the RPN uploads them on its target-preparation stream (nerf_rpn.py forward)
     gts = [sc[1].cpu() for sc in scenes]
 
+    keep = [None]       # --dump-outputs: a dict here makes the next step leave what it computed in it
+
     def make_step(model_, trainer_, xs_, gts_):
         def step():
-            _, losses, _ = model_(xs_, gts_)
+            outs, losses, _ = model_(xs_, gts_)
             if fcos:
                 loss = losses["loss_cls"] + losses["loss_reg"] + losses["loss_centerness"]
             else:
                 loss = losses["loss_objectness"] + 5.0 * losses["loss_rpn_box_reg"] + 0.0 * losses["loss_rpn_box_reg_2d"]
             loss.backward()
             trainer_.step()
+            if keep[0] is not None:
+                keep[0].update(outs=outs, losses=losses, loss=loss)
             return loss
         return step
     step = make_step(model, trainer, xs, gts)
@@ -573,15 +615,20 @@ def main():
         step()
     if dist_on:
         dist.barrier()
-        trainer.exchange_events = []
+        if args.full:
+            trainer.exchange_events = []
     torch.cuda.synchronize()
     probe.enabled = not args.no_probe
     from nerf_rpn_amd import ops as _ops0
     side_stream = _ops0._WGRAD_SIDE["enabled"]
     packs0 = _ops0.PACK_COUNT["conv"] + _ops0.PACK_COUNT["stem"]
+    last = {}
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if args.dump_outputs and i == args.steps - 1:
+            keep[0] = last
         loss = step()
+    keep[0] = None
     torch.cuda.synchronize()
     own_elapsed = time.perf_counter() - t0          # this rank's own K steps (before the closing barrier)
     if dist_on:
@@ -595,27 +642,31 @@ def main():
     per_rank_ms, exch = [round(1e3 * own_elapsed / args.steps, 3)], None
     if dist_on:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        ev = trainer.exchange_events
+        ev = trainer.exchange_events or []      # recorded by --full runs only
         wait_ms = sum(a.elapsed_time(b) for a, b in ev) / max(1, len(ev))
         trainer.exchange_events = None
         mine = torch.tensor([1e3 * own_elapsed / args.steps, wait_ms], device=dev, dtype=torch.float64)
         allr = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
         per_rank_ms = [round(v[0].item(), 3) for v in allr]
-        # comm-only arm: every exchange mode x bucket size on the real arena with no compute in flight (the start-up measurement of
-        # exchange='auto', or taken here when a mode was forced), next to the wait the training steps actually saw
-        startup = dict(trainer.exchange_table) if trainer.exchange_table else None
-        table = trainer.measure_exchange()       # the full table (every mode x bucket size); start-up times only the candidates of 'auto'
-        exch = {"mode": trainer.exchange, "mode_chosen_by": "comm-only measurement at start-up (fastest of the fp32 modes x 16/32/64 MiB; pin with NRPN_GRAD_EXCHANGE / NRPN_GRAD_BUCKET_MIB)" if startup else "--exchange / NRPN_GRAD_EXCHANGE",
-                **({"startup_comm_only_ms": {f"{m}@{mib}MiB": v for (m, mib), v in sorted(startup.items())}} if startup else {}),
-                "comm_only_ms": {f"{m}@{mib}MiB": v for (m, mib), v in sorted(table.items())},
-                "buckets": len(trainer.buckets), "bucket_mib": [round((e - s_) * 4 / 2 ** 20, 1) for s_, e in trainer.buckets],
-                "bytes_per_step_per_rank": int(trainer.g_arena.numel() * 4),
-                "wait_after_backward_ms_per_rank": [round(v[1].item(), 3) for v in allr],
-                "note": "wait = main-stream time between the end of the enqueued backward and the arrival of the last reduced bucket "
-                        "(HIP events around FlatTrainer.sync_gradients): the part of the exchange NOT hidden behind backward"}
+        if args.full:
+            # comm-only arm: every exchange mode x bucket size on the real arena with no compute in flight (the start-up measurement of
+            # exchange='auto', or taken here when a mode was forced), next to the wait the training steps actually saw
+            startup = dict(trainer.exchange_table) if trainer.exchange_table else None
+            table = trainer.measure_exchange()       # the full table (every mode x bucket size); start-up times only the candidates of 'auto'
+            exch = {"mode": trainer.exchange, "mode_chosen_by": "comm-only measurement at start-up (fastest of the fp32 modes x 16/32/64 MiB; pin with NRPN_GRAD_EXCHANGE / NRPN_GRAD_BUCKET_MIB)" if startup else "--exchange / NRPN_GRAD_EXCHANGE",
+                    **({"startup_comm_only_ms": {f"{m}@{mib}MiB": v for (m, mib), v in sorted(startup.items())}} if startup else {}),
+                    "comm_only_ms": {f"{m}@{mib}MiB": v for (m, mib), v in sorted(table.items())},
+                    "buckets": len(trainer.buckets), "bucket_mib": [round((e - s_) * 4 / 2 ** 20, 1) for s_, e in trainer.buckets],
+                    "bytes_per_step_per_rank": int(trainer.g_arena.numel() * 4),
+                    "wait_after_backward_ms_per_rank": [round(v[1].item(), 3) for v in allr],
+                    "note": "wait = main-stream time between the end of the enqueued backward and the arrival of the last reduced bucket "
+                            "(HIP events around FlatTrainer.sync_gradients): the part of the exchange NOT hidden behind backward"}
     elapsed = t.item()
     final_loss = loss.item()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, trainer)
+    last.clear()
     if probe.only is not None:
         timed_records, probe.records, probe.only, probe.enabled = probe.records, [], None, True
         _ops0.set_wgrad_stream(False)       # per-class durations: one kernel at a time (no overlap with the weight-gradient stream)
@@ -630,7 +681,7 @@ def main():
     # idle at its start (synchronise, then time until step() returns) -- the step is host-bound once this exceeds the GPU time
     # (every rank runs these steps -- a step holds the gradient exchange's collectives -- rank 0 reports its own figures)
     host = None
-    if True:
+    if args.full:
         from nerf_rpn_amd import ops as _opsh
         cnt = [0]
         orig_call = _opsh.call

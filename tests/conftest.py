@@ -1,7 +1,12 @@
 import os
 import sys
 
-import pytest
+# MKL picks its sgemm kernels by CPU (AVX-512 on one host, AVX2 on another), and the bit-exact host fixtures (tests/golden/datasets.npz,
+# roipool.npz) go through small matmuls: its reproducible branch gives the same bits on every x86-64 CPU.  Set before torch loads MKL.
+MKL_CBWR_SET_HERE = "MKL_CBWR" not in os.environ
+os.environ.setdefault("MKL_CBWR", "COMPATIBLE")
+
+import pytest  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "tests")):
