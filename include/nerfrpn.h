@@ -603,6 +603,38 @@ int nrpn_reduce_slices(const float *partials, int slices, int64_t count, float *
                        int wrows, int cout, float *gbias, int accumulate_bias, nrpn_stream_t stream);
 size_t nrpn_conv3d_wgrad_bias_offset(int n, int gx, int gy, int gz, int ksize);
 
+/* ------------------------------------------------------------------------------------------------
+ * Proposal heatmap rendering of scripts/render_heatmap.py.  [f4]  Volumes are f32 [x][y][z], z fastest.
+ * nrpn_heatmap_splat: generate_heatmap's box loop (render_heatmap.py:196-204) with gkern_3d (:21-33).  aabbs i32 [K][6] =
+ *   (x1, y1, z1, x2, y2, z2), half-open [x1, x2) like the reference's slices; every voxel of `out` is written (no memset needed).
+ *   NRPN_HEATMAP_GAUSSIAN: factors f64 = per box gx [x2-x1] | gy [y2-y1] | gz [z2-z1], box k's gx at factor_offsets[k] (i32 [K]); a voxel
+ *   adds (gx[i] * gy[j]) * gz[k] in f64 to its f64-widened value, rounded to f32 after each box, boxes in order (numpy's
+ *   f32 += f64: bit-identical).  NRPN_HEATMAP_BOX: every factor is 1 (factors / factor_offsets unused).
+ * nrpn_gaussian_filter3d: scipy.ndimage.gaussian_filter(in, sigma) (:205) with mode 'reflect' and truncate 4: radius = int(4 sigma + 0.5),
+ *   weights f64 [2 radius + 1] = exp(-0.5 / sigma^2 x^2) / sum (scipy's _gaussian_kernel1d).  Axes x, y, z in turn (in -> out -> work ->
+ *   out, three distinct buffers), f64 accumulation in scipy's order, f32 after each axis: bit-identical.  sigma <= 1e-15 copies.
+ * nrpn_heatmap_standardize: out = (in - mean) / std, ddof 0 (:206-207); f64 sums over a fixed tree (no atomics: run-to-run identical),
+ *   mean and std rounded to f32, then f32 arithmetic.  work: f64 [nrpn_heatmap_work_doubles()]; mean_std (optional) f32 [2].
+ * nrpn_render_mip: maximum-intensity render replacing render_volume (:243-305; pyvista add_volume(cmap='jet', opacity='linear',
+ *   blending='maximum')), semantics defined here:
+ *   V = heatmap[::d, ::d, ::d] * value_scale (f32), cell (i,j,k) = [i,i+1) x [j,j+1) x [k,k+1).  cams f64 [F][6] = camera position,
+ *   focal point (frame2config :220-241, in units of V's cells); up (0,0,1), vertical field of view 60 degrees; f = normalize(focal - pos),
+ *   r = normalize(f x up), u = r x f; pixel (x, y) centre (x+0.5, y+0.5), row 0 on top.  The ray pos + s dir, s > 0, visits every cell it
+ *   crosses with positive length (Amanatides-Woo, from inside the volume if the camera is inside); m = max of V over them.
+ *   t = clamp((m - lo) / (hi - lo), 0, 1), lo / hi = min / max of V; rgb = rint(255 * jet[min(int(t * 256), 255)] * t) (jet f64 [256][3]);
+ *   a ray that misses V is black.  rgb u8 [F][height][width][3]; mip (optional) f32 [F][height][width] = m (-inf on a miss).
+ *   work: f64 [nrpn_heatmap_work_doubles()].
+ * ---------------------------------------------------------------------------------------------- */
+enum nrpn_heatmap_kernel { NRPN_HEATMAP_GAUSSIAN = 0, NRPN_HEATMAP_BOX = 1 };
+int nrpn_heatmap_splat(const int32_t *aabbs, int num_boxes, const double *factors, const int32_t *factor_offsets, int kernel_type,
+                       int x, int y, int z, float *out, nrpn_stream_t stream);
+int nrpn_gaussian_filter3d(const float *in, int x, int y, int z, float sigma, int radius, const double *weights, float *work, float *out,
+                           nrpn_stream_t stream);
+int nrpn_heatmap_work_doubles(void);
+int nrpn_heatmap_standardize(const float *in, int64_t n, double *work, float *out, float *mean_std, nrpn_stream_t stream);
+int nrpn_render_mip(const float *heatmap, int x, int y, int z, int downsample, float value_scale, const double *cams, int num_frames,
+                    const double *jet, int width, int height, double *work, uint8_t *rgb, float *mip, nrpn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2184,3 +2184,125 @@ class RoiPoolFn(torch.autograd.Function):
                      o0, o1, o2, _p(df), _p(ws), code, _s())
             grads.append(df.permute(3, 0, 1, 2))
         return (None, None, None, None, None, *grads)
+
+
+# ======================================================================================================================
+# proposal heatmap (scripts/render_heatmap.py)  [f4]
+# ======================================================================================================================
+HEATMAP_KERNELS = {"gaussian": 0, "box": 1}      # enum nrpn_heatmap_kernel
+
+# matplotlib's piecewise-linear 'jet' segment data (x, y0, y1), written out so the product does not import matplotlib
+_JET_SEGMENTS = (((0.00, 0, 0), (0.35, 0, 0), (0.66, 1, 1), (0.89, 1, 1), (1.00, 0.5, 0.5)),
+                 ((0.000, 0, 0), (0.125, 0, 0), (0.375, 1, 1), (0.640, 1, 1), (0.910, 0, 0), (1.000, 0, 0)),
+                 ((0.00, 0.5, 0.5), (0.11, 1, 1), (0.34, 1, 1), (0.65, 0, 0), (1.00, 0, 0)))
+
+
+def jet_table(n=256):
+    """float64 [n,3]: the 'jet' colormap's lookup table, built as a LinearSegmentedColormap builds it (linear interpolation of the
+    segment data at linspace(0, 1, n), clipped to [0, 1])."""
+    import numpy as np
+    cols = []
+    for seg in _JET_SEGMENTS:
+        a = np.array(seg, dtype=np.float64)
+        x, y0, y1 = a[:, 0], a[:, 1], a[:, 2]
+        xi = np.linspace(0, 1, n)
+        ind = np.searchsorted(x, xi)[1:-1]
+        dist = (xi[1:-1] - x[ind - 1]) / (x[ind] - x[ind - 1])
+        cols.append(np.clip(np.concatenate([[y1[0]], dist * (y0[ind] - y1[ind - 1]) + y1[ind - 1], [y0[-1]]]), 0, 1))
+    return np.stack(cols, axis=1)
+
+
+def gkern_factors(w):
+    """1-D factor of the reference's gkern_3d (render_heatmap.py:21-33) for a box extent w, float64 [w], computed with numpy exactly as
+    the reference computes it (the 3-D kernel is their outer product)."""
+    import numpy as np
+    a = np.linspace(-(w - 1) / 2., (w - 1) / 2., w)
+    return np.exp(-0.5 * np.square(a) / np.square(w / 5))
+
+
+def heatmap_factor_tables(aabbs):
+    """aabbs int [K,6] -> (factors float64 [sum of extents], offsets int32 [K]): gx | gy | gz of every box, box k's gx at offsets[k]."""
+    import numpy as np
+    parts, offs, at = [], [], 0
+    for b in np.asarray(aabbs).reshape(-1, 6):
+        offs.append(at)
+        for e in (b[3] - b[0], b[4] - b[1], b[5] - b[2]):
+            f = gkern_factors(e) if e > 0 else np.zeros(0)
+            parts.append(f)
+            at += f.size
+    return (np.concatenate(parts) if parts else np.zeros(0)).astype(np.float64), np.array(offs, dtype=np.int32)
+
+
+def gaussian_weights(sigma, truncate=4.0):
+    """scipy.ndimage's gaussian_filter1d kernel (order 0): (radius, float64 [2 radius + 1])."""
+    import numpy as np
+    sd = float(sigma)
+    radius = int(truncate * sd + 0.5)
+    x = np.arange(-radius, radius + 1)
+    phi = np.exp(-0.5 / (sd * sd) * x ** 2)
+    return radius, phi / phi.sum()
+
+
+def heatmap_splat(aabbs, shape, kernel_type="gaussian", device="cuda"):
+    """generate_heatmap's box loop: aabbs int [K,6] (half-open, clipped) -> float32 [X,Y,Z] on `device` (bit-identical to numpy)."""
+    import numpy as np
+    if kernel_type not in HEATMAP_KERNELS:
+        raise lib.NrpnError(f"heatmap_splat: unknown kernel_type {kernel_type!r}")
+    a = np.ascontiguousarray(np.asarray(aabbs).reshape(-1, 6), dtype=np.int32)
+    X, Y, Z = (int(v) for v in shape)
+    out = torch.empty((X, Y, Z), dtype=torch.float32, device=device)
+    boxes = torch.from_numpy(a).to(device)
+    fac = offs = None
+    if kernel_type == "gaussian" and a.shape[0]:
+        f, o = heatmap_factor_tables(a)
+        fac, offs = torch.from_numpy(f if f.size else np.zeros(1)).to(device), torch.from_numpy(o).to(device)
+    _chk(out, boxes, fac, offs)
+    call("heatmap_splat", _p(boxes), a.shape[0], _p(fac), _p(offs), HEATMAP_KERNELS[kernel_type], X, Y, Z, _p(out), _s())
+    return out
+
+
+def gaussian_filter3d(vol, sigma):
+    """scipy.ndimage.gaussian_filter(vol, sigma) of a float32 [X,Y,Z] volume (mode 'reflect', truncate 4), bit-identical."""
+    vol = vol.contiguous()
+    _chk(vol)
+    if vol.dim() != 3 or vol.dtype != torch.float32:
+        raise lib.NrpnError("gaussian_filter3d expects a float32 [X,Y,Z] tensor")
+    sigma = float(sigma)
+    radius, w = gaussian_weights(sigma) if sigma == sigma and sigma >= 0 else (0, None)
+    wt = torch.from_numpy(w).to(vol.device) if w is not None else torch.ones(1, dtype=torch.float64, device=vol.device)
+    out, work = torch.empty_like(vol), torch.empty_like(vol)
+    call("gaussian_filter3d", _p(vol), *vol.shape, sigma, radius, _p(wt), _p(work), _p(out), _s())
+    return out
+
+
+def standardize(vol):
+    """(vol - mean) / std (ddof 0) of a float32 tensor -> (out, mean_std float32 [2] on the device)."""
+    vol = vol.contiguous()
+    _chk(vol)
+    if vol.dtype != torch.float32:
+        raise lib.NrpnError("standardize expects a float32 tensor")
+    out = torch.empty_like(vol)
+    ms = torch.empty(2, dtype=torch.float32, device=vol.device)
+    work = torch.empty(query("heatmap_work_doubles"), dtype=torch.float64, device=vol.device)
+    call("heatmap_standardize", _p(vol), vol.numel(), _p(work), _p(out), _p(ms), _s())
+    return out, ms
+
+
+def render_mip(heatmap, cams, downsample=2, value_scale=20.0, width=640, height=480, jet=None, with_mip=False):
+    """Maximum-intensity render of heatmap[::d, ::d, ::d] * value_scale (semantics: include/nerfrpn.h, nrpn_render_mip).
+    cams float [F,6] = (position, focal point) in units of the downsampled grid -> uint8 [F,height,width,3] (+ float32 [F,height,width]
+    ray maxima if with_mip)."""
+    heatmap = heatmap.contiguous()
+    _chk(heatmap)
+    if heatmap.dim() != 3 or heatmap.dtype != torch.float32:
+        raise lib.NrpnError("render_mip expects a float32 [X,Y,Z] tensor")
+    dev = heatmap.device
+    cams = torch.as_tensor(cams, dtype=torch.float64).reshape(-1, 6).contiguous().to(dev)
+    jet = torch.as_tensor(jet_table() if jet is None else jet, dtype=torch.float64).contiguous().to(dev)
+    F = int(cams.shape[0])
+    rgb = torch.empty((F, int(height), int(width), 3), dtype=torch.uint8, device=dev)
+    mip = torch.empty((F, int(height), int(width)), dtype=torch.float32, device=dev) if with_mip else None
+    work = torch.empty(query("heatmap_work_doubles"), dtype=torch.float64, device=dev)
+    call("render_mip", _p(heatmap), *heatmap.shape, int(downsample), float(value_scale), _p(cams), F, _p(jet), int(width), int(height),
+         _p(work), _p(rgb), _p(mip), _s())
+    return (rgb, mip) if with_mip else rgb
