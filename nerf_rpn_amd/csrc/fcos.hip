@@ -41,7 +41,9 @@ template <> struct gvec4<bf16s> {
   }
 };
 
-// per-(sample, channel) sums over the sample's rows: fwd (sum x, sum x^2), bwd (sum g, sum g*x) with g = dy * relu mask.
+// per-(sample, channel) sums over the sample's rows: fwd (sum d, sum d^2) with d = x - K, K = x[n, row 0, first channel of the group]
+// (gn_finalize_fwd_kernel reads K back); bwd (sum g, sum g * (x - mean)) with g = dy * relu mask.  Both are shifted so that they do not
+// cancel when |mean| >> std: the unshifted sum x^2 - count * mean^2 in fp32 lost 1.6e-3 of rstd at mean / std = 100.
 // Block = one slab of rows of one sample; thread = (4-channel group, row lane), 8/16-byte loads, 4 rows in flight per thread;
 // the row lanes are reduced through LDS and the block writes ONE partial row [C][2]; gn_reduce_kernel sums the partial rows
 // into ws[n][c][2].  (The first version added every block's sums with fp32 atomics and read one element per thread.)
@@ -50,7 +52,8 @@ static inline int gn_slab(long long rows) { const long long s = (rows + kGnMaxPa
 
 template <typename T, bool BWD>
 __global__ void __launch_bounds__(256) gn_partial_kernel(const T *__restrict__ x, const T *__restrict__ y, const T *__restrict__ dy,
-                                                         float *__restrict__ partial, long long rows, int c, int relu, int nparts, int slab) {
+                                                         const float *__restrict__ mean, float *__restrict__ partial, long long rows, int c,
+                                                         int groups, int relu, int nparts, int slab) {
   __shared__ float red[2][256][4];
   const int n = blockIdx.y;
   const int ct = c / 4;                        // 4-channel groups (<= 256)
@@ -60,6 +63,13 @@ __global__ void __launch_bounds__(256) gn_partial_kernel(const T *__restrict__ x
   const long long base = (long long)n * rows;
   float s0[4] = {0.f, 0.f, 0.f, 0.f}, s1[4] = {0.f, 0.f, 0.f, 0.f};
   if (ty < lanes) {
+    const int cpg = c / groups;
+    float sh[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int grp = (tx * 4 + k) / cpg;
+      sh[k] = BWD ? mean[n * groups + grp] : elem<T>::ld(x + base * c + grp * cpg);
+    }
 #pragma unroll 4
     for (long long r = r0 + ty; r < r1; r += lanes) {
       const long long o = (base + r) * c + tx * 4;
@@ -67,7 +77,7 @@ __global__ void __launch_bounds__(256) gn_partial_kernel(const T *__restrict__ x
       gvec4<T>::ld(x + o, xv);
       if (!BWD) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { s0[k] += xv[k]; s1[k] += xv[k] * xv[k]; }
+        for (int k = 0; k < 4; ++k) { const float d = xv[k] - sh[k]; s0[k] += d; s1[k] += d * d; }
       } else {
         float g[4], yv[4] = {1.f, 1.f, 1.f, 1.f};
         gvec4<T>::ld(dy + o, g);
@@ -75,7 +85,7 @@ __global__ void __launch_bounds__(256) gn_partial_kernel(const T *__restrict__ x
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const float gk = (relu && !(yv[k] > 0.f)) ? 0.f : g[k];
-          s0[k] += gk; s1[k] += gk * xv[k];
+          s0[k] += gk; s1[k] += gk * (xv[k] - sh[k]);
         }
       }
     }
@@ -116,17 +126,19 @@ __global__ void gn_reduce_kernel(const float *__restrict__ partial, float *__res
   }
 }
 
-__global__ void gn_finalize_fwd_kernel(const float *__restrict__ ws, float *__restrict__ mean, float *__restrict__ rstd, int ng, int c,
-                                       int groups, float count, float eps) {
+// mean = K + s0 / count, var = s1 / count - (s0 / count)^2 of the shifted sums, finished in fp64
+template <typename T>
+__global__ void gn_finalize_fwd_kernel(const float *__restrict__ ws, const T *__restrict__ x, long long rows, float *__restrict__ mean,
+                                       float *__restrict__ rstd, int ng, int c, int groups, double count, float eps) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= ng) return;
   const int n = i / groups, g = i % groups, cpg = c / groups;
-  float s0 = 0.f, s1 = 0.f;
+  double s0 = 0.0, s1 = 0.0;
   for (int k = 0; k < cpg; ++k) { s0 += ws[((long long)n * c + g * cpg + k) * 2]; s1 += ws[((long long)n * c + g * cpg + k) * 2 + 1]; }
-  const float m = s0 / count;
-  const float var = fmaxf(s1 / count - m * m, 0.f);
-  mean[i] = m;
-  rstd[i] = 1.0f / sqrtf(var + eps);
+  const double d = s0 / count;
+  const double var = fmax(s1 / count - d * d, 0.0);
+  mean[i] = (float)((double)elem<T>::ld(x + (long long)n * rows * c + g * cpg) + d);
+  rstd[i] = (float)(1.0 / sqrt(var + (double)eps));
 }
 
 template <typename T>
@@ -231,7 +243,7 @@ static inline int gn_fast_blocks(long long rows, int c) {
   return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
 }
 
-// per (sample, group): A = mean_c(g gamma xhat), B = mean_c(g gamma)
+// per (sample, group): A = mean_c(g gamma xhat), B = mean_c(g gamma); ws holds (sum g, sum g * (x - mean))
 __global__ void gn_finalize_bwd_kernel(const float *__restrict__ ws, const float *__restrict__ mean, const float *__restrict__ rstd,
                                        const float *__restrict__ gamma, float *__restrict__ coef, int ng, int c, int groups, float count) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -241,7 +253,7 @@ __global__ void gn_finalize_bwd_kernel(const float *__restrict__ ws, const float
   for (int k = 0; k < cpg; ++k) {
     const int ch = g * cpg + k;
     const float s0 = ws[((long long)n * c + ch) * 2], s1 = ws[((long long)n * c + ch) * 2 + 1];
-    A += gamma[ch] * (s1 - mean[i] * s0) * rstd[i];
+    A += gamma[ch] * s1 * rstd[i];
     B += gamma[ch] * s0;
   }
   coef[i * 2] = A / count;
@@ -256,7 +268,7 @@ __global__ void gn_param_grad_kernel(const float *__restrict__ ws, const float *
   float dg = 0.f, db = 0.f;
   for (int s = 0; s < n; ++s) {
     const float s0 = ws[((long long)s * c + ch) * 2], s1 = ws[((long long)s * c + ch) * 2 + 1];
-    dg += (s1 - mean[s * groups + g] * s0) * rstd[s * groups + g];
+    dg += s1 * rstd[s * groups + g];
     db += s0;
   }
   dgamma[ch] = acc ? dgamma[ch] + dg : dg;       // acc: added to the gradient-arena slots instead of a torch add per parameter
@@ -301,11 +313,11 @@ extern "C" int nrpn_groupnorm_fwd(const void *x, void *y, const float *gamma, co
   float *partial = ws + (size_t)n * c * 2 + (size_t)n * groups * 2;
   const int slab = gn_slab(rows), nparts = (int)cdiv64(rows, slab);
   DISPATCH_T(dtype, hipLaunchKernelGGL((gn_partial_kernel<T, false>), dim3(nparts, n), dim3(256), 0, st, (const T *)x, (const T *)nullptr,
-                                       (const T *)nullptr, partial, (long long)rows, c, 0, nparts, slab));
+                                       (const T *)nullptr, (const float *)nullptr, partial, (long long)rows, c, groups, 0, nparts, slab));
   hipLaunchKernelGGL(gn_reduce_kernel, dim3((c + 63) / 64, n), dim3(64, 16), 0, st, (const float *)partial, ws, nparts, c);
   const int ng = n * groups;
-  hipLaunchKernelGGL(gn_finalize_fwd_kernel, dim3((ng + 63) / 64), dim3(64), 0, st, ws, mean, rstd, ng, c, groups,
-                     (float)((double)rows * (c / groups)), eps);
+  DISPATCH_T(dtype, hipLaunchKernelGGL(gn_finalize_fwd_kernel<T>, dim3((ng + 63) / 64), dim3(64), 0, st, (const float *)ws, (const T *)x, (long long)rows,
+                                       mean, rstd, ng, c, groups, (double)rows * (c / groups), eps));
   const long long total = (long long)n * rows * c;
   if (gn_fast_ok(c, groups, dtype)) {
     hipLaunchKernelGGL(gn_apply_fast_kernel, dim3(gn_fast_blocks(rows, c), n), dim3(256), 0, st, (const bf16s *)x, (bf16s *)y, mean, rstd, gamma, beta,
@@ -330,7 +342,7 @@ extern "C" int nrpn_groupnorm_bwd(const void *x, const void *y, const void *dy, 
   float *partial = coef + (size_t)n * groups * 2;
   const int slab = gn_slab(rows), nparts = (int)cdiv64(rows, slab);
   DISPATCH_T(dtype, hipLaunchKernelGGL((gn_partial_kernel<T, true>), dim3(nparts, n), dim3(256), 0, st, (const T *)x, (const T *)y, (const T *)dy,
-                                       partial, (long long)rows, c, relu, nparts, slab));
+                                       mean, partial, (long long)rows, c, groups, relu, nparts, slab));
   hipLaunchKernelGGL(gn_reduce_kernel, dim3((c + 63) / 64, n), dim3(64, 16), 0, st, (const float *)partial, ws, nparts, c);
   const int ng = n * groups;
   hipLaunchKernelGGL(gn_finalize_bwd_kernel, dim3((ng + 63) / 64), dim3(64), 0, st, ws, mean, rstd, gamma, coef, ng, c, groups,

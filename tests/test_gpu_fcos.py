@@ -29,11 +29,11 @@ def fcos_args(rot, **kw):
     return argparse.Namespace(**a)
 
 
-def build(rot, backbone, dev, **kw):
+def build(rot, backbone, dev, depths=(2, 2, 18, 2), **kw):
     from nerf_rpn_amd.model.feature_extractor import VGG_FPN, SwinTransformer_FPN
     from nerf_rpn_amd.model.fcos import FCOSOverNeRF
     if backbone == "swin":
-        bb = SwinTransformer_FPN(patch_size=[4, 4, 4], embed_dim=96, depths=[2, 2, 18, 2], num_heads=[3, 6, 12, 24], window_size=[4, 4, 4],
+        bb = SwinTransformer_FPN(patch_size=[4, 4, 4], embed_dim=96, depths=list(depths), num_heads=[3, 6, 12, 24], window_size=[4, 4, 4],
                                  stochastic_depth_prob=0, expand_dim=True)
     else:
         bb = VGG_FPN("EF", 4, True, 160)

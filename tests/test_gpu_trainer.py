@@ -54,6 +54,34 @@ def test_flat_trainer_arena_equals_autograd_grads(golden, dev):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_flat_trainer_arena_equals_autograd_grads_swin_fcos(dtype, dev):
+    """The same standard for Swin + FCOS, which trains through the accumulate flags of the LayerNorm, GroupNorm and window-attention
+    finishing kernels (they add straight into the arena slots): depths 2,2,2,2, no stochastic depth, a grid that needs window padding."""
+    from nerf_rpn_amd.engine import FlatTrainer
+    from test_gpu_fcos import build as build_fcos, scene as fcos_scene
+    x = fcos_scene((40, 36, 44), 3).to(dev)
+    gt = torch.tensor([[20., 18., 16., 14., 12., 10., 0.3], [12., 24., 30., 10., 9., 12., -0.8]], device=dev)
+
+    def loss_of(model):
+        _, ls, _ = model([x], [gt])
+        return ls["loss_cls"] + ls["loss_reg"] + ls["loss_centerness"]
+
+    ref = build_fcos(True, "swin", dev, depths=(2, 2, 2, 2)).train()
+    ref.set_compute_dtype(dtype)
+    loss_of(ref).backward()
+    plain = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).reshape(-1).float() for p in ref.parameters() if p.requires_grad])
+    m = build_fcos(True, "swin", dev, depths=(2, 2, 2, 2)).train()
+    m.set_compute_dtype(dtype)
+    tr = FlatTrainer(m, lr=1e-4, weight_decay=0.01, clip_grad_norm=0.1)
+    for _ in range(2):
+        tr.g_arena.zero_()
+        loss_of(m).backward()
+        tr.sync_gradients()
+        got = tr.flat_grads()
+        assert torch.equal(got, plain), (got - plain).abs().max().item() / plain.abs().max().item()
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_flat_trainer_trains_like_torch_adamw(dtype, golden, dev):
     """Three optimiser steps.  The GEMM-layout weight copies must follow the raw-pointer AdamW update (round-1 bug: they were
     cached on tensor._version and every conv kept the step-0 weights): the loss trajectory and the weights must track the same
