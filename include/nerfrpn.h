@@ -635,6 +635,38 @@ int nrpn_heatmap_standardize(const float *in, int64_t n, double *work, float *ou
 int nrpn_render_mip(const float *heatmap, int x, int y, int z, int downsample, float value_scale, const double *cams, int num_frames,
                     const double *jet, int width, int height, double *work, uint8_t *rgb, float *mip, nrpn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * PLY export of scripts/visualize_rpn_input.py.  [f4]  Grids are f32 [x][y][z], z fastest.
+ * nrpn_zoom_cubic3d: scipy.ndimage.zoom(in, factors, order=3) (the call in get_objectness_grid, visualize_rpn_input.py:149) with its
+ *   defaults (mode 'constant', prefilter, grid_mode False) onto [ox][oy][oz], bit-identical: the B-spline prefilter (pole
+ *   -0.267949192431122706472553658494127633, gain first, mirror initialisation, axes x, y, z; lines of length 1 unchanged) in f64 into
+ *   coef f64 [nx][ny][nz], then 4 x 4 x 4 taps at o * (n - 1) / (no - 1) per axis (whole-sample mirrored indices, weights and summation
+ *   in scipy's order), 0 where that coordinate exceeds n - 1, f32 out.  h_zpow: host f64 [3] = pow(pole, n - 1) of each axis (libm pow).
+ * nrpn_objectness_grid: get_objectness_grid (:145-156): score = sum over the levels, in order, of float32 zoom(level) onto [x][y][z],
+ *   accumulated in f64 from 0, transposed to point order p = (k * y + j) * x + i, divided by its maximum (NaN propagates; fixed tree,
+ *   run-to-run identical).  levels: the level grids f32 laid end to end; h_level_dims host int32 [num_levels][3], h_zpow host f64
+ *   [num_levels][3] as above; num_levels 1 .. 8.  coef f64 [total level elements]; work f64 [nrpn_objectness_work_doubles()];
+ *   score f64 [x * y * z].
+ * nrpn_ply_points_count / nrpn_ply_points_write: the grid rows of write_rgb_to_ply / write_objectness_heatmap_to_ply (:127-142) with
+ *   construct_grid (:21-42), byte-identical.  Point p = (z * sy + y) * sx + x takes rgbsigma f32 [sx][sy][sz][4] at (x, y, z) (the
+ *   reference's transpose(2, 1, 0, 3)) and the grid coordinates of p decomposed by the resolution (rx, ry, rz), x fastest:
+ *   linspace(0, n, n)[k] / max(r) + 0.5 * (1.0 / max(r)) in f64.  It is kept when clip(1 - exp(-exp(sigma) / 100), 0, 1) > alpha_threshold
+ *   in f32; its row is  "%.6f %.6f %.6f %u %u %u\n"  (exact decimal rounding, half-even) with rgb = (uint8)(clamp(c, 0, 1) * 255) when
+ *   score is null, else turbo u8 [256][3] at int(score[p] * 256) (matplotlib's rule: 1 -> 255, below 0 -> 0, from 256 -> 255; NaN ->
+ *   0 0 0).  count writes per-workgroup sums and their scan into work int64 [nrpn_ply_points_work_int64(n)] and totals int64 [2] =
+ *   (kept points, bytes); write (same arguments, after count) fills out u8 [bytes] in point order.  sx * sy * sz == rx * ry * rz.
+ * ---------------------------------------------------------------------------------------------- */
+int nrpn_zoom_cubic3d(const float *in, int nx, int ny, int nz, const double *h_zpow, int ox, int oy, int oz, double *coef, float *out,
+                      nrpn_stream_t stream);
+int nrpn_objectness_work_doubles(void);
+int nrpn_objectness_grid(const float *levels, const int32_t *h_level_dims, const double *h_zpow, int num_levels, int x, int y, int z,
+                         double *coef, double *work, double *score, nrpn_stream_t stream);
+int64_t nrpn_ply_points_work_int64(int64_t n);
+int nrpn_ply_points_count(const float *rgbsigma, int sx, int sy, int sz, int rx, int ry, int rz, float alpha_threshold, const double *score,
+                          const uint8_t *turbo, int64_t *work, int64_t *totals, nrpn_stream_t stream);
+int nrpn_ply_points_write(const float *rgbsigma, int sx, int sy, int sz, int rx, int ry, int rz, float alpha_threshold, const double *score,
+                          const uint8_t *turbo, const int64_t *work, uint8_t *out, nrpn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
