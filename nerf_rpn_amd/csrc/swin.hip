@@ -395,6 +395,14 @@ __global__ void __launch_bounds__(64) window_attn_fwd_kernel(const T *__restrict
   }
 }
 
+// dP_ij = sum_d dO_id V_jd as one chain of fused multiply-adds: the same bits wherever it is evaluated
+__device__ __forceinline__ float attn_dp(const float (&dO)[HD], const float *v) {
+  float dp = 0.f;
+#pragma unroll
+  for (int d = 0; d < HD; ++d) dp = __builtin_fmaf(dO[d], v[d], dp);
+  return dp;
+}
+
 // backward: recompute P, then dV = P^T dO, dS = P (dP - rowdot), dq = scale dS K, dK = dS^T (scale q), dbias_table += dS
 template <typename T>
 __global__ void __launch_bounds__(64) window_attn_bwd_kernel(const T *__restrict__ qkv, const float *__restrict__ qkv_bias,
@@ -467,15 +475,13 @@ __global__ void __launch_bounds__(64) window_attn_bwd_kernel(const T *__restrict
       for (int d = 0; d < HD; ++d) atomicAdd(&padacc[HD + d], dv[d]);
     }
   }
-  // rowdot_i = sum_j dP_ij P_ij
+  // rowdot_i = sum_j dP_ij P_ij.  dP is formed twice (here and for dS below) and dS = P (dP - rowdot) relies on both being the SAME bits:
+  // on a near-one-hot row rowdot is dP of the selected key, and the difference has to cancel to the last bit.  Written as `dp += a * b`
+  // the compiler fused one loop and split the other into packed multiplies and adds, which left an error of 2^-24 sum_d |dO V| (not
+  // 2^-24 |dP|) in dS; explicit fused multiply-adds pin one rounding sequence for both (attn_dp).
   float rowdot = 0.f;
 #pragma unroll 2
-  for (int j = 0; j < WT; ++j) {
-    float dp = 0.f;
-#pragma unroll
-    for (int d = 0; d < HD; ++d) dp += dO[d] * V[j][d];
-    rowdot += dp * M[i][j];
-  }
+  for (int j = 0; j < WT; ++j) rowdot += attn_dp(dO, V[j]) * M[i][j];
   __syncthreads();
   // dS row of query i (overwrites P row i), dq, bias-table gradient
   {
@@ -484,9 +490,7 @@ __global__ void __launch_bounds__(64) window_attn_bwd_kernel(const T *__restrict
     for (int d = 0; d < HD; ++d) dq[d] = 0.f;
 #pragma unroll 2
     for (int j = 0; j < WT; ++j) {
-      float dp = 0.f;
-#pragma unroll
-      for (int d = 0; d < HD; ++d) dp += dO[d] * V[j][d];
+      const float dp = attn_dp(dO, V[j]);
       const float ds = M[i][j] * (dp - rowdot);
       M[i][j] = ds;
 #pragma unroll

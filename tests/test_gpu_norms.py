@@ -528,45 +528,6 @@ def test_arena_slots_batchnorm(dtype, dev):
     assert torch.equal(slots[0], pre[0] + gg) and torch.equal(slots[1], pre[1] + gb)
 
 
-def _attn_core_ref(qkv, table, index, heads, shift, ws=4):
-    """fp64 attention core on an unpadded [B, X, Y, Z, 3C] qkv tensor (oracle.nets.window_attention without the Linears and the padding);
-    returns the output and the score tensor after the bias add, whose gradient is the per-window term of the table gradient."""
-    B, H, W, D, C3 = qkv.shape
-    C = C3 // 3
-    sh = [0 if ws >= p else shift for p in (H, W, D)]
-    x = torch.roll(qkv, shifts=(-sh[0], -sh[1], -sh[2]), dims=(1, 2, 3)) if sum(sh) else qkv
-
-    def partition(t):
-        lead, c = t.shape[:-4], t.shape[-1]
-        t = t.reshape(*lead, H // ws, ws, W // ws, ws, D // ws, ws, c)
-        n = len(lead)
-        return t.permute(*range(n), n, n + 2, n + 4, n + 1, n + 3, n + 5, n + 6).reshape(-1, ws ** 3, c)
-
-    xw = partition(x).reshape(-1, ws ** 3, 3, heads, C // heads).permute(2, 0, 3, 1, 4)
-    q, k, v = xw[0] * (C // heads) ** -0.5, xw[1], xw[2]
-    s = q @ k.transpose(-2, -1) + table[index].view(ws ** 3, ws ** 3, -1).permute(2, 0, 1).unsqueeze(0)
-    s.retain_grad()
-    a = s
-    if sum(sh):
-        region = x.new_zeros((H, W, D))
-        cnt = 0
-        for h in ((0, -ws), (-ws, -sh[0]), (-sh[0], None)):
-            for w in ((0, -ws), (-ws, -sh[1]), (-sh[1], None)):
-                for d in ((0, -ws), (-ws, -sh[2]), (-sh[2], None)):
-                    region[h[0]:h[1], w[0]:w[1], d[0]:d[1]] = cnt
-                    cnt += 1
-        rr = partition(region[..., None])[..., 0]
-        mask = rr.unsqueeze(1) - rr.unsqueeze(2)
-        mask = torch.where(mask != 0, torch.full_like(mask, -100.0), torch.zeros_like(mask))
-        nW = rr.shape[0]
-        a = (a.view(B, nW, heads, ws ** 3, ws ** 3) + mask[None, :, None]).view(-1, heads, ws ** 3, ws ** 3)
-    y = (F.softmax(a, dim=-1) @ v).transpose(1, 2).reshape(-1, ws ** 3, C)
-    y = y.view(B, H // ws, W // ws, D // ws, ws, ws, ws, C).permute(0, 1, 4, 2, 5, 3, 6, 7).reshape(B, H, W, D, C)
-    if sum(sh):
-        y = torch.roll(y, shifts=(sh[0], sh[1], sh[2]), dims=(1, 2, 3))
-    return y, s
-
-
 @pytest.mark.parametrize("shift", [0, 2])
 def test_arena_slot_window_attention_table(shift, dev):
     """The relative-position bias table's gradient: added into a contiguous slot by the table reduction itself (direct), or handed back and
@@ -581,13 +542,10 @@ def test_arena_slot_window_attention_table(shift, dev):
     qkv = torch.randn(*shape, 3 * c, generator=g)
     dout = torch.randn(*shape, c, generator=g)
     table = torch.randn(343, heads, generator=g) * 0.5
-    q64, t64 = qkv.double(), table.double().requires_grad_()
-    y64, s = _attn_core_ref(q64, t64, index, heads, shift)
-    y64.backward(dout.double())
-    dt64 = t64.grad
+    from attention_ref import attn_core_ref      # the fp64 attention core shared with test_gpu_attention.py
+    ref = attn_core_ref(qkv.double(), None, table.double(), index, heads, shift, dout=dout.double())
     # sum |terms|: |score gradient| of every window and (i, j), scattered onto the table entries
-    sabs = s.grad.abs().sum(0).permute(1, 2, 0).reshape(-1, heads)
-    terms = torch.zeros(343, heads, dtype=torch.float64).index_add_(0, index, sabs)
+    dt64, terms = ref.dtable, ref.terms["dtable"]
     tp = table.to(dev).requires_grad_()
     pre = _prefills([(343, heads)], 53, dev)
     got = {}

@@ -163,13 +163,15 @@ def test_bf16_mfma_attention_matches_valu_kernels(shape, heads, shift, dev):
     x = torch.randn(b, h, w, d, c, generator=g).to(dev).bfloat16()
     dy = torch.randn(b, h, w, d, c, generator=g).to(dev).bfloat16()
     res = {}
-    for mode in (0, 1):
-        lib.call("set_window_attn_mfma", mode)
-        xg = x.clone().requires_grad_()
-        y = att(xg)
-        grads = torch.autograd.grad(y, [xg] + list(att.parameters()), dy)
-        res[mode] = [y.float()] + [t.float() for t in grads]
-    lib.call("set_window_attn_mfma", 1)
+    try:
+        for mode in (0, 1):
+            lib.call("set_window_attn_mfma", mode)
+            xg = x.clone().requires_grad_()
+            y = att(xg)
+            grads = torch.autograd.grad(y, [xg] + list(att.parameters()), dy)
+            res[mode] = [y.float()] + [t.float() for t in grads]
+    finally:
+        lib.call("set_window_attn_mfma", 1)
     names = ["y", "x"] + [n for n, _ in att.named_parameters()]
     for n, a, r in zip(names, res[1], res[0]):
         assert rel(a, r) < 3e-2, (n, rel(a, r))
