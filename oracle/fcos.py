@@ -136,7 +136,7 @@ def targets_for_scene(loc, counts, strides, gt, radius, use_obb):
     """compute_targets_for_locations[_obb], loss.py:318-437 -> labels [K], reg_targets [K, 6|8] (not yet stride-normalised)."""
     D = 8 if use_obb else 6
     if gt.shape[0] == 0:
-        return torch.zeros(loc.shape[0]), torch.zeros(loc.shape[0], D)
+        return torch.zeros(loc.shape[0], dtype=loc.dtype), torch.zeros(loc.shape[0], D, dtype=loc.dtype)
     if use_obb:
         aabb, alpha, beta = obb_summary(gt)
     else:
@@ -152,7 +152,7 @@ def targets_for_scene(loc, counts, strides, gt, radius, use_obb):
     vol[inside == 0] = INF
     vol[cared == 0] = INF
     best, which = vol.min(dim=1)
-    labels = torch.ones(loc.shape[0])
+    labels = torch.ones(loc.shape[0], dtype=loc.dtype)      # (a float32 label would make binary_cross_entropy_with_logits answer in float32)
     labels[best == INF] = 0
     return labels, reg[torch.arange(loc.shape[0]), which]
 
