@@ -667,6 +667,43 @@ int nrpn_ply_points_count(const float *rgbsigma, int sx, int sy, int sz, int rx,
 int nrpn_ply_points_write(const float *rgbsigma, int sx, int sy, int sz, int rx, int ry, int rz, float alpha_threshold, const double *score,
                           const uint8_t *turbo, const int64_t *work, uint8_t *out, nrpn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * ScanNet ground-truth boxes of scripts/scannet_generate_bbox.py.  [f4]  Replaces, for all G instances of a scene at once,
+ * Instance.add_vertices / add_vertex_positions (data/scannet/generate_bbox.py:45-60), find_minimum_bounding_box (:10-27) and
+ * MinimumBoundingBox with bounding_area / to_xy_coordinates (data/scannet/MinimumBoundingBox.py:23-47, 92-119).
+ * Inputs: vertices f32 [V][3]; seg_of_vertex i32 [V]; the instances' segments as a CSR keyed by segment: seg_ids i32 [S] ascending and
+ *   unique, seg_offsets i32 [S + 1], seg_insts i32 [P] -- the instances (0 .. G-1) that list segment seg_ids[k] are
+ *   seg_insts[seg_offsets[k] .. seg_offsets[k + 1]).  A segment may be listed by several instances; each then owns its vertices.
+ * Three calls on one stream, two small read-backs between them:
+ * nrpn_scanbox_count: counts i64 [G] = vertices per instance (the output num_vertices), total i64 [1] = their sum M.
+ * nrpn_scanbox_reduce: membership lists, then per instance min_pt / max_pt f32 [G][3] (exact float32 min / max: bit-equal to numpy),
+ *   obb[2] = f32(min_z + max_z) / 2 and obb[5] = f32(max_z - min_z) widened (the reference's float32 arithmetic), status, and the
+ *   xy points that can still be hull vertices (strict interior of the octagon of 8 support points discarded, float64, conservative).
+ *   counts / num_members are what nrpn_scanbox_count gave for the same inputs; work: nrpn_scanbox_work_bytes(V, G, M) bytes, 16-byte
+ *   aligned, kept for nrpn_scanbox_hull.  info i32 [4] = (largest survivor count, instances with more than nrpn_scanbox_lds_points()
+ *   survivors, 1 if counts did not sum to M -- every instance is then empty, 0).
+ * nrpn_scanbox_hull: max_survivors / num_large = info[0] / info[1].  Convex hull of the survivors: sorted by (x, y), monotone chain with
+ *   cross <= 0 pops in float64 of the float32 coordinates (in LDS up to nrpn_scanbox_lds_points() survivors, in global memory above),
+ *   counter-clockwise from the lexicographically smallest vertex.  Then for every hull edge the rectangle of bounding_area in float64
+ *   (unit vector, projections of all hull vertices, length_parallel * length_orthogonal) and the FIRST edge of minimum area in that
+ *   order: obb f64 [G][7] = (cx, cy, cz, length_parallel, length_orthogonal, dz, angle), angle = atan2(u_y, u_x), centre through
+ *   to_xy_coordinates.  The outputs depend only on the set of vertices of each instance (no float atomics; run-to-run and
+ *   order-of-vertices identical bits).
+ * status i32 [G]: 0 ok; 1 fewer than three vertices; 2 all vertices collinear or coincident (the reference raises in these cases).
+ *   obb is NaN where status != 0; min_pt / max_pt of an instance without vertices are +inf / -inf.
+ * ---------------------------------------------------------------------------------------------- */
+int nrpn_scanbox_lds_points(void);
+int64_t nrpn_scanbox_work_bytes(int64_t num_vertices, int num_instances, int64_t num_members);
+int nrpn_scanbox_count(const int32_t *seg_of_vertex, int64_t num_vertices, const int32_t *seg_ids, const int32_t *seg_offsets,
+                       const int32_t *seg_insts, int num_segs, int num_pairs, int num_instances, int64_t *counts, int64_t *total,
+                       nrpn_stream_t stream);
+int nrpn_scanbox_reduce(const float *vertices, const int32_t *seg_of_vertex, int64_t num_vertices, const int32_t *seg_ids,
+                        const int32_t *seg_offsets, const int32_t *seg_insts, int num_segs, int num_pairs, int num_instances,
+                        const int64_t *counts, int64_t num_members, void *work, int64_t work_bytes, float *min_pt, float *max_pt,
+                        double *obb, int32_t *status, int32_t *info, nrpn_stream_t stream);
+int nrpn_scanbox_hull(int num_instances, int64_t num_members, int max_survivors, int num_large, void *work, int64_t work_bytes,
+                      double *obb, int32_t *status, nrpn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

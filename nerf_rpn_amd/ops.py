@@ -2442,3 +2442,68 @@ def ply_points(rgbsigma, res, alpha_threshold, score=None, turbo=None):
     if nbytes:
         call("ply_points_write", *args, _p(work), _p(out), _s())
     return count, out
+
+
+# ======================================================================================================================
+# ScanNet ground-truth boxes (scripts/scannet_generate_bbox.py)  [f4]
+# ======================================================================================================================
+def segment_csr(instance_segments):
+    """The instances' segment lists (one iterable of segment ids per instance; set semantics, a segment may appear in several
+    instances) -> (seg_ids ascending unique, seg_offsets [S + 1], seg_insts [P]) int32 numpy arrays: the instances of seg_ids[k] are
+    seg_insts[seg_offsets[k]:seg_offsets[k + 1]], ascending."""
+    import numpy as np
+    pairs = sorted({(int(s), g) for g, segs in enumerate(instance_segments) for s in segs})
+    if any(not -2 ** 31 <= s < 2 ** 31 for s, _ in pairs):
+        raise lib.NrpnError("segment ids must fit int32")
+    seg = np.array([s for s, _ in pairs], dtype=np.int32)
+    insts = np.array([g for _, g in pairs], dtype=np.int32)
+    ids, first = np.unique(seg, return_index=True)
+    offs = np.concatenate([first, [len(pairs)]]).astype(np.int32)
+    return ids.astype(np.int32), offs, insts
+
+
+def scannet_instance_boxes(vertices, seg_of_vertex, instance_segments):
+    """Boxes of the G instances of a ScanNet-style scan: vertices float32 [V,3] and seg_of_vertex int32 [V] on the device,
+    instance_segments = G iterables of segment ids -> (min_pt float32 [G,3], max_pt float32 [G,3], obb float64 [G,7], status int32 [G],
+    num_vertices int64 [G]) on the device.
+
+    obb = (cx, cy, cz, length_parallel, length_orthogonal, dz, angle) as the reference's find_minimum_bounding_box returns it: the
+    minimum-area rectangle over the hull edges of the xy projection, in float64 of the float32 coordinates -- what the reference computes
+    under its pinned numpy 1.x, where float32 / float widens; under numpy 2 the same reference code stays in float32 and lands 1e-7 to
+    1e-6 relative away -- and cz, dz in the reference's float32 arithmetic.  Hull edges are taken counter-clockwise from the
+    lexicographically smallest (x, y) hull vertex and the first edge of minimum area wins, so the result depends only on the set of
+    vertices (the reference starts where Qhull does and may pick another edge of exactly equal area).
+    status: 0 ok, 1 fewer than three vertices, 2 all collinear or coincident (the reference raises); obb is NaN there."""
+    import numpy as np
+    _chk(vertices, seg_of_vertex)
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
+        raise lib.NrpnError("scannet_instance_boxes expects float32 [V,3] vertices")
+    V, G = int(vertices.shape[0]), len(instance_segments)
+    if seg_of_vertex.dtype != torch.int32 or tuple(seg_of_vertex.shape) != (V,):
+        raise lib.NrpnError("scannet_instance_boxes expects int32 [V] seg_of_vertex")
+    if G < 1:
+        raise lib.NrpnError("scannet_instance_boxes: no instances")
+    dev = vertices.device
+    ids, offs, insts = (torch.from_numpy(a).to(dev) for a in segment_csr(instance_segments))
+    S, P = int(ids.numel()), int(insts.numel())
+    seg_args = (_p(seg_of_vertex), V, _p(ids), _p(offs), _p(insts), S, P, G)
+    counts = torch.empty(G, dtype=torch.int64, device=dev)
+    total = torch.empty(1, dtype=torch.int64, device=dev)
+    call("scanbox_count", *seg_args, _p(counts), _p(total), _s())
+    M = int(total.item())
+    nbytes = lib.query("scanbox_work_bytes", V, G, M)
+    if nbytes < 0:
+        raise lib.NrpnError("scanbox_work_bytes: bad sizes")
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    min_pt = torch.empty((G, 3), dtype=torch.float32, device=dev)
+    max_pt = torch.empty((G, 3), dtype=torch.float32, device=dev)
+    obb = torch.empty((G, 7), dtype=torch.float64, device=dev)
+    status = torch.empty(G, dtype=torch.int32, device=dev)
+    info = torch.empty(4, dtype=torch.int32, device=dev)
+    call("scanbox_reduce", _p(vertices), *seg_args, _p(counts), M, _p(work), nbytes, _p(min_pt), _p(max_pt), _p(obb), _p(status),
+         _p(info), _s())
+    max_surv, num_large, err, _ = (int(v) for v in info.tolist())
+    if err:
+        raise lib.NrpnError("scanbox_reduce: the membership counts changed between the two passes")
+    call("scanbox_hull", G, M, max_surv, num_large, _p(work), nbytes, _p(obb), _p(status), _s())
+    return min_pt, max_pt, obb, status, counts
