@@ -704,6 +704,31 @@ int nrpn_scanbox_reduce(const float *vertices, const int32_t *seg_of_vertex, int
 int nrpn_scanbox_hull(int num_instances, int64_t num_members, int max_survivors, int num_large, void *work, int64_t work_bytes,
                       double *obb, int32_t *status, nrpn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * rgb-sigma grid of a trained NeRF MLP, scripts/nerf_extract.py.  [f5]  Replaces extract_nerf (data/scannet/run_nerf.py:1157-1194)
+ * with run_network (:50-65) for the model of DESIGN.md 3.16: D = 8, W = 256, skips = [4], multires L (input_ch = 3 + 6 L <= 64),
+ * view directions.  The trunk (encoding, pts_linears, feature_linear, alpha_linear and the feature columns W_f of views_linears.0)
+ * runs once per point on the exact-fp32 MFMA; the poses loop over the head only.
+ * nrpn_nerfgrid_work_bytes(what, num_points): what = 0 -> bytes of the packed weights; what = 1 -> bytes of the scratch a chunk of
+ *   num_points points needs (128 floats per point, whole tiles of 64 points); -1 for anything else.
+ * nrpn_nerfgrid_pack (the model create_nerf builds, run_nerf.py:344-358): raw f32, tensors in torch's [out][in] layout back to back:
+ *   pts_linears.0 .. 7 weights ([256][input_ch], [256][256] x 4, [256][input_ch + 256], [256][256] x 2), feature_linear.weight
+ *   [256][256], views_linears.0.weight[:, :256] as [128][256], then pts_linears.0 .. 7 biases, feature_linear.bias, alpha_linear.weight
+ *   [256], alpha_linear.bias [1], rgb_linear.weight [3][128], rgb_linear.bias [3].  packed: nrpn_nerfgrid_work_bytes(0, 0) bytes.
+ * nrpn_nerfgrid_query (extract_nerf, run_nerf.py:1166-1192; run_network :53-55): xs / ys / zs f32 [res_x] / [res_y] / [res_z] are the
+ *   torch.linspace values; point r = (iz * res_y + iy) * res_x + ix is ((xs[ix], ys[iy], zs[iz]) - center) * bb_scale.  ctab f32
+ *   [num_poses][128] = W_d embed_dirs(d_p) + bias of views_linears.0 (the camera embedding is zero, :1177).  out f32, 4 per point:
+ *   mean over the poses, summed in pose order, of sigmoid(rgb) (:1187-1191) and the raw alpha_linear output; layout 0 = (N, 4) rows
+ *   in point order (the reference's array), layout 1 = (res_x, res_y, res_z, 4).  The points are processed chunk at a time (chunk >= 1
+ *   points, rounded up to tiles of 64); work: nrpn_nerfgrid_work_bytes(1, min(chunk, N)) bytes, 16-byte aligned.  No atomics; the
+ *   result does not depend on chunk.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t nrpn_nerfgrid_work_bytes(int what, int64_t num_points);
+int nrpn_nerfgrid_pack(const float *raw, int input_ch, float *packed, nrpn_stream_t stream);
+int nrpn_nerfgrid_query(const float *xs, const float *ys, const float *zs, int res_x, int res_y, int res_z, float center_x,
+                        float center_y, float center_z, float bb_scale, int multires, const float *packed, const float *ctab,
+                        int num_poses, int layout, int64_t chunk, void *work, int64_t work_bytes, float *out, nrpn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

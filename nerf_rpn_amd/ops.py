@@ -2507,3 +2507,112 @@ def scannet_instance_boxes(vertices, seg_of_vertex, instance_segments):
         raise lib.NrpnError("scanbox_reduce: the membership counts changed between the two passes")
     call("scanbox_hull", G, M, max_surv, num_large, _p(work), nbytes, _p(obb), _p(status), _s())
     return min_pt, max_pt, obb, status, counts
+
+
+# ======================================================================================================================
+# rgb-sigma grid of a trained NeRF MLP (scripts/nerf_extract.py)  [f5]
+# ======================================================================================================================
+NERF_GRID_DEFAULT_CHUNK = 1 << 20      # points per trunk / head launch pair: 512 MiB of scratch (128 floats per point)
+_NERF_LAYOUTS = {"flat": 0, "wlh": 1}
+
+
+def nerf_grid_config(cfg):
+    """The options of the training run's args.json (a dict or a namespace) that decide the network -> dict(multires, multires_views,
+    input_ch_cam).  Supported is what run_nerf.py's config_parser defaults to (run_nerf.py:924-1008): netdepth 8, netwidth 256, multires
+    9, use_viewdirs, N_importance 0, i_embed 0, with any multires_views >= 0 and input_ch_cam >= 0; skips is [4] in create_nerf."""
+    get = cfg.get if isinstance(cfg, dict) else lambda k, d=None: getattr(cfg, k, d)
+    fixed = (("netdepth", 8), ("netwidth", 256), ("multires", 9), ("use_viewdirs", True), ("N_importance", 0), ("i_embed", 0))
+    for name, want in fixed:
+        have = get(name, want)
+        if have != want:
+            raise NotImplementedError(f"{name}={have!r}: the HIP NeRF grid kernels are specialised for {name}={want!r}")
+    out = {"multires": 9}
+    for name, default in (("multires_views", 0), ("input_ch_cam", 4)):
+        v = get(name, default)
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise NotImplementedError(f"{name}={v!r}: expected an integer >= 0")
+        out[name] = v
+    return out
+
+
+class NerfGridWeights:
+    """The device-side weights of one NeRF MLP for nerf_grid_query: the packed trunk and rgb_linear (nrpn_nerfgrid_pack), the view
+    columns W_d and the bias of views_linears.0 for the c_p table, and the options they were built for."""
+    def __init__(self, packed, w_dirs, b_views, config):
+        self.packed, self.w_dirs, self.b_views, self.config = packed, w_dirs, b_views, config
+
+
+def nerf_grid_pack(state_dict, cfg):
+    """Upload and pack a checkpoint's network_fn_state_dict once (keys with or without DataParallel's ``module.``) -> NerfGridWeights,
+    which nerf_grid_query accepts in place of the state dict."""
+    c = nerf_grid_config(cfg)
+    if not torch.cuda.is_available():
+        raise lib.NrpnError("nerf_grid_query needs a gfx950 device (the product path has no CPU fallback)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state_dict.items()}
+    W, input_ch, views_ch = 256, 3 + 6 * c["multires"], 3 + 6 * c["multires_views"]
+    want = {f"pts_linears.{i}.weight": (W, input_ch if i == 0 else W + input_ch if i == 5 else W) for i in range(8)}
+    want.update({f"pts_linears.{i}.bias": (W,) for i in range(8)})
+    want.update({"feature_linear.weight": (W, W), "feature_linear.bias": (W,), "alpha_linear.weight": (1, W), "alpha_linear.bias": (1,),
+                 "views_linears.0.weight": (W // 2, views_ch + c["input_ch_cam"] + W), "views_linears.0.bias": (W // 2,),
+                 "rgb_linear.weight": (3, W // 2), "rgb_linear.bias": (3,)})
+    for k, shape in want.items():
+        if k not in sd:
+            raise lib.NrpnError(f"nerf_grid_query: the state dict has no {k}")
+        if tuple(sd[k].shape) != shape:
+            raise lib.NrpnError(f"nerf_grid_query: {k} has shape {tuple(sd[k].shape)}, the configuration implies {shape}")
+    t = {k: sd[k].detach().to(device=dev, dtype=torch.float32) for k in want}
+    wv = t["views_linears.0.weight"]
+    raw = torch.cat([t[f"pts_linears.{i}.weight"].reshape(-1) for i in range(8)]
+                    + [t["feature_linear.weight"].reshape(-1), wv[:, :W].reshape(-1)]
+                    + [t[f"pts_linears.{i}.bias"] for i in range(8)]
+                    + [t["feature_linear.bias"], t["alpha_linear.weight"].reshape(-1), t["alpha_linear.bias"],
+                       t["rgb_linear.weight"].reshape(-1), t["rgb_linear.bias"]]).contiguous()
+    packed = torch.empty(lib.query("nerfgrid_work_bytes", 0, 0) // 4, dtype=torch.float32, device=dev)
+    call("nerfgrid_pack", _p(raw), input_ch, _p(packed), _s())
+    return NerfGridWeights(packed, wv[:, W:W + views_ch].contiguous(), t["views_linears.0.bias"], c)
+
+
+def nerf_grid_query(state_dict, cfg, xs, ys, zs, bb_center, bb_scale, poses, layout="flat", chunk=None):
+    """extract_nerf of the reference's run_nerf.py (:1157-1194) for the NeRF MLP of DESIGN.md 3.16.
+
+    state_dict: the checkpoint's network_fn_state_dict (keys with or without DataParallel's ``module.``), or the NerfGridWeights
+    nerf_grid_pack made of it (several queries of one network then pack once); cfg: the run's args.json;
+    xs / ys / zs: the float32 torch.linspace values of the grid axes; bb_center [3], bb_scale: the scene normalisation of run_network;
+    poses [P, >=3, >=3]: the training camera-to-world matrices.  Returns a float32 device tensor: layout "flat" (N, 4) with row
+    (iz * res_y + iy) * res_x + ix -- the reference's array -- or "wlh" (res_x, res_y, res_z, 4), the grid datasets.py reads.
+    Channels: mean over the poses of sigmoid(rgb), summed in pose order, and the raw density.  The trunk of the MLP runs once per point
+    on the exact-fp32 MFMA; the poses loop over views_linears.0 / rgb_linear only.  ``chunk`` (points, default 2^20) bounds the scratch
+    and never changes the result."""
+    if layout not in _NERF_LAYOUTS:
+        raise ValueError(f"layout {layout!r}: expected 'flat' or 'wlh'")
+    weights = state_dict if isinstance(state_dict, NerfGridWeights) else nerf_grid_pack(state_dict, cfg)
+    c, packed, dev = weights.config, weights.packed, weights.packed.device
+    if c != nerf_grid_config(cfg):
+        raise lib.NrpnError("nerf_grid_query: the weights were packed for other options")
+    # c_p = W_d embed_dirs(d_p) + b: the camera embedding is zero at extraction (run_nerf.py:1177), its columns drop out
+    poses = torch.as_tensor(poses, dtype=torch.float32).to(dev)
+    if poses.dim() != 3 or poses.shape[0] < 1 or poses.shape[1] < 3 or poses.shape[2] < 3:
+        raise lib.NrpnError(f"nerf_grid_query expects poses [P, >=3, >=3], got {tuple(poses.shape)}")
+    d = poses[:, :3, :3] @ torch.tensor([0.0, 0.0, -1.0], device=dev)
+    emb = [d]
+    for freq in 2. ** torch.linspace(0., c["multires_views"] - 1, steps=c["multires_views"]):
+        emb += [torch.sin(d * freq.item()), torch.cos(d * freq.item())]
+    ctab = (torch.cat(emb, -1) @ weights.w_dirs.T + weights.b_views).contiguous()
+
+    axes = [torch.as_tensor(a, dtype=torch.float32).reshape(-1).to(dev).contiguous() for a in (xs, ys, zs)]
+    rx, ry, rz = (int(a.numel()) for a in axes)
+    if min(rx, ry, rz) < 1:
+        raise lib.NrpnError(f"nerf_grid_query: empty axis in resolution {rx} x {ry} x {rz}")
+    n = rx * ry * rz
+    chunk = NERF_GRID_DEFAULT_CHUNK if chunk is None else int(chunk)
+    if chunk < 1:
+        raise lib.NrpnError(f"nerf_grid_query: chunk {chunk}")
+    nbytes = lib.query("nerfgrid_work_bytes", 1, min(chunk, n))
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    out = torch.empty((n, 4) if layout == "flat" else (rx, ry, rz, 4), dtype=torch.float32, device=dev)
+    cx, cy, cz = (float(v) for v in torch.as_tensor(bb_center, dtype=torch.float32).reshape(3).tolist())
+    scale = float(torch.as_tensor(bb_scale, dtype=torch.float32).reshape(()).item())
+    call("nerfgrid_query", _p(axes[0]), _p(axes[1]), _p(axes[2]), rx, ry, rz, cx, cy, cz, scale, c["multires"], _p(packed), _p(ctab),
+         int(ctab.shape[0]), _NERF_LAYOUTS[layout], chunk, _p(work), nbytes, _p(out), _s())
+    return out
