@@ -729,6 +729,45 @@ int nrpn_nerfgrid_query(const float *xs, const float *ys, const float *zs, int r
                         float center_y, float center_z, float bb_scale, int multires, const float *packed, const float *ctab,
                         int num_poses, int layout, int64_t chunk, void *work, int64_t work_bytes, float *out, nrpn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Views of a trained NeRF MLP, scripts/nerf_render.py.  [f6]  Replaces render / batchify_rays / render_rays of
+ * data/scannet/run_nerf.py (:68-157, :514-614) at test time (perturb 0, raw_noise_std 0, N_importance 0) for the model of DESIGN.md
+ * 3.16, with the packed weights of nrpn_nerfgrid_pack.  Rays are processed chunk rays at a time; no atomics, the result does not
+ * depend on chunk.
+ * nrpn_nerfrender_work_bytes(chunk_rays, s1, s2): bytes of the scratch for chunks of chunk_rays rays with s1 first-pass and s2
+ *   second-pass samples per ray; -1 for sizes outside the supported range.
+ * nrpn_nerfrender_samples (compute_samples_around_depth :497-502 = raw2depth :431-435, compute_weights :419-429, sample_3sigma
+ *   :471-478 and the deterministic sample_pdf): raw f32 [num_rays][num_samples][4] (rgb before the sigmoid, sigma), rays f32
+ *   [num_rays][6] (o, d), z f32 [num_samples] shared by the rays -> z2 f32 [num_rays][num_samples].  The lower bound of the std is
+ *   z[-1] - z[-2]; the bin edges are clamped to [near, far].  Reductions in float64.
+ * nrpn_nerfrender_rays / nrpn_nerfrender_frame: rays f32 [num_rays][6], or the rays of every pixel (row-major, ray v * width + u) of
+ *   the camera f32 [16] = fx, fy, cx, cy, c2w[:3, :4] row-major: d = R [(u - cx) / fx, -(v - cy) / fy, -1], o = t (render :108-110 with
+ *   the assumed get_rays).  Points o + d z, then (p - center) * bb_scale (run_network :53-55), in float32 without contraction.  w_view
+ *   f32 [128][3 + 6 multires_views + input_ch_cam] = views_linears.0.weight[:, 256:], b_view f32 [128], embedded_cam f32
+ *   [input_ch_cam] (may be null if that is 0); the view direction is d / |d| (render :127-132).  z1 f32 [s1]: the first-pass samples
+ *   shared by all rays (precomputed_z_samples, or the plain path's near .. far samples :602-606).  z2_mode 0: one pass (s2 = 0,
+ *   :611-614); 1: s2 = s1 samples around the first pass's depth as nrpn_nerfrender_samples draws them (:595-600); 2: z2_in f32
+ *   [num_rays][s2], non-decreasing per ray.  The two sample lists are merged (forward_with_additonal_samples :504-512; a stable
+ *   sort is not needed: equal z give equal raw) and composited (raw2outputs :437-469) in float64: rgb f32 [num_rays][3], depth, acc,
+ *   disp f32 [num_rays], depth_std = sqrt(clamp(sum((z - depth)^2 w), 0, 1)) (render_video :184-185).  Optional (null to skip):
+ *   z_vals, weights f32 [num_rays][s1 + s2]; raw1_out f32 [num_rays][s1][4], the first pass's raw; z2_out f32 [num_rays][s2] in
+ *   mode 1.  work: nrpn_nerfrender_work_bytes(min(chunk, num_rays), s1, s2) bytes, 16-byte aligned.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t nrpn_nerfrender_work_bytes(int64_t chunk_rays, int s1, int s2);
+int nrpn_nerfrender_samples(const float *raw, const float *rays, const float *z, int num_samples, float near, float far,
+                            int64_t num_rays, float *z2, nrpn_stream_t stream);
+int nrpn_nerfrender_rays(const float *rays, int64_t num_rays, float near, float far, float center_x, float center_y, float center_z,
+                         float bb_scale, int multires, int multires_views, int input_ch_cam, const float *packed, const float *w_view,
+                         const float *b_view, const float *embedded_cam, const float *z1, int s1, int z2_mode, const float *z2_in, int s2,
+                         int64_t chunk, void *work, int64_t work_bytes, float *rgb, float *depth, float *acc, float *disp,
+                         float *depth_std, float *z_vals, float *weights, float *raw1_out, float *z2_out, nrpn_stream_t stream);
+int nrpn_nerfrender_frame(int height, int width, const float *camera, float near, float far, float center_x, float center_y,
+                          float center_z, float bb_scale, int multires, int multires_views, int input_ch_cam, const float *packed,
+                          const float *w_view, const float *b_view, const float *embedded_cam, const float *z1, int s1, int z2_mode,
+                          const float *z2_in, int s2, int64_t chunk, void *work, int64_t work_bytes, float *rgb, float *depth, float *acc,
+                          float *disp, float *depth_std, float *z_vals, float *weights, float *raw1_out, float *z2_out,
+                          nrpn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

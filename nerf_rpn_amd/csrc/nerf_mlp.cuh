@@ -1,0 +1,189 @@
+// The 8 x 256 trunk of the NeRF MLP of DESIGN.md 3.16 on the exact-fp32 MFMA, shared by nerfgrid.hip (lattice points) and
+// nerfrender.hip (ray samples): packed-weight layout (nrpn_nerfgrid_pack), fragment loads, the k-ordered MFMA product and the body
+// of one workgroup.  A caller supplies where a tile's 64 points come from and where their sigma goes; g goes to a [column][point]
+// tile.  The arithmetic of a point does not depend on the caller, its tile or its neighbours.
+#pragma once
+#include "common.h"
+
+#include <cmath>
+
+namespace nerfmlp {
+
+constexpr int kTile = 64;        // points per workgroup
+constexpr int kEnc = 64;         // columns 0 .. 63 of the LDS image: the encoding (input_ch <= 64, zero-padded)
+constexpr int kW = 256;          // hidden width
+constexpr int kHalf = 128;       // views_linears.0 width
+constexpr int kLd = 324;         // row stride of the LDS image in floats: 16-byte aligned rows, 4-bank skew between rows
+constexpr int kLayers = 8;
+constexpr int kSkipLayer = 5;    // the layer after skip 4 reads cat([e, h])
+constexpr int kLdsBytes = kTile * kLd * 4;
+
+// packed layout, in floats (include/nerfrpn.h: nrpn_nerfgrid_pack)
+constexpr int64_t kOffL0 = 0;
+constexpr int64_t kSzL0 = (int64_t)kEnc * kW;
+constexpr int64_t kSzSq = (int64_t)kW * kW;
+constexpr int64_t kSzSkip = (int64_t)(kEnc + kW) * kW;
+__host__ __device__ constexpr int64_t off_layer(int i) {          // i = 0 .. 7 pts_linears, 8 feature_linear, 9 W_f
+  return i == 0 ? kOffL0 : kSzL0 + (int64_t)(i - 1) * kSzSq + (i > kSkipLayer ? kSzSkip - kSzSq : 0);
+}
+constexpr int64_t kOffBias = off_layer(9) + (int64_t)kW * kHalf;   // 9 x 256: pts_linears 0 .. 7, feature_linear
+constexpr int64_t kOffAlphaW = kOffBias + 9 * kW;                  // 256
+constexpr int64_t kOffAlphaB = kOffAlphaW + kW;                    // 1 (+3 pad)
+constexpr int64_t kOffRgbW = kOffAlphaB + 4;                       // 3 x 128
+constexpr int64_t kOffRgbB = kOffRgbW + 3 * kHalf;                 // 3 (+1 pad)
+constexpr int64_t kPackedFloats = kOffRgbB + 4;
+
+using f32x16 = __attribute__((ext_vector_type(16))) float;
+
+// acc[m][c] += act[32 m .. 32 m + 31][k0 .. k0 + K) * W[:, col0 + 32 c .. + 31]; one wave, NC column blocks.  K / 8 is even.  Two
+// register sets alternate, so the loads of k-group n + 1 are in flight during the 8 * NC MFMAs of group n without register copies.
+template <int NC>
+struct Frag {
+  float4 a[2], b[NC];
+};
+
+template <int NC>
+__device__ __forceinline__ void frag_load(Frag<NC> &f, const float *a_ptr, const float4 *__restrict__ b_ptr, int kg, int n_out) {
+  f.a[0] = *reinterpret_cast<const float4 *>(a_ptr + kg * 8);
+  f.a[1] = *reinterpret_cast<const float4 *>(a_ptr + 32 * kLd + kg * 8);
+#pragma unroll
+  for (int c = 0; c < NC; ++c) f.b[c] = b_ptr[(int64_t)kg * n_out * 2 + c * 64];
+}
+
+template <int NC>
+__device__ __forceinline__ void frag_mma(const Frag<NC> &f, f32x16 (&acc)[2][NC]) {
+  const float av[2][4] = {{f.a[0].x, f.a[0].y, f.a[0].z, f.a[0].w}, {f.a[1].x, f.a[1].y, f.a[1].z, f.a[1].w}};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const float bv = j == 0 ? f.b[c].x : j == 1 ? f.b[c].y : j == 2 ? f.b[c].z : f.b[c].w;
+#pragma unroll
+      for (int m = 0; m < 2; ++m) acc[m][c] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[m][j], bv, acc[m][c], 0, 0, 0);
+    }
+  }
+}
+
+template <int NC>
+__device__ __forceinline__ void gemm_tile(const float *act, int k0, int K, const float4 *__restrict__ wp, int n_out, int col0,
+                                          f32x16 (&acc)[2][NC]) {
+  const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+  const float *a_ptr = act + r * kLd + k0 + 4 * h;
+  const float4 *b_ptr = wp + ((int64_t)(col0 + r) * 2 + h);
+  const int groups = K >> 3;
+  Frag<NC> f0, f1;
+  frag_load(f0, a_ptr, b_ptr, 0, n_out);
+  // the scheduling barriers keep each load block ahead of the MFMA block it overlaps (left alone, the scheduler sinks the loads to
+  // their first use and the L2 latency of every group is exposed)
+  for (int kg = 0; kg < groups; kg += 2) {
+    frag_load(f1, a_ptr, b_ptr, kg + 1, n_out);
+    __builtin_amdgcn_sched_barrier(0);
+    frag_mma(f0, acc);
+    __builtin_amdgcn_sched_barrier(0);
+    frag_load(f0, a_ptr, b_ptr, kg + 2 < groups ? kg + 2 : kg, n_out);      // the last iteration reloads its own group: in bounds, unused
+    __builtin_amdgcn_sched_barrier(0);
+    frag_mma(f1, acc);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// row of the 32 x 32 accumulator that register reg of this lane holds
+__device__ __forceinline__ int acc_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
+
+// One workgroup of 256 threads, one tile of 64 points.  act: the kLdsBytes LDS image.  src.point(i, p) gives the normalised position
+// of tile point i (a partial tile repeats a valid point; nothing of it may be stored), sink.sigma(i, s) takes alpha_linear's output of
+// tile point i; g = W_f f goes to g_tile as [column][point], 128 x 64 floats, for every point of the tile.
+template <class Src, class Sink>
+__device__ __forceinline__ void trunk_body(float *act, const float *__restrict__ packed, int multires, int input_ch, const Src &src,
+                                           const Sink &sink, float *__restrict__ g_tile) {
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
+
+  // encoding: thread = (point i, quarter q of the 3 L (frequency, axis) pairs)
+  {
+    const int i = t & 63, q = t >> 6;
+    float p[3];
+    src.point(i, p);
+    float *row = act + i * kLd;
+    if (q == 0) {
+      row[0] = p[0];
+      row[1] = p[1];
+      row[2] = p[2];
+      for (int c = input_ch; c < kEnc; ++c) row[c] = 0.f;
+    }
+    for (int idx = q; idx < 3 * multires; idx += 4) {
+      const int l = idx / 3, a = idx - 3 * l;
+      const float arg = p[a] * ldexpf(1.0f, l);
+      row[3 + 6 * l + a] = sinf(arg);
+      row[3 + 6 * l + 3 + a] = cosf(arg);
+    }
+  }
+  __syncthreads();
+
+  const float4 *wp = reinterpret_cast<const float4 *>(packed);
+  const float *bias = packed + kOffBias;
+  const int col0 = wave * 64;
+
+  for (int layer = 0; layer <= kLayers; ++layer) {           // 0 .. 7 pts_linears (relu), 8 feature_linear (no relu)
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[m][c][e] = 0.f;
+    const int k0 = (layer == 0 || layer == kSkipLayer) ? 0 : kEnc;
+    const int K = layer == 0 ? kEnc : layer == kSkipLayer ? kEnc + kW : kW;
+    gemm_tile<2>(act, k0, K, wp + off_layer(layer) / 4, kW, col0, acc);
+    if (layer == kLayers && t < kTile) {
+      // sigma = alpha_linear(h): h is still in the image; one thread per point, k in order
+      const float4 *hrow = reinterpret_cast<const float4 *>(act + t * kLd + kEnc);
+      const float *aw = packed + kOffAlphaW;
+      float s = 0.f;
+      for (int k = 0; k < kW / 4; ++k) {
+        const float4 v = hrow[k];
+        s = fmaf(v.x, aw[4 * k], s);
+        s = fmaf(v.y, aw[4 * k + 1], s);
+        s = fmaf(v.z, aw[4 * k + 2], s);
+        s = fmaf(v.w, aw[4 * k + 3], s);
+      }
+      s += packed[kOffAlphaB];
+      sink.sigma(t, s);
+    }
+    __syncthreads();                                          // every wave has read the layer's input
+    const bool relu = layer < kLayers;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const int col = col0 + 32 * c + r;
+      const float bv = bias[layer * kW + col];
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          float v = acc[m][c][e] + bv;
+          if (relu) v = fmaxf(v, 0.f);
+          act[(32 * m + acc_row(e, h)) * kLd + kEnc + col] = v;
+        }
+    }
+    __syncthreads();
+  }
+
+  // g = W_f f: 128 columns, 32 per wave; stored [column][point] so a head reads it coalesced
+  {
+    f32x16 acc[2][1];
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[m][0][e] = 0.f;
+    gemm_tile<1>(act, kEnc, kW, wp + off_layer(9) / 4, kHalf, wave * 32, acc);
+    float *gt = g_tile + (wave * 32 + r) * kTile;
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        float4 v = {acc[m][0][4 * q], acc[m][0][4 * q + 1], acc[m][0][4 * q + 2], acc[m][0][4 * q + 3]};
+        *reinterpret_cast<float4 *>(gt + 32 * m + 8 * q + 4 * h) = v;
+      }
+  }
+}
+
+}  // namespace nerfmlp

@@ -2538,8 +2538,9 @@ def nerf_grid_config(cfg):
 class NerfGridWeights:
     """The device-side weights of one NeRF MLP for nerf_grid_query: the packed trunk and rgb_linear (nrpn_nerfgrid_pack), the view
     columns W_d and the bias of views_linears.0 for the c_p table, and the options they were built for."""
-    def __init__(self, packed, w_dirs, b_views, config):
+    def __init__(self, packed, w_dirs, b_views, config, w_view=None):
         self.packed, self.w_dirs, self.b_views, self.config = packed, w_dirs, b_views, config
+        self.w_view = w_view        # the view and camera columns together, [128][views_ch + input_ch_cam]: nerf_render's head
 
 
 def nerf_grid_pack(state_dict, cfg):
@@ -2570,7 +2571,7 @@ def nerf_grid_pack(state_dict, cfg):
                        t["rgb_linear.weight"].reshape(-1), t["rgb_linear.bias"]]).contiguous()
     packed = torch.empty(lib.query("nerfgrid_work_bytes", 0, 0) // 4, dtype=torch.float32, device=dev)
     call("nerfgrid_pack", _p(raw), input_ch, _p(packed), _s())
-    return NerfGridWeights(packed, wv[:, W:W + views_ch].contiguous(), t["views_linears.0.bias"], c)
+    return NerfGridWeights(packed, wv[:, W:W + views_ch].contiguous(), t["views_linears.0.bias"], c, wv[:, W:].contiguous())
 
 
 def nerf_grid_query(state_dict, cfg, xs, ys, zs, bb_center, bb_scale, poses, layout="flat", chunk=None):
@@ -2616,3 +2617,132 @@ def nerf_grid_query(state_dict, cfg, xs, ys, zs, bb_center, bb_scale, poses, lay
     call("nerfgrid_query", _p(axes[0]), _p(axes[1]), _p(axes[2]), rx, ry, rz, cx, cy, cz, scale, c["multires"], _p(packed), _p(ctab),
          int(ctab.shape[0]), _NERF_LAYOUTS[layout], chunk, _p(work), nbytes, _p(out), _s())
     return out
+
+
+# ======================================================================================================================
+# views of a trained NeRF MLP (scripts/nerf_render.py)  [f6]
+# ======================================================================================================================
+NERF_RENDER_DEFAULT_CHUNK = 4096       # rays per launch group: 256 MiB of g scratch at 128 samples per pass
+
+
+def nerf_render(weights_or_state, cfg, H=None, W=None, intrinsic=None, c2w=None, rays=None, near=None, far=None, bb_center=(0., 0., 0.),
+                bb_scale=1., z_samples=None, n_samples=None, lindisp=False, embedded_cam=None, chunk=None, return_samples=False,
+                z2=None, return_stages=False):
+    """render (run_nerf.py:82-157) with render_rays (:514-614) at test time for the NeRF MLP of DESIGN.md 3.16, on the GPU.
+
+    weights_or_state: the NerfGridWeights of nerf_grid_pack, or a network_fn_state_dict; cfg: the run's args.json.  The rays are those
+    of every pixel of an H x W frame with intrinsic = (fx, fy, cx, cy) and the camera-to-world matrix c2w [>=3, 4] (the assumed
+    get_rays: d = R [(u - cx) / fx, -(v - cy) / fy, -1], o = t), or ``rays`` [R, 6] = (o, d); giving both is an error.  near, far: the
+    ray bounds, which the plain path's samples span and the drawn samples are clamped to -- required there; with z2 given nothing
+    reads them.  bb_center [3], bb_scale: the scene normalisation of run_network.  z_samples [N / 2] float32 (precomputed_z_samples) selects the two-pass
+    path: those samples on every ray, then as many around the depth they predict (compute_samples_around_depth), both composited.
+    z_samples None selects the plain path: n_samples between near and far, linear in depth or, with lindisp, in inverse depth.
+    embedded_cam [input_ch_cam]: the camera embedding (default zeros, as video and test use).  chunk: rays per launch group (default
+    4096); it never changes the result.
+
+    Returns a dict of float32 device tensors keyed as render_rays returns them -- rgb_map [.., 3], depth_map, acc_map, disp_map [..]
+    -- plus depth_std = sqrt(clamp(sum((z - depth)^2 w), 0, 1)) (render_video :184-185), with leading shape (H, W) or (R,);
+    return_samples adds z_vals and weights [.., S].  z2 [R, S2]: run the second pass on these samples instead of drawing them;
+    return_stages adds raw1 [R, S1, 4] (the first pass's rgb before the sigmoid and sigma) and z2 (the drawn samples)."""
+    weights = weights_or_state if isinstance(weights_or_state, NerfGridWeights) else nerf_grid_pack(weights_or_state, cfg)
+    c, packed, dev = weights.config, weights.packed, weights.packed.device
+    if c != nerf_grid_config(cfg):
+        raise lib.NrpnError("nerf_render: the weights were packed for other options")
+
+    def f32(x, shape=None):
+        x = torch.as_tensor(x, dtype=torch.float32).to(dev)
+        return (x if shape is None else x.reshape(shape)).contiguous()
+    cam_ch = c["input_ch_cam"]
+    cam = torch.zeros(cam_ch, dtype=torch.float32, device=dev) if embedded_cam is None else f32(embedded_cam, -1)
+    if cam.numel() != cam_ch:
+        raise lib.NrpnError(f"nerf_render: embedded_cam has {cam.numel()} values, input_ch_cam is {cam_ch}")
+    if (near is None or far is None) and (z_samples is None or z2 is None):
+        raise lib.NrpnError("nerf_render: near and far are needed to place the samples")
+    near, far = (0. if near is None else float(near)), (0. if far is None else float(far))
+    if z_samples is not None:
+        z1 = f32(z_samples, -1)
+        s1 = int(z1.numel())
+        mode, s2 = (1, s1) if z2 is None else (2, int(torch.as_tensor(z2).shape[-1]))
+        if mode == 1 and s1 < 3:
+            raise lib.NrpnError(f"nerf_render: {s1} precomputed samples, the depth-guided pass needs at least 3")
+    else:
+        if z2 is not None:
+            raise lib.NrpnError("nerf_render: z2 goes with z_samples")
+        if n_samples is None or int(n_samples) < 1:
+            raise lib.NrpnError(f"nerf_render: n_samples {n_samples!r}")
+        # render_rays :571, :602-606 on [1, 1] bounds: the float32 values the reference gives every ray
+        t_vals = torch.linspace(0., 1., steps=int(n_samples))
+        n_t, f_t = torch.full((1, 1), near), torch.full((1, 1), far)
+        z1 = n_t * (1. - t_vals) + f_t * t_vals if not lindisp else 1. / (1. / n_t * (1. - t_vals) + 1. / f_t * t_vals)
+        z1 = f32(z1, -1)
+        s1, mode, s2 = int(z1.numel()), 0, 0
+    frame = [x is not None for x in (H, W, intrinsic, c2w)]
+    if rays is not None and any(frame):
+        raise lib.NrpnError("nerf_render: give H, W, intrinsic and c2w, or rays, not both")
+    if rays is not None:
+        rays_t = f32(rays)
+        if rays_t.dim() != 2 or rays_t.shape[1] != 6 or rays_t.shape[0] < 1:
+            raise lib.NrpnError(f"nerf_render expects rays [R, 6], got {tuple(rays_t.shape)}")
+        lead = (int(rays_t.shape[0]),)
+    else:
+        if not all(frame) or int(H) < 1 or int(W) < 1:
+            raise lib.NrpnError("nerf_render: give H, W, intrinsic and c2w, or rays")
+        pose = torch.as_tensor(c2w, dtype=torch.float32)
+        if pose.dim() != 2 or pose.shape[0] < 3 or pose.shape[1] != 4:
+            raise lib.NrpnError(f"nerf_render expects c2w [>=3, 4], got {tuple(pose.shape)}")
+        camera = f32(torch.cat([torch.as_tensor(intrinsic, dtype=torch.float32).reshape(4), pose[:3].reshape(12)]))
+        lead = (int(H), int(W))
+    n = lead[0] if len(lead) == 1 else lead[0] * lead[1]
+    z2_t = None
+    if mode == 2:
+        z2_t = f32(z2)
+        if tuple(z2_t.shape) != (n, s2) or s2 < 1:
+            raise lib.NrpnError(f"nerf_render expects z2 [{n}, S2], got {tuple(z2_t.shape)}")
+    chunk = NERF_RENDER_DEFAULT_CHUNK if chunk is None else int(chunk)
+    if chunk < 1:
+        raise lib.NrpnError(f"nerf_render: chunk {chunk}")
+    nbytes = lib.query("nerfrender_work_bytes", min(chunk, n), s1, s2)
+    if nbytes < 0:
+        raise lib.NrpnError(f"nerf_render: chunk {chunk} with {s1} + {s2} samples is outside the supported range")
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+    def new(*shape):
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    out = {"rgb_map": new(n, 3), "depth_map": new(n), "acc_map": new(n), "disp_map": new(n), "depth_std": new(n)}
+    if return_samples:
+        out["z_vals"], out["weights"] = new(n, s1 + s2), new(n, s1 + s2)
+    if return_stages:
+        out["raw1"] = new(n, s1, 4)
+        if mode == 1:
+            out["z2"] = new(n, s2)
+
+    def opt(k):
+        return _p(out[k]) if k in out else None
+    cx, cy, cz = (float(v) for v in torch.as_tensor(bb_center, dtype=torch.float32).reshape(3).tolist())
+    scale = float(torch.as_tensor(bb_scale, dtype=torch.float32).reshape(()).item())
+    common = (near, far, cx, cy, cz, scale, c["multires"], c["multires_views"], cam_ch, _p(packed), _p(weights.w_view),
+              _p(weights.b_views), _p(cam) if cam_ch else None, _p(z1), s1, mode, _p(z2_t) if z2_t is not None else None, s2, chunk,
+              _p(work), nbytes, _p(out["rgb_map"]), _p(out["depth_map"]), _p(out["acc_map"]), _p(out["disp_map"]), _p(out["depth_std"]),
+              opt("z_vals"), opt("weights"), opt("raw1"), opt("z2"), _s())
+    if rays is not None:
+        call("nerfrender_rays", _p(rays_t), n, *common)
+    else:
+        call("nerfrender_frame", lead[0], lead[1], _p(camera), *common)
+    return {k: (v if k in ("raw1", "z2") else v.reshape(*lead, *v.shape[1:])) for k, v in out.items()}
+
+
+def nerf_render_samples(raw, rays, z_samples, near, far):
+    """compute_samples_around_depth (run_nerf.py:497-502) on its own: raw [R, S, 4] and rays [R, 6] on the first-pass samples
+    z_samples [S] -> z2 [R, S] float32, the depth-guided samples nerf_render draws between its two passes."""
+    if not torch.cuda.is_available():
+        raise lib.NrpnError("nerf_render_samples needs a gfx950 device (the product path has no CPU fallback)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    raw = torch.as_tensor(raw, dtype=torch.float32).to(dev).contiguous()
+    rays = torch.as_tensor(rays, dtype=torch.float32).to(dev).contiguous()
+    z = torch.as_tensor(z_samples, dtype=torch.float32).to(dev).reshape(-1).contiguous()
+    n, s = int(rays.shape[0]), int(z.numel())
+    if tuple(raw.shape) != (n, s, 4) or rays.dim() != 2 or rays.shape[1] != 6:
+        raise lib.NrpnError(f"nerf_render_samples expects raw [R, {s}, 4] and rays [R, 6], got {tuple(raw.shape)} and {tuple(rays.shape)}")
+    z2 = torch.empty((n, s), dtype=torch.float32, device=dev)
+    call("nerfrender_samples", _p(raw), _p(rays), _p(z), s, float(near), float(far), n, _p(z2), _s())
+    return z2

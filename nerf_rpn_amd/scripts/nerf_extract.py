@@ -77,8 +77,8 @@ def grid_axes(lo, hi, max_res):
     return (res, *(torch.linspace(lo[a], hi[a], res[a]) for a in range(3)))
 
 
-def load_transforms(path):
-    """-> (poses float32 [P, 4, 4], intrinsics float32 [P, 4] = fx, fy, cx, cy, far or None)."""
+def load_transforms(path, with_meta=False):
+    """-> (poses float32 [P, 4, 4], intrinsics float32 [P, 4] = fx, fy, cx, cy, far or None); with_meta adds the parsed json."""
     with open(path) as f:
         meta = json.load(f)
     frames = meta['frames']
@@ -86,7 +86,7 @@ def load_transforms(path):
         raise SystemExit(f'{path}: no frames')
     poses = torch.tensor([fr['transform_matrix'] for fr in frames], dtype=torch.float32)
     intr = torch.tensor([[fr.get(k, meta.get(k)) for k in ('fx', 'fy', 'cx', 'cy')] for fr in frames], dtype=torch.float32)
-    return poses, intr, meta.get('far')
+    return (poses, intr, meta.get('far'), meta) if with_meta else (poses, intr, meta.get('far'))
 
 
 def corner_bounds(H, W, intrinsics, poses, far):
