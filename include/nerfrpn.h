@@ -768,6 +768,33 @@ int nrpn_nerfrender_frame(int height, int width, const float *camera, float near
                           float *disp, float *depth_std, float *z_vals, float *weights, float *raw1_out, float *z2_out,
                           nrpn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Metrics of a rendered view against its ground truth, scripts/nerf_test.py.  [f7]  Replaces what render_images_with_metrics
+ * (data/scannet/run_nerf.py:231-311) computes per frame and what write_images_with_metrics (:313-331) quantises; DESIGN.md 3.18.
+ * nrpn_nerfmetrics_tile(): the edge of the square tile of pixels one workgroup owns.
+ * nrpn_nerfmetrics_work_bytes(height, width): bytes of the per-tile partial sums; -1 below 7 x 7 or beyond 2^31 pixels.
+ * nrpn_nerfmetrics_frame: rgb f32 [height][width][3] (the raw rgb_map), target f32 [height][width][3]; depth, target_depth f32
+ *   [height][width] and valid u8 [height][width] (non-zero = selected) go together or are all null.  sums f64 [8]:
+ *   [0] sum over the height * width * 3 values of (rgb - target)^2 on the unclamped rgb (img2mse, :283);
+ *   [1..3] per channel, the sum over the (height - 6)(width - 6) 7 x 7 windows inside the image of skimage's structural_similarity
+ *     (:287: gaussian_weights off, K1 0.01, K2 0.03, data_range 1, sample covariance) of clamp(rgb, 0, 1) (:286) against target -- the
+ *     map skimage averages after its crop by 3;
+ *   [4] sum over the selected pixels of (depth - target_depth)^2 and [5] their number (compute_rmse on the masked tensors, :277; an
+ *     unselected target_depth is never read); [6], [7] zero.
+ *   Operands are widened to float64, everything is float64.  Each workgroup writes one row of work and a second kernel adds the rows
+ *   in a fixed order: no atomics, repeated calls are bit-equal.  work: nrpn_nerfmetrics_work_bytes(height, width) bytes, 8-byte
+ *   aligned.
+ * nrpn_nerfmetrics_quantise: rgb8[i] = (uint8)(255 * clip(rgb[i], 0, 1)) for num_rgb values (to8b, :325, on the clamped frame :291)
+ *   and depth16[i] = (uint16)(65535 * clip(depth[i] / far, 0, 1)) for num_depth values (to16b of depth_map / far, :293, :327), in
+ *   float32 with numpy's operation order and truncation.  Either count may be 0 and its pointers null.
+ * ---------------------------------------------------------------------------------------------- */
+int nrpn_nerfmetrics_tile(void);
+int64_t nrpn_nerfmetrics_work_bytes(int height, int width);
+int nrpn_nerfmetrics_frame(const float *rgb, const float *target, int height, int width, const float *depth, const float *target_depth,
+                           const uint8_t *valid, void *work, int64_t work_bytes, double *sums, nrpn_stream_t stream);
+int nrpn_nerfmetrics_quantise(const float *rgb, int64_t num_rgb, uint8_t *rgb8, const float *depth, float far, int64_t num_depth,
+                              uint16_t *depth16, nrpn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2746,3 +2746,78 @@ def nerf_render_samples(raw, rays, z_samples, near, far):
     z2 = torch.empty((n, s), dtype=torch.float32, device=dev)
     call("nerfrender_samples", _p(raw), _p(rays), _p(z), s, float(near), float(far), n, _p(z2), _s())
     return z2
+
+
+# ======================================================================================================================
+# metrics of a rendered view against its ground truth (scripts/nerf_test.py)  [f7]
+# ======================================================================================================================
+NERF_SSIM_WINDOW = 7
+
+
+def nerf_view_metrics(rgb, target_rgb, depth=None, target_depth=None, valid_depth=None, far=None, return_images=False):
+    """What render_images_with_metrics (run_nerf.py:231-311) computes for one rendered frame, on the GPU (csrc/nerfmetrics.hip).
+
+    rgb [H, W, 3] float32: the raw rgb_map; target_rgb [H, W, 3] float32.  depth, target_depth [H, W] float32 and valid_depth [H, W]
+    bool / uint8 go together (all three or none).  Returns a dict of Python numbers:
+      img_loss    mean of (rgb - target)^2 over H W 3, on the unclamped rgb (:283);  psnr = -10 log10(img_loss) (:284)
+      ssim        skimage's structural_similarity(clamp(rgb, 0, 1), target, data_range=1., channel_axis=-1) with its defaults (:286-287)
+      depth_rmse  sqrt of the mean of (depth - target_depth)^2 over the selected pixels (:277), None if none is selected (:278) or
+                  no depth is given; an unselected target is never read, so it may hold NaN or inf
+      n_valid     the number of selected pixels
+    All sums run in float64 on the widened float32 values, without atomics: repeated calls are bit-equal.  return_images adds the
+    device tensors rgb8 [H, W, 3] uint8 = to8b(clamp(rgb)) (:291, :325) and, given depth and ``far``, depth16 [H, W] uint16 =
+    to16b(depth / far) (:293, :327).  Shape or dtype mismatches raise lib.NrpnError; a frame below 7 x 7 raises ValueError, as
+    skimage does."""
+    if not torch.cuda.is_available():
+        raise lib.NrpnError("nerf_view_metrics needs a gfx950 device (the product path has no CPU fallback)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+
+    def dev_tensor(name, x, dtypes, shape=None):
+        if not isinstance(x, torch.Tensor):
+            x = torch.as_tensor(x)
+        if x.dtype not in dtypes:
+            raise lib.NrpnError(f"nerf_view_metrics: {name} is {x.dtype}, expected {' / '.join(str(d) for d in dtypes)}")
+        if shape is not None and tuple(x.shape) != shape:
+            raise lib.NrpnError(f"nerf_view_metrics: {name} has shape {tuple(x.shape)}, expected {shape}")
+        return x.to(dev).contiguous()
+    rgb = dev_tensor("rgb", rgb, (torch.float32,))
+    if rgb.dim() != 3 or rgb.shape[2] != 3:
+        raise lib.NrpnError(f"nerf_view_metrics expects rgb [H, W, 3], got {tuple(rgb.shape)}")
+    H, W = int(rgb.shape[0]), int(rgb.shape[1])
+    target = dev_tensor("target_rgb", target_rgb, (torch.float32,), (H, W, 3))
+    given = [x is not None for x in (depth, target_depth, valid_depth)]
+    if any(given) and not all(given):
+        raise lib.NrpnError("nerf_view_metrics: depth, target_depth and valid_depth go together")
+    if all(given):
+        depth = dev_tensor("depth", depth, (torch.float32,), (H, W))
+        target_depth = dev_tensor("target_depth", target_depth, (torch.float32,), (H, W))
+        valid = dev_tensor("valid_depth", valid_depth, (torch.bool, torch.uint8), (H, W))
+        valid = valid.view(torch.uint8) if valid.dtype == torch.bool else valid
+    else:
+        depth = target_depth = valid = None
+    if return_images and depth is not None and far is None:
+        raise lib.NrpnError("nerf_view_metrics: far is needed for depth16 = to16b(depth / far)")
+    if H < NERF_SSIM_WINDOW or W < NERF_SSIM_WINDOW:
+        raise ValueError(f"nerf_view_metrics: a {H} x {W} frame is smaller than the 7 x 7 SSIM window")
+    nbytes = lib.query("nerfmetrics_work_bytes", H, W)
+    if nbytes < 0:
+        raise lib.NrpnError(f"nerf_view_metrics: a {H} x {W} frame is outside the supported range")
+    work = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    sums = torch.empty(8, dtype=torch.float64, device=dev)
+    call("nerfmetrics_frame", _p(rgb), _p(target), H, W, _p(depth) or None, _p(target_depth) or None, _p(valid) or None, _p(work),
+         nbytes, _p(sums), _s())
+    out = {}
+    if return_images:
+        out["rgb8"] = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+        if depth is not None:
+            out["depth16"] = torch.empty((H, W), dtype=torch.uint16, device=dev)
+        call("nerfmetrics_quantise", _p(rgb), H * W * 3, _p(out["rgb8"]), _p(depth) or None, float(far) if depth is not None else 1.0,
+             H * W if depth is not None else 0, _p(out.get("depth16")) or None, _s())
+    s = sums.cpu().tolist()          # the frame's only float traffic to the host: eight doubles
+    windows = (H - NERF_SSIM_WINDOW + 1) * (W - NERF_SSIM_WINDOW + 1)
+    img_loss = s[0] / (H * W * 3)
+    n_valid = int(s[5])
+    out.update(img_loss=img_loss, psnr=-10. * math.log10(img_loss) if img_loss > 0. else (math.inf if img_loss == 0. else math.nan),
+               ssim=(s[1] / windows + s[2] / windows + s[3] / windows) / 3.,
+               depth_rmse=math.sqrt(s[4] / n_valid) if n_valid > 0 else None, n_valid=n_valid)
+    return out

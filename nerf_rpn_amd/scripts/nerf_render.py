@@ -85,24 +85,28 @@ def write_frame(output_dir, index, result):
     return png, npz
 
 
-def main(argv=None):
-    args = build_parser().parse_args(argv)
+def prepare(args, tool='nerf_render', transforms_name='transforms_test.json'):
+    """What nerf_render and nerf_test share between the parsed flags and the frame loop: the checkpoint and its options, the poses and
+    intrinsics of ``--transforms`` (default ``<data_dir>/<scene_id>/<transforms_name>``), near / far, the scene bounds, the frame
+    selection, the first-pass samples and the packed weights -> namespace."""
+    from types import SimpleNamespace
     if args.expname is None:
-        raise SystemExit('nerf_render: --expname is required')
+        raise SystemExit(f'{tool}: --expname is required')
     if args.image_hw is None:
-        raise SystemExit('nerf_render: --image_hw H W is required')
+        raise SystemExit(f'{tool}: --image_hw H W is required')
     from nerf_rpn_amd import ops
     cfg, state_dict, ckpt_path = load_checkpoint(args.ckpt_dir, args.expname)
     ops.nerf_grid_config(cfg)            # unsupported options stop here, before any file is read
     n_samples, two_pass, lindisp = render_options(args, cfg)
-    print(f'nerf_render: weights from {ckpt_path}')
+    print(f'{tool}: weights from {ckpt_path}')
     H, W = args.image_hw
     scene = os.path.join(args.data_dir, args.scene_id)
-    poses, intrinsics, meta_far, meta = load_transforms(args.transforms or os.path.join(scene, 'transforms_test.json'), with_meta=True)
+    transforms = args.transforms or os.path.join(scene, transforms_name)
+    poses, intrinsics, meta_far, meta = load_transforms(transforms, with_meta=True)
     near = args.near if args.near is not None else meta.get('near')
     far = args.far if args.far is not None else meta_far
     if near is None or far is None:
-        raise SystemExit('nerf_render: give --near and --far (or "near" / "far" in the transforms json)')
+        raise SystemExit(f'{tool}: give --near and --far (or "near" / "far" in the transforms json)')
     if (args.bb_center is None) != (args.bb_scale is None):
         raise SystemExit('--bb_center and --bb_scale go together')
     if args.bb_center is not None:
@@ -110,19 +114,34 @@ def main(argv=None):
     else:
         t_poses, t_intr, _ = load_transforms(args.bounds_transforms or os.path.join(scene, 'transforms_train.json'))
         bb_center, bb_scale, lo, hi = corner_bounds(H, W, t_intr, t_poses, far)
-        print(f'nerf_render: scene bounds from the corner rays: {lo.tolist()} .. {hi.tolist()}')
+        print(f'{tool}: scene bounds from the corner rays: {lo.tolist()} .. {hi.tolist()}')
     frames = list(range(len(poses))) if args.frames is None else args.frames
     for i in frames:
         if not 0 <= i < len(poses):
-            raise SystemExit(f'nerf_render: frame {i} of {len(poses)}')
+            raise SystemExit(f'{tool}: frame {i} of {len(poses)}')
     z_samples = precompute_quadratic_samples(near, far, n_samples // 2) if two_pass else None
     weights = ops.nerf_grid_pack(state_dict, cfg)
+    return SimpleNamespace(cfg=cfg, weights=weights, H=H, W=W, poses=poses, intrinsics=intrinsics, near=near, far=far, meta=meta,
+                           transforms=transforms, bb_center=bb_center, bb_scale=bb_scale, frames=frames, z_samples=z_samples,
+                           n_samples=n_samples, lindisp=lindisp)
+
+
+def render_frame(run, i, chunk=None):
+    """ops.nerf_render of frame i of a prepared run."""
+    from nerf_rpn_amd import ops
+    return ops.nerf_render(run.weights, run.cfg, H=run.H, W=run.W, intrinsic=run.intrinsics[i], c2w=run.poses[i][:3, :4], near=run.near,
+                           far=run.far, bb_center=run.bb_center, bb_scale=run.bb_scale, z_samples=run.z_samples, n_samples=run.n_samples,
+                           lindisp=run.lindisp, chunk=chunk)
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    run = prepare(args)
+    H, W, frames = run.H, run.W, run.frames
     os.makedirs(args.output_dir or '.', exist_ok=True)
     written = []
     for i in frames:
-        out = ops.nerf_render(weights, cfg, H=H, W=W, intrinsic=intrinsics[i], c2w=poses[i][:3, :4], near=near, far=far,
-                              bb_center=bb_center, bb_scale=bb_scale, z_samples=z_samples, n_samples=n_samples, lindisp=lindisp,
-                              chunk=args.chunk)
+        out = render_frame(run, i, args.chunk)
         written.append(write_frame(args.output_dir, i, {k: v.cpu().numpy() for k, v in out.items()}))
     print(f'nerf_render: {len(written)} frames of {H} x {W} in {args.output_dir or "."}')
     return written
