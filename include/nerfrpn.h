@@ -795,6 +795,41 @@ int nrpn_nerfmetrics_frame(const float *rgb, const float *target, int height, in
 int nrpn_nerfmetrics_quantise(const float *rgb, int64_t num_rgb, uint8_t *rgb8, const float *depth, float far, int64_t num_depth,
                               uint16_t *depth16, nrpn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Test-time optimisation of the camera embedding, scripts/nerf_test_opt.py.  [f8]  Replaces what one step of
+ * optimize_camera_embedding (data/scannet/run_nerf.py:193-229) computes -- render (:218), img2mse (:219) and backward (:220) over
+ * every batch of the image -- for the model and the packed weights of nrpn_nerfrender_*; DESIGN.md 3.19.  The embedding enters the
+ * network at views_linears.0 only, so everything else is computed once per image (prepare) and an evaluation runs the rgb head
+ * forward and backward only.  Rays are processed chunk rays at a time; chunk c is rays [c chunk, (c + 1) chunk).  No atomics.
+ * nrpn_nerfcamopt_work_bytes(what, num_rays, chunk_rays, s1, s2): what 0: bytes of prepare's scratch; 1: of eval's scratch; 2: of
+ *   one chunk's slot in the g cache.  -1 for sizes outside the supported range.
+ * nrpn_nerfcamopt_prepare: rays f32 [num_rays][6], or (rays null) the rays of the height x width frame of camera f32 [16] as
+ *   nrpn_nerfrender_frame makes them, written to rays_out f32 [num_rays][6].  z1, s1, z2_mode, z2_in, s2 as in nrpn_nerfrender_rays;
+ *   in mode 1 the drawn samples go to z2_out f32 [num_rays][s2], which eval takes as z2.  w1 f64 [num_rays][s1], w2 f64
+ *   [num_rays][s2] (null if s2 = 0): the weight compute_weights (:419-429) gives each sample among the merged samples of its ray
+ *   (forward_with_additonal_samples :504-512), stored at the sample's place in its own list; the values nrpn_nerfrender_rays
+ *   composites with, before their rounding to float32.  g_cache (null if cached_chunks = 0): the trunk's output of the first
+ *   cached_chunks chunks, one slot of work_bytes(2, ..) each.
+ * nrpn_nerfcamopt_eval: the objective at embedded_cam f32 [input_ch_cam >= 1] from prepare's rays, z2, w1, w2 and g_cache (the
+ *   trunk is re-run for a chunk >= cached_chunks: the same bits).  target f32 [num_rays][3]; ray_weight f64 [num_rays].
+ *   rgb = sum w sigmoid(raw) in merged order, float64, rounded to rgb f32 [num_rays][3] (null to skip) -- bit-equal to
+ *   nrpn_nerfrender_rays's rgb at the same embedding.  loss_grad f64 [1 + input_ch_cam]: L = sum_r ray_weight[r] sum_ch (rgb -
+ *   target)^2 on the unrounded rgb, then dL / d embedded_cam.  Everything after the head's float32 raw rgb is float64; sums over
+ *   rays, tiles and chunks are fixed-order trees, so repeated calls are bit-equal and the cache does not change a bit.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t nrpn_nerfcamopt_work_bytes(int what, int64_t num_rays, int64_t chunk_rays, int s1, int s2);
+int nrpn_nerfcamopt_prepare(const float *rays, int height, int width, const float *camera, int64_t num_rays, float near, float far,
+                            float center_x, float center_y, float center_z, float bb_scale, int multires, const float *packed,
+                            const float *z1, int s1, int z2_mode, const float *z2_in, int s2, int64_t chunk, void *work,
+                            int64_t work_bytes, float *rays_out, float *z2_out, double *w1, double *w2, float *g_cache,
+                            int64_t cached_chunks, nrpn_stream_t stream);
+int nrpn_nerfcamopt_eval(const float *rays, int64_t num_rays, float center_x, float center_y, float center_z, float bb_scale,
+                         int multires, int multires_views, int input_ch_cam, const float *packed, const float *w_view,
+                         const float *b_view, const float *embedded_cam, const float *z1, int s1, const float *z2, int s2,
+                         const double *w1, const double *w2, const float *target, const double *ray_weight, int64_t chunk,
+                         const float *g_cache, int64_t cached_chunks, void *work, int64_t work_bytes, double *loss_grad, float *rgb,
+                         nrpn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

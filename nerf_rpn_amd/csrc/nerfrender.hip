@@ -83,24 +83,29 @@ __global__ __launch_bounds__(256) void nerfrender_trunk_kernel(RayPoints rp, int
 
 // ---- head ------------------------------------------------------------------------------------------------------------------------
 // rgb_linear over v = relu(g + c) for one point: g the point's 128 trunk outputs in registers, c[j] the view part of its ray.
-// 128-term fmaf chains in j order; W_rgb is wave-uniform and comes through the scalar cache.
+// 128-term fmaf chains in j order; W_rgb is wave-uniform and comes through the scalar cache.  kMask: bit j of m is g[j] + c[j] > 0,
+// the derivative of the relu (0 at exactly 0, as torch has it), for the camera-embedding gradient.
+template <bool kMask>
 __device__ __forceinline__ void rgb_head(const float (&g)[kHalf], const float *c, const float *__restrict__ w, float &r0, float &r1,
-                                         float &r2) {
+                                         float &r2, uint32_t (&m)[4]) {
   r0 = r1 = r2 = 0.f;
 #pragma unroll
   for (int j = 0; j < kHalf; ++j) {
-    const float v = fmaxf(g[j] + c[j], 0.f);
+    const float pre = g[j] + c[j];
+    const float v = fmaxf(pre, 0.f);
+    if (kMask) m[j >> 5] |= (uint32_t)(pre > 0.f) << (j & 31);
     r0 = fmaf(w[j], v, r0);
     r1 = fmaf(w[kHalf + j], v, r1);
     r2 = fmaf(w[2 * kHalf + j], v, r2);
   }
 }
 
-// w_view [128][views_ch + cam_ch]: the view and camera columns of views_linears.0.weight; b_view [128]; cam [cam_ch]
-__global__ __launch_bounds__(kTile) void nerfrender_head_kernel(RayPoints rp, const float *__restrict__ packed,
-                                                                const float *__restrict__ w_view, const float *__restrict__ b_view,
-                                                                const float *__restrict__ cam, int multires_views, int cam_ch,
-                                                                const float *__restrict__ gbuf, float *__restrict__ raw) {
+// One workgroup of 64 threads, one tile of 64 points.  w_view [128][views_ch + cam_ch]: the view and camera columns of
+// views_linears.0.weight; b_view [128]; cam [cam_ch]; mask [points][4] (kMask only)
+template <bool kMask>
+__device__ __forceinline__ void head_tile(const RayPoints &rp, const float *__restrict__ packed, const float *__restrict__ w_view,
+                                          const float *__restrict__ b_view, const float *__restrict__ cam, int multires_views, int cam_ch,
+                                          const float *__restrict__ gbuf, float *__restrict__ raw, uint32_t *__restrict__ mask) {
   __shared__ float emb[kTile][kMaxViewsCh];
   __shared__ float cbase[kHalf];
   __shared__ float ctile[kTile * kCtileLd];
@@ -145,13 +150,22 @@ __global__ __launch_bounds__(kTile) void nerfrender_head_kernel(RayPoints rp, co
 #pragma unroll
   for (int j = 0; j < kHalf; ++j) g[j] = gt[j * kTile];
   float r0, r1, r2;
-  rgb_head(g, crow, packed + kOffRgbW, r0, r1, r2);
+  uint32_t m[4] = {0u, 0u, 0u, 0u};
+  rgb_head<kMask>(g, crow, packed + kOffRgbW, r0, r1, r2, m);
   if (pi < rp.num_points) {
     float *o = raw + pi * 4;
     o[0] = r0 + packed[kOffRgbB];
     o[1] = r1 + packed[kOffRgbB + 1];
     o[2] = r2 + packed[kOffRgbB + 2];
+    if (kMask) *reinterpret_cast<uint4 *>(mask + pi * 4) = make_uint4(m[0], m[1], m[2], m[3]);
   }
+}
+
+__global__ __launch_bounds__(kTile) void nerfrender_head_kernel(RayPoints rp, const float *__restrict__ packed,
+                                                                const float *__restrict__ w_view, const float *__restrict__ b_view,
+                                                                const float *__restrict__ cam, int multires_views, int cam_ch,
+                                                                const float *__restrict__ gbuf, float *__restrict__ raw) {
+  head_tile<false>(rp, packed, w_view, b_view, cam, multires_views, cam_ch, gbuf, raw, nullptr);
 }
 
 // ---- per-ray reductions, float64 ---------------------------------------------------------------------------------------------
@@ -391,6 +405,364 @@ int render(const RenderCall &c) {
   return NRPN_OK;
 }
 
+// ---- camera-embedding objective (scripts/nerf_test.py --task test_opt; run_nerf.py optimize_camera_embedding :193-229) ---------
+// The embedding enters the network at views_linears.0 only: sigma, both sample lists and every compositing weight do not depend on
+// it.  prepare computes them once per image -- z2, the float64 weight of every sample in its own list's slot, and, for the chunks
+// that fit the budget, the trunk's g tiles.  An evaluation at one embedding then runs, per chunk of rays:
+//   head       the head above, which also writes the 128-bit mask g + c > 0 of every point
+//   colour     one thread per ray, float64: rgb = sum w sigmoid(raw) in merged order (the composite kernel's sum), e = rgb - target,
+//              the ray's loss term rw sum e^2 and dL/drgb = 2 rw e
+//   backward   one workgroup per tile: d[p][ch] = dL/drgb[ray][ch] w s (1 - s), A[j][ch] = sum_p mask[p][j] d[p][ch] in point order
+//   sum_rows   fixed-order float64 sums of the tiles' A, then of the chunks' A and of the rays' loss terms
+// and finish: dc[j] = sum_ch W_rgb[ch][j] A[j][ch], grad[k] = sum_j W_c[j][k] dc[j].  No atomics; a ray's rgb and loss term do not
+// depend on its chunk or tile, the sums over rays do only in their rounding.
+constexpr int kAcols = 3 * kHalf;     // A as [j][ch]
+constexpr int kSumRows = 256;         // rows one workgroup of sum_rows adds
+
+__global__ __launch_bounds__(kTile) void nerfcamopt_head_kernel(RayPoints rp, const float *__restrict__ packed,
+                                                                const float *__restrict__ w_view, const float *__restrict__ b_view,
+                                                                const float *__restrict__ cam, int multires_views, int cam_ch,
+                                                                const float *__restrict__ gbuf, float *__restrict__ raw,
+                                                                uint32_t *__restrict__ mask) {
+  head_tile<true>(rp, packed, w_view, b_view, cam, multires_views, cam_ch, gbuf, raw, mask);
+}
+
+struct MergeCursor {      // the composite kernel's order: the smaller head of the two lists, list 1 first on a tie
+  const float *za, *zb;
+  int S1, S2, ia, ib;
+  __device__ __forceinline__ bool next(int &i) {
+    const bool a = ib >= S2 || (ia < S1 && za[ia] <= zb[ib]);
+    i = a ? ia++ : ib++;
+    return a;
+  }
+};
+
+// raw1 [rays][S1][4], raw2 [rays][S2][4] (sigma only), z1 [S1] shared, z2 [rays][S2] -> w1 [rays][S1], w2 [rays][S2]: the weight the
+// composite kernel gives each sample, in the sample's own list
+__global__ void nerfcamopt_weights_kernel(const float *__restrict__ raw1, const float *__restrict__ z1, int S1,
+                                          const float *__restrict__ raw2, const float *__restrict__ z2, int S2,
+                                          const float *__restrict__ rays, int num_rays, double *__restrict__ w1, double *__restrict__ w2) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= num_rays) return;
+  const double nd = ray_norm(rays + (int64_t)r * 6 + 3);
+  const float *zb = z2 + (int64_t)r * S2;
+  const float *ra = raw1 + (int64_t)r * S1 * 4 + 3, *rb = raw2 + (int64_t)r * S2 * 4 + 3;
+  double *wa = w1 + (int64_t)r * S1, *wb = w2 + (int64_t)r * S2;
+  const int S = S1 + S2;
+  MergeCursor m{z1, zb, S1, S2, 0, 0};
+  int i;
+  bool a = m.next(i);
+  float zc = a ? z1[i] : zb[i], sg = a ? ra[4 * i] : rb[4 * i];
+  double *dst = a ? wa + i : wb + i;
+  double T = 1.0;
+  for (int s = 0; s < S; ++s) {
+    float zn = zc, sn = sg;
+    double *dn = dst;
+    if (s + 1 < S) {
+      a = m.next(i);
+      zn = a ? z1[i] : zb[i];
+      sn = a ? ra[4 * i] : rb[4 * i];
+      dn = a ? wa + i : wb + i;
+    }
+    const double dist = (s + 1 < S ? (double)zn - (double)zc : 1e10) * nd;
+    *dst = sample_weight(sg, dist, T);
+    zc = zn, sg = sn, dst = dn;
+  }
+}
+
+// raw1 / raw2: the heads' rgb; w1 / w2, z2, target [rays][3] and rw [rays] start at the chunk's first ray, terms and rgb likewise
+__global__ void nerfcamopt_colour_kernel(const float *__restrict__ raw1, const float *__restrict__ z1, int S1,
+                                         const float *__restrict__ raw2, const float *__restrict__ z2, int S2,
+                                         const double *__restrict__ w1, const double *__restrict__ w2, const float *__restrict__ target,
+                                         const double *__restrict__ rw, int num_rays, double *__restrict__ dl,
+                                         double *__restrict__ terms, float *__restrict__ rgb) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= num_rays) return;
+  const float *ra = raw1 + (int64_t)r * S1 * 4, *rb = raw2 + (int64_t)r * S2 * 4;
+  const double *wa = w1 + (int64_t)r * S1, *wb = w2 + (int64_t)r * S2;
+  MergeCursor m{z1, z2 + (int64_t)r * S2, S1, S2, 0, 0};
+  double c[3] = {0.0, 0.0, 0.0};
+  for (int s = 0; s < S1 + S2; ++s) {
+    int i;
+    const bool a = m.next(i);
+    const float *p = a ? ra + 4 * i : rb + 4 * i;
+    const double w = a ? wa[i] : wb[i];
+    c[0] += w / (1.0 + exp(-(double)p[0]));
+    c[1] += w / (1.0 + exp(-(double)p[1]));
+    c[2] += w / (1.0 + exp(-(double)p[2]));
+  }
+  const double q = rw[r];
+  double e[3];
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    e[ch] = c[ch] - (double)target[(int64_t)r * 3 + ch];
+    dl[(int64_t)r * 3 + ch] = 2.0 * q * e[ch];
+    if (rgb) rgb[(int64_t)r * 3 + ch] = (float)c[ch];
+  }
+  terms[r] = q * (e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
+}
+
+// One workgroup of 128 threads (thread j) per tile of 64 points of one pass: raw [points][4], mask [points][4], w [points] (the
+// pass's weights, ray-major like the points), dl [rays][3] -> partial [tile][128][3]
+__global__ __launch_bounds__(kHalf) void nerfcamopt_backward_kernel(const float *__restrict__ raw, const uint32_t *__restrict__ mask,
+                                                                    const double *__restrict__ w, const double *__restrict__ dl, int S,
+                                                                    int64_t num_points, double *__restrict__ partial) {
+  __shared__ double d[kTile][3];
+  __shared__ uint32_t mk[kTile][4];
+  const int t = threadIdx.x;
+  if (t < kTile) {
+    const int64_t pi = (int64_t)blockIdx.x * kTile + t;
+    const bool in = pi < num_points;
+    const int64_t ray = in ? pi / S : 0;
+    const double wp = in ? w[pi] : 0.0;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      double v = 0.0;
+      if (in) {
+        const double s = 1.0 / (1.0 + exp(-(double)raw[pi * 4 + ch]));
+        v = dl[ray * 3 + ch] * wp * s * (1.0 - s);
+      }
+      d[t][ch] = v;
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) mk[t][q] = in ? mask[pi * 4 + q] : 0u;
+  }
+  __syncthreads();
+  const int word = t >> 5, bit = t & 31;
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+  for (int p = 0; p < kTile; ++p) {
+    const bool on = (mk[p][word] >> bit) & 1u;
+    a0 += on ? d[p][0] : 0.0;
+    a1 += on ? d[p][1] : 0.0;
+    a2 += on ? d[p][2] : 0.0;
+  }
+  double *o = partial + (int64_t)blockIdx.x * kAcols + t * 3;
+  o[0] = a0, o[1] = a1, o[2] = a2;
+}
+
+// in [n][width] -> out [ceil(n / 256)][width]: thread (column, lane q of 4) adds rows q, q + 4, .. of its 256 in order, then
+// (q0 + q1) + (q2 + q3).  grid (ceil(n / 256), ceil(width / 64))
+__global__ __launch_bounds__(256) void nerfcamopt_sum_rows_kernel(const double *__restrict__ in, int64_t n, int width,
+                                                                  double *__restrict__ out) {
+  __shared__ double part[4][64];
+  const int t = threadIdx.x, col = blockIdx.y * 64 + (t & 63), q = t >> 6;
+  const int64_t row0 = (int64_t)blockIdx.x * kSumRows;
+  double a = 0.0;
+  if (col < width)
+    for (int i = q; i < kSumRows && row0 + i < n; i += 4) a += in[(row0 + i) * width + col];
+  part[q][t & 63] = a;
+  __syncthreads();
+  if (q == 0 && col < width) out[(int64_t)blockIdx.x * width + col] = (part[0][t] + part[1][t]) + (part[2][t] + part[3][t]);
+}
+
+// A [128][3], loss [1] -> out [1 + cam_ch]: the loss, then grad[k] = sum_j W_c[j][k] sum_ch W_rgb[ch][j] A[j][ch]
+__global__ __launch_bounds__(kHalf) void nerfcamopt_finish_kernel(const double *__restrict__ A, const double *__restrict__ loss,
+                                                                  const float *__restrict__ packed, const float *__restrict__ w_view,
+                                                                  int views_ch, int cam_ch, double *__restrict__ out) {
+  __shared__ double dc[kHalf];
+  const int j = threadIdx.x;
+  const float *wr = packed + kOffRgbW;
+  dc[j] = ((double)wr[j] * A[j * 3] + (double)wr[kHalf + j] * A[j * 3 + 1]) + (double)wr[2 * kHalf + j] * A[j * 3 + 2];
+  __syncthreads();
+  for (int k = j; k < cam_ch; k += kHalf) {
+    double g = 0.0;
+    for (int i = 0; i < kHalf; ++i) g += (double)w_view[i * (views_ch + cam_ch) + views_ch + k] * dc[i];
+    out[1 + k] = g;
+  }
+  if (j == 0) out[0] = loss[0];
+}
+
+// rows of the buffer that sum_rows' levels need after the n input rows
+int64_t sum_rows_extra(int64_t n) {
+  int64_t total = 0;
+  while (n > 1) {
+    n = cdiv64(n, kSumRows);
+    total += n;
+  }
+  return total;
+}
+
+// buf: n rows of width doubles followed by sum_rows_extra(n) rows -> *result, the row of their sums
+int sum_rows(double *buf, int64_t n, int width, hipStream_t stream, const double **result) {
+  while (n > 1) {
+    const int64_t m = cdiv64(n, kSumRows);
+    double *out = buf + n * width;
+    nerfcamopt_sum_rows_kernel<<<dim3((unsigned)m, (unsigned)((width + 63) / 64)), 256, 0, stream>>>(buf, n, width, out);
+    NRPN_LAUNCH_CHECK("nerfcamopt_sum_rows_kernel");
+    buf = out;
+    n = m;
+  }
+  *result = buf;
+  return NRPN_OK;
+}
+
+struct CamoptLayout {     // of the work buffer, in bytes; every part 16-byte aligned.  prepare uses raw1 .. gbuf only
+  int64_t raw1, raw2, gbuf, prepare_total, mask1, mask2, dl, partial, chunk_a, terms, total;
+  int64_t tiles1, tiles2, slot_floats;      // g tiles of a full chunk per pass; floats of a chunk's slot in the g cache
+};
+CamoptLayout camopt_layout(int64_t num_rays, int64_t chunk, int s1, int s2) {
+  auto al = [](int64_t b) { return (b + 15) / 16 * 16; };
+  CamoptLayout l{};
+  const int smax = s1 > s2 ? s1 : s2;
+  l.tiles1 = cdiv64(chunk * s1, kTile);
+  l.tiles2 = cdiv64(chunk * s2, kTile);
+  l.slot_floats = (l.tiles1 + l.tiles2) * kTile * kHalf;
+  l.raw1 = 0;
+  l.raw2 = l.raw1 + al(chunk * s1 * 16);
+  l.gbuf = l.raw2 + al(chunk * s2 * 16);
+  l.prepare_total = l.gbuf + cdiv64(chunk * smax, kTile) * kTile * kHalf * 4;
+  l.mask1 = l.prepare_total;
+  l.mask2 = l.mask1 + al(chunk * s1 * 16);
+  l.dl = l.mask2 + al(chunk * s2 * 16);
+  l.partial = l.dl + al(chunk * 3 * 8);
+  const int64_t tiles = l.tiles1 + l.tiles2, chunks = cdiv64(num_rays, chunk);
+  l.chunk_a = l.partial + (tiles + sum_rows_extra(tiles)) * kAcols * 8;
+  l.terms = l.chunk_a + (chunks + sum_rows_extra(chunks)) * kAcols * 8;
+  l.total = l.terms + al((num_rays + sum_rows_extra(num_rays)) * 8);
+  return l;
+}
+
+bool camopt_sizes_ok(int64_t num_rays, int64_t chunk, int s1, int s2) {
+  if (num_rays < 1 || num_rays >= ((int64_t)1 << 31) || chunk < 1 || s1 < 1 || s2 < 0 || s1 > 65536 || s2 > 65536) return false;
+  return (chunk < num_rays ? chunk : num_rays) * (s1 > s2 ? s1 : s2) < ((int64_t)1 << 31) - kTile;
+}
+
+struct CamoptCall {
+  const float *rays;        // [num_rays][6]
+  int64_t num_rays;
+  float cx, cy, cz, scale;
+  int multires;
+  const float *packed, *z1;
+  int s1;
+  const float *z2;          // [num_rays][s2]
+  int s2;
+  int64_t chunk;
+  float *gcache;
+  int64_t cached_chunks;
+  void *work;
+  int64_t work_bytes;
+  hipStream_t stream;
+};
+
+int camopt_check(const CamoptCall &c, const char *who) {
+  NRPN_REQUIRE(c.rays && c.packed && c.z1 && c.work, "%s: null pointer", who);
+  NRPN_REQUIRE(c.multires >= 0 && 3 + 6 * c.multires <= kEnc, "%s: multires %d does not fit %d encoding columns", who, c.multires, kEnc);
+  NRPN_REQUIRE(camopt_sizes_ok(c.num_rays, c.chunk, c.s1, c.s2), "%s: %lld rays in chunks of %lld with %d + %d samples", who,
+               (long long)c.num_rays, (long long)c.chunk, c.s1, c.s2);
+  NRPN_REQUIRE(c.s2 == 0 || c.z2, "%s: %d second-pass samples without z2", who, c.s2);
+  NRPN_REQUIRE(c.cached_chunks >= 0 && (c.cached_chunks == 0 || c.gcache), "%s: %lld cached chunks without a cache", who,
+               (long long)c.cached_chunks);
+  return NRPN_OK;
+}
+
+int camopt_prepare(const CamoptCall &c, const float *camera, int W, float near, float far, bool draw_z2, float *rays_out, float *z2_out,
+                   double *w1, double *w2) {
+  if (int rc = camopt_check(c, "nerfcamopt_prepare")) return rc;
+  NRPN_REQUIRE(w1 && (c.s2 == 0 || w2), "nerfcamopt_prepare: null output");
+  NRPN_REQUIRE(!draw_z2 || (c.s2 == c.s1 && c.s1 >= 3 && z2_out), "nerfcamopt_prepare: depth-guided sampling draws as many samples as pass 1 has, >= 3");
+  const int64_t chunk = c.chunk < c.num_rays ? c.chunk : c.num_rays;
+  const CamoptLayout lay = camopt_layout(c.num_rays, chunk, c.s1, c.s2);
+  NRPN_REQUIRE(c.work_bytes >= lay.prepare_total, "nerfcamopt_prepare: work buffer of %lld bytes is too small", (long long)c.work_bytes);
+  NRPN_LDS(nerfrender_trunk_kernel, kLdsBytes);
+  char *wk = static_cast<char *>(c.work);
+  float *raw1 = reinterpret_cast<float *>(wk + lay.raw1), *raw2 = reinterpret_cast<float *>(wk + lay.raw2);
+  int64_t ci = 0;
+  for (int64_t r0 = 0; r0 < c.num_rays; r0 += chunk, ++ci) {
+    const int n = (int)(c.num_rays - r0 < chunk ? c.num_rays - r0 : chunk);
+    const int blocks = (n + 63) / 64;
+    const float *rays = c.rays + r0 * 6;
+    if (camera) {
+      nerfrender_rays_kernel<<<blocks, 64, 0, c.stream>>>(camera, W, r0, n, rays_out + r0 * 6);
+      NRPN_LAUNCH_CHECK("nerfrender_rays_kernel");
+    }
+    float *scratch = reinterpret_cast<float *>(wk + lay.gbuf);
+    float *g1 = ci < c.cached_chunks ? c.gcache + ci * lay.slot_floats : scratch;
+    float *g2 = ci < c.cached_chunks ? g1 + lay.tiles1 * kTile * kHalf : scratch;
+    RayPoints rp{rays, c.z1, 0, c.s1, (int64_t)n * c.s1, c.cx, c.cy, c.cz, c.scale};
+    nerfrender_trunk_kernel<<<(int)cdiv64(rp.num_points, kTile), 256, kLdsBytes, c.stream>>>(rp, c.multires, c.packed, g1, raw1);
+    NRPN_LAUNCH_CHECK("nerfrender_trunk_kernel");
+    const float *z2 = c.s2 ? c.z2 + r0 * c.s2 : nullptr;
+    if (draw_z2) {
+      nerfrender_sample_kernel<<<blocks, 64, 0, c.stream>>>(raw1, rays, c.z1, c.s1, near, far, n, z2_out + r0 * c.s2);
+      NRPN_LAUNCH_CHECK("nerfrender_sample_kernel");
+    }
+    if (z2) {
+      RayPoints rp2{rays, z2, c.s2, c.s2, (int64_t)n * c.s2, c.cx, c.cy, c.cz, c.scale};
+      nerfrender_trunk_kernel<<<(int)cdiv64(rp2.num_points, kTile), 256, kLdsBytes, c.stream>>>(rp2, c.multires, c.packed, g2, raw2);
+      NRPN_LAUNCH_CHECK("nerfrender_trunk_kernel");
+    }
+    nerfcamopt_weights_kernel<<<blocks, 64, 0, c.stream>>>(raw1, c.z1, c.s1, raw2, z2 ? z2 : c.z1, c.s2, rays, n, w1 + r0 * c.s1,
+                                                           c.s2 ? w2 + r0 * c.s2 : w1);
+    NRPN_LAUNCH_CHECK("nerfcamopt_weights_kernel");
+  }
+  return NRPN_OK;
+}
+
+int camopt_eval(const CamoptCall &c, int multires_views, int cam_ch, const float *w_view, const float *b_view, const float *cam,
+                const double *w1, const double *w2, const float *target, const double *rw, double *out, float *rgb) {
+  if (int rc = camopt_check(c, "nerfcamopt_eval")) return rc;
+  NRPN_REQUIRE(w_view && b_view && cam && w1 && (c.s2 == 0 || w2) && target && rw && out, "nerfcamopt_eval: null pointer");
+  NRPN_REQUIRE(multires_views >= 0 && 3 + 6 * multires_views <= kMaxViewsCh && cam_ch >= 1 && cam_ch <= 65536,
+               "nerfcamopt_eval: multires_views %d / input_ch_cam %d", multires_views, cam_ch);
+  const int64_t chunk = c.chunk < c.num_rays ? c.chunk : c.num_rays;
+  const CamoptLayout lay = camopt_layout(c.num_rays, chunk, c.s1, c.s2);
+  NRPN_REQUIRE(c.work_bytes >= lay.total, "nerfcamopt_eval: work buffer of %lld bytes is too small", (long long)c.work_bytes);
+  NRPN_LDS(nerfrender_trunk_kernel, kLdsBytes);
+  char *wk = static_cast<char *>(c.work);
+  float *raw1 = reinterpret_cast<float *>(wk + lay.raw1), *raw2 = reinterpret_cast<float *>(wk + lay.raw2);
+  float *scratch = reinterpret_cast<float *>(wk + lay.gbuf);
+  uint32_t *mask1 = reinterpret_cast<uint32_t *>(wk + lay.mask1), *mask2 = reinterpret_cast<uint32_t *>(wk + lay.mask2);
+  double *dl = reinterpret_cast<double *>(wk + lay.dl), *partial = reinterpret_cast<double *>(wk + lay.partial);
+  double *chunk_a = reinterpret_cast<double *>(wk + lay.chunk_a), *terms = reinterpret_cast<double *>(wk + lay.terms);
+  int64_t ci = 0;
+  for (int64_t r0 = 0; r0 < c.num_rays; r0 += chunk, ++ci) {
+    const int n = (int)(c.num_rays - r0 < chunk ? c.num_rays - r0 : chunk);
+    const int blocks = (n + 63) / 64;
+    const float *rays = c.rays + r0 * 6;
+    const bool cached = ci < c.cached_chunks;
+    const float *z2 = c.s2 ? c.z2 + r0 * c.s2 : nullptr;
+    const RayPoints rps[2] = {{rays, c.z1, 0, c.s1, (int64_t)n * c.s1, c.cx, c.cy, c.cz, c.scale},
+                              {rays, z2, c.s2, c.s2, (int64_t)n * c.s2, c.cx, c.cy, c.cz, c.scale}};
+    float *const raws[2] = {raw1, raw2};
+    uint32_t *const masks[2] = {mask1, mask2};
+    int tiles[2] = {0, 0};
+    for (int pass = 0; pass < (c.s2 ? 2 : 1); ++pass) {
+      const RayPoints &rp = rps[pass];
+      tiles[pass] = (int)cdiv64(rp.num_points, kTile);
+      const float *g = scratch;
+      if (cached) {
+        g = c.gcache + ci * lay.slot_floats + (pass ? lay.tiles1 * kTile * kHalf : 0);
+      } else {      // the same kernel on the same points as in prepare: the same g
+        nerfrender_trunk_kernel<<<tiles[pass], 256, kLdsBytes, c.stream>>>(rp, c.multires, c.packed, scratch, raws[pass]);
+        NRPN_LAUNCH_CHECK("nerfrender_trunk_kernel");
+      }
+      nerfcamopt_head_kernel<<<tiles[pass], kTile, 0, c.stream>>>(rp, c.packed, w_view, b_view, cam, multires_views, cam_ch, g,
+                                                                  raws[pass], masks[pass]);
+      NRPN_LAUNCH_CHECK("nerfcamopt_head_kernel");
+    }
+    const double *wc1 = w1 + r0 * c.s1, *wc2 = c.s2 ? w2 + r0 * c.s2 : w1;
+    nerfcamopt_colour_kernel<<<blocks, 64, 0, c.stream>>>(raw1, c.z1, c.s1, raw2, z2 ? z2 : c.z1, c.s2, wc1, wc2, target + r0 * 3,
+                                                          rw + r0, n, dl, terms + r0, rgb ? rgb + r0 * 3 : nullptr);
+    NRPN_LAUNCH_CHECK("nerfcamopt_colour_kernel");
+    nerfcamopt_backward_kernel<<<tiles[0], kHalf, 0, c.stream>>>(raw1, mask1, wc1, dl, c.s1, rps[0].num_points, partial);
+    NRPN_LAUNCH_CHECK("nerfcamopt_backward_kernel");
+    if (c.s2) {
+      nerfcamopt_backward_kernel<<<tiles[1], kHalf, 0, c.stream>>>(raw2, mask2, wc2, dl, c.s2, rps[1].num_points,
+                                                                   partial + (int64_t)tiles[0] * kAcols);
+      NRPN_LAUNCH_CHECK("nerfcamopt_backward_kernel");
+    }
+    const double *a;
+    if (int rc = sum_rows(partial, tiles[0] + tiles[1], kAcols, c.stream, &a)) return rc;
+    NRPN_HIP(hipMemcpyAsync(chunk_a + ci * kAcols, a, kAcols * sizeof(double), hipMemcpyDeviceToDevice, c.stream));
+  }
+  const double *a, *loss;
+  if (int rc = sum_rows(chunk_a, ci, kAcols, c.stream, &a)) return rc;
+  if (int rc = sum_rows(terms, c.num_rays, 1, c.stream, &loss)) return rc;
+  nerfcamopt_finish_kernel<<<1, kHalf, 0, c.stream>>>(a, loss, c.packed, w_view, 3 + 6 * multires_views, cam_ch, out);
+  NRPN_LAUNCH_CHECK("nerfcamopt_finish_kernel");
+  return NRPN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -434,6 +806,39 @@ int nrpn_nerfrender_frame(int height, int width, const float *camera, float near
                multires_views, input_ch_cam, packed, w_view, b_view, embedded_cam, z1, s1, z2_mode, z2_in, s2, chunk, work, work_bytes,
                CompositeOut{rgb, depth, acc, disp, depth_std, z_vals, weights}, raw1_out, z2_out, as_stream(stream)};
   return render(c);
+}
+
+int64_t nrpn_nerfcamopt_work_bytes(int what, int64_t num_rays, int64_t chunk_rays, int s1, int s2) {
+  if (what < 0 || what > 2 || !camopt_sizes_ok(num_rays, chunk_rays, s1, s2)) return -1;
+  const CamoptLayout l = camopt_layout(num_rays, chunk_rays < num_rays ? chunk_rays : num_rays, s1, s2);
+  return what == 0 ? l.prepare_total : what == 1 ? l.total : l.slot_floats * 4;
+}
+
+int nrpn_nerfcamopt_prepare(const float *rays, int height, int width, const float *camera, int64_t num_rays, float near, float far,
+                            float center_x, float center_y, float center_z, float bb_scale, int multires, const float *packed,
+                            const float *z1, int s1, int z2_mode, const float *z2_in, int s2, int64_t chunk, void *work,
+                            int64_t work_bytes, float *rays_out, float *z2_out, double *w1, double *w2, float *g_cache,
+                            int64_t cached_chunks, nrpn_stream_t stream) {
+  NRPN_REQUIRE((rays != nullptr) != (camera != nullptr), "nerfcamopt_prepare: give rays or a camera");
+  NRPN_REQUIRE(!camera || (rays_out && height >= 1 && width >= 1 && (int64_t)height * width == num_rays),
+               "nerfcamopt_prepare: camera / %d x %d for %lld rays", height, width, (long long)num_rays);
+  NRPN_REQUIRE(z2_mode >= 0 && z2_mode <= 2 && (z2_mode == 0) == (s2 == 0), "nerfcamopt_prepare: z2 mode %d with %d second-pass samples",
+               z2_mode, s2);
+  NRPN_REQUIRE(z2_mode != 2 || z2_in, "nerfcamopt_prepare: z2 mode 2 without z2");
+  CamoptCall c{camera ? rays_out : rays, num_rays, center_x, center_y, center_z, bb_scale, multires, packed, z1, s1,
+               z2_mode == 1 ? z2_out : z2_in, s2, chunk, g_cache, cached_chunks, work, work_bytes, as_stream(stream)};
+  return camopt_prepare(c, camera, width, near, far, z2_mode == 1, rays_out, z2_out, w1, w2);
+}
+
+int nrpn_nerfcamopt_eval(const float *rays, int64_t num_rays, float center_x, float center_y, float center_z, float bb_scale,
+                         int multires, int multires_views, int input_ch_cam, const float *packed, const float *w_view,
+                         const float *b_view, const float *embedded_cam, const float *z1, int s1, const float *z2, int s2,
+                         const double *w1, const double *w2, const float *target, const double *ray_weight, int64_t chunk,
+                         const float *g_cache, int64_t cached_chunks, void *work, int64_t work_bytes, double *loss_grad, float *rgb,
+                         nrpn_stream_t stream) {
+  CamoptCall c{rays, num_rays, center_x, center_y, center_z, bb_scale, multires, packed, z1, s1, z2, s2, chunk,
+               const_cast<float *>(g_cache), cached_chunks, work, work_bytes, as_stream(stream)};
+  return camopt_eval(c, multires_views, input_ch_cam, w_view, b_view, embedded_cam, w1, w2, target, ray_weight, loss_grad, rgb);
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@ pointers + the current HIP stream to ``libnerfrpn_hip.so``.  Activations are cha
 """
 import itertools
 import math
+from types import SimpleNamespace
 
 import torch
 
@@ -2625,6 +2626,70 @@ def nerf_grid_query(state_dict, cfg, xs, ys, zs, bb_center, bb_scale, poses, lay
 NERF_RENDER_DEFAULT_CHUNK = 4096       # rays per launch group: 256 MiB of g scratch at 128 samples per pass
 
 
+def _nerf_render_inputs(who, weights_or_state, cfg, H, W, intrinsic, c2w, rays, near, far, bb_center, bb_scale, z_samples, n_samples,
+                        lindisp, embedded_cam, z2):
+    """The arguments nerf_render and nerf_camopt_prepare share, checked and on the device -> namespace."""
+    weights = weights_or_state if isinstance(weights_or_state, NerfGridWeights) else nerf_grid_pack(weights_or_state, cfg)
+    c, packed, dev = weights.config, weights.packed, weights.packed.device
+    if c != nerf_grid_config(cfg):
+        raise lib.NrpnError(f"{who}: the weights were packed for other options")
+
+    def f32(x, shape=None):
+        x = torch.as_tensor(x, dtype=torch.float32).to(dev)
+        return (x if shape is None else x.reshape(shape)).contiguous()
+    cam_ch = c["input_ch_cam"]
+    cam = torch.zeros(cam_ch, dtype=torch.float32, device=dev) if embedded_cam is None else f32(embedded_cam, -1)
+    if cam.numel() != cam_ch:
+        raise lib.NrpnError(f"{who}: embedded_cam has {cam.numel()} values, input_ch_cam is {cam_ch}")
+    if (near is None or far is None) and (z_samples is None or z2 is None):
+        raise lib.NrpnError(f"{who}: near and far are needed to place the samples")
+    near, far = (0. if near is None else float(near)), (0. if far is None else float(far))
+    if z_samples is not None:
+        z1 = f32(z_samples, -1)
+        s1 = int(z1.numel())
+        mode, s2 = (1, s1) if z2 is None else (2, int(torch.as_tensor(z2).shape[-1]))
+        if mode == 1 and s1 < 3:
+            raise lib.NrpnError(f"{who}: {s1} precomputed samples, the depth-guided pass needs at least 3")
+    else:
+        if z2 is not None:
+            raise lib.NrpnError(f"{who}: z2 goes with z_samples")
+        if n_samples is None or int(n_samples) < 1:
+            raise lib.NrpnError(f"{who}: n_samples {n_samples!r}")
+        # render_rays :571, :602-606 on [1, 1] bounds: the float32 values the reference gives every ray
+        t_vals = torch.linspace(0., 1., steps=int(n_samples))
+        n_t, f_t = torch.full((1, 1), near), torch.full((1, 1), far)
+        z1 = n_t * (1. - t_vals) + f_t * t_vals if not lindisp else 1. / (1. / n_t * (1. - t_vals) + 1. / f_t * t_vals)
+        z1 = f32(z1, -1)
+        s1, mode, s2 = int(z1.numel()), 0, 0
+    frame = [x is not None for x in (H, W, intrinsic, c2w)]
+    if rays is not None and any(frame):
+        raise lib.NrpnError(f"{who}: give H, W, intrinsic and c2w, or rays, not both")
+    if rays is not None:
+        rays_t = f32(rays)
+        if rays_t.dim() != 2 or rays_t.shape[1] != 6 or rays_t.shape[0] < 1:
+            raise lib.NrpnError(f"{who} expects rays [R, 6], got {tuple(rays_t.shape)}")
+        lead = (int(rays_t.shape[0]),)
+    else:
+        if not all(frame) or int(H) < 1 or int(W) < 1:
+            raise lib.NrpnError(f"{who}: give H, W, intrinsic and c2w, or rays")
+        pose = torch.as_tensor(c2w, dtype=torch.float32)
+        if pose.dim() != 2 or pose.shape[0] < 3 or pose.shape[1] != 4:
+            raise lib.NrpnError(f"{who} expects c2w [>=3, 4], got {tuple(pose.shape)}")
+        camera = f32(torch.cat([torch.as_tensor(intrinsic, dtype=torch.float32).reshape(4), pose[:3].reshape(12)]))
+        lead = (int(H), int(W))
+    n = lead[0] if len(lead) == 1 else lead[0] * lead[1]
+    z2_t = None
+    if mode == 2:
+        z2_t = f32(z2)
+        if tuple(z2_t.shape) != (n, s2) or s2 < 1:
+            raise lib.NrpnError(f"{who} expects z2 [{n}, S2], got {tuple(z2_t.shape)}")
+    cx, cy, cz = (float(v) for v in torch.as_tensor(bb_center, dtype=torch.float32).reshape(3).tolist())
+    scale = float(torch.as_tensor(bb_scale, dtype=torch.float32).reshape(()).item())
+    return SimpleNamespace(weights=weights, c=c, packed=packed, dev=dev, cam_ch=cam_ch, cam=cam, near=near, far=far, z1=z1, s1=s1, mode=mode,
+                           s2=s2, rays_t=rays_t if rays is not None else None, camera=camera if rays is None else None, lead=lead, n=n,
+                           z2_t=z2_t, center=(cx, cy, cz), scale=scale, f32=f32)
+
+
 def nerf_render(weights_or_state, cfg, H=None, W=None, intrinsic=None, c2w=None, rays=None, near=None, far=None, bb_center=(0., 0., 0.),
                 bb_scale=1., z_samples=None, n_samples=None, lindisp=False, embedded_cam=None, chunk=None, return_samples=False,
                 z2=None, return_stages=False):
@@ -2644,60 +2709,10 @@ def nerf_render(weights_or_state, cfg, H=None, W=None, intrinsic=None, c2w=None,
     -- plus depth_std = sqrt(clamp(sum((z - depth)^2 w), 0, 1)) (render_video :184-185), with leading shape (H, W) or (R,);
     return_samples adds z_vals and weights [.., S].  z2 [R, S2]: run the second pass on these samples instead of drawing them;
     return_stages adds raw1 [R, S1, 4] (the first pass's rgb before the sigmoid and sigma) and z2 (the drawn samples)."""
-    weights = weights_or_state if isinstance(weights_or_state, NerfGridWeights) else nerf_grid_pack(weights_or_state, cfg)
-    c, packed, dev = weights.config, weights.packed, weights.packed.device
-    if c != nerf_grid_config(cfg):
-        raise lib.NrpnError("nerf_render: the weights were packed for other options")
-
-    def f32(x, shape=None):
-        x = torch.as_tensor(x, dtype=torch.float32).to(dev)
-        return (x if shape is None else x.reshape(shape)).contiguous()
-    cam_ch = c["input_ch_cam"]
-    cam = torch.zeros(cam_ch, dtype=torch.float32, device=dev) if embedded_cam is None else f32(embedded_cam, -1)
-    if cam.numel() != cam_ch:
-        raise lib.NrpnError(f"nerf_render: embedded_cam has {cam.numel()} values, input_ch_cam is {cam_ch}")
-    if (near is None or far is None) and (z_samples is None or z2 is None):
-        raise lib.NrpnError("nerf_render: near and far are needed to place the samples")
-    near, far = (0. if near is None else float(near)), (0. if far is None else float(far))
-    if z_samples is not None:
-        z1 = f32(z_samples, -1)
-        s1 = int(z1.numel())
-        mode, s2 = (1, s1) if z2 is None else (2, int(torch.as_tensor(z2).shape[-1]))
-        if mode == 1 and s1 < 3:
-            raise lib.NrpnError(f"nerf_render: {s1} precomputed samples, the depth-guided pass needs at least 3")
-    else:
-        if z2 is not None:
-            raise lib.NrpnError("nerf_render: z2 goes with z_samples")
-        if n_samples is None or int(n_samples) < 1:
-            raise lib.NrpnError(f"nerf_render: n_samples {n_samples!r}")
-        # render_rays :571, :602-606 on [1, 1] bounds: the float32 values the reference gives every ray
-        t_vals = torch.linspace(0., 1., steps=int(n_samples))
-        n_t, f_t = torch.full((1, 1), near), torch.full((1, 1), far)
-        z1 = n_t * (1. - t_vals) + f_t * t_vals if not lindisp else 1. / (1. / n_t * (1. - t_vals) + 1. / f_t * t_vals)
-        z1 = f32(z1, -1)
-        s1, mode, s2 = int(z1.numel()), 0, 0
-    frame = [x is not None for x in (H, W, intrinsic, c2w)]
-    if rays is not None and any(frame):
-        raise lib.NrpnError("nerf_render: give H, W, intrinsic and c2w, or rays, not both")
-    if rays is not None:
-        rays_t = f32(rays)
-        if rays_t.dim() != 2 or rays_t.shape[1] != 6 or rays_t.shape[0] < 1:
-            raise lib.NrpnError(f"nerf_render expects rays [R, 6], got {tuple(rays_t.shape)}")
-        lead = (int(rays_t.shape[0]),)
-    else:
-        if not all(frame) or int(H) < 1 or int(W) < 1:
-            raise lib.NrpnError("nerf_render: give H, W, intrinsic and c2w, or rays")
-        pose = torch.as_tensor(c2w, dtype=torch.float32)
-        if pose.dim() != 2 or pose.shape[0] < 3 or pose.shape[1] != 4:
-            raise lib.NrpnError(f"nerf_render expects c2w [>=3, 4], got {tuple(pose.shape)}")
-        camera = f32(torch.cat([torch.as_tensor(intrinsic, dtype=torch.float32).reshape(4), pose[:3].reshape(12)]))
-        lead = (int(H), int(W))
-    n = lead[0] if len(lead) == 1 else lead[0] * lead[1]
-    z2_t = None
-    if mode == 2:
-        z2_t = f32(z2)
-        if tuple(z2_t.shape) != (n, s2) or s2 < 1:
-            raise lib.NrpnError(f"nerf_render expects z2 [{n}, S2], got {tuple(z2_t.shape)}")
+    a = _nerf_render_inputs("nerf_render", weights_or_state, cfg, H, W, intrinsic, c2w, rays, near, far, bb_center, bb_scale, z_samples,
+                            n_samples, lindisp, embedded_cam, z2)
+    weights, c, packed, dev, cam_ch, cam, near, far = a.weights, a.c, a.packed, a.dev, a.cam_ch, a.cam, a.near, a.far
+    z1, s1, mode, s2, rays_t, camera, lead, n, z2_t = a.z1, a.s1, a.mode, a.s2, a.rays_t, a.camera, a.lead, a.n, a.z2_t
     chunk = NERF_RENDER_DEFAULT_CHUNK if chunk is None else int(chunk)
     if chunk < 1:
         raise lib.NrpnError(f"nerf_render: chunk {chunk}")
@@ -2746,6 +2761,90 @@ def nerf_render_samples(raw, rays, z_samples, near, far):
     z2 = torch.empty((n, s), dtype=torch.float32, device=dev)
     call("nerfrender_samples", _p(raw), _p(rays), _p(z), s, float(near), float(far), n, _p(z2), _s())
     return z2
+
+
+# ======================================================================================================================
+# test-time optimisation of the camera embedding (scripts/nerf_test_opt.py)  [f8]
+# ======================================================================================================================
+class NerfCamoptState:
+    """What nerf_camopt_prepare keeps of one image for nerf_camopt_eval: the rays, the second-pass samples, every sample's float64
+    compositing weight, the trunk's g of the chunks that fit the cache, the target and the ray weights."""
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def nerf_camopt_prepare(weights_or_state, cfg, target, H=None, W=None, intrinsic=None, c2w=None, rays=None, near=None, far=None,
+                        bb_center=(0., 0., 0.), bb_scale=1., z_samples=None, n_samples=None, lindisp=False, chunk=None, z2=None,
+                        ray_weight=None, cache_bytes=None):
+    """Everything of optimize_camera_embedding's objective (run_nerf.py:193-229) that does not depend on the embedding, once per image.
+
+    The arguments of nerf_render select the model, the rays and the samples; ``target`` [R, 3] or [H, W, 3] float32 is the image;
+    ``ray_weight`` [R] float64 the weight rw of each ray's squared error (default 1 / (3 R), the image's mean squared error; the
+    reference's batches: camopt.ray_weights).  The embedding enters the network at views_linears.0 only, so sigma, both sample lists
+    and every compositing weight are computed here; ``cache_bytes`` (default: what all chunks need, capped at half of the free
+    device memory, torch's unused reserve included) decides how many chunks also keep the trunk's output g, 512 bytes per sample -- the others re-run the trunk at
+    every evaluation, to the same bits.  ``chunk`` fixes the chunks (default 4096 rays).  -> NerfCamoptState"""
+    a = _nerf_render_inputs("nerf_camopt_prepare", weights_or_state, cfg, H, W, intrinsic, c2w, rays, near, far, bb_center, bb_scale,
+                            z_samples, n_samples, lindisp, None, z2)
+    if a.cam_ch < 1:
+        raise lib.NrpnError("nerf_camopt_prepare: the model has no camera embedding (input_ch_cam is 0)")
+    dev, n, s1, s2 = a.dev, a.n, a.s1, a.s2
+    target = a.f32(target, (-1, 3))
+    if target.shape[0] != n:
+        raise lib.NrpnError(f"nerf_camopt_prepare: target has {target.shape[0]} pixels, there are {n} rays")
+    if ray_weight is None:
+        rw = torch.full((n,), 1. / (3. * n), dtype=torch.float64, device=dev)
+    else:
+        rw = torch.as_tensor(ray_weight, dtype=torch.float64).to(dev).reshape(-1).contiguous()
+        if rw.numel() != n:
+            raise lib.NrpnError(f"nerf_camopt_prepare: ray_weight has {rw.numel()} values, there are {n} rays")
+    chunk = NERF_RENDER_DEFAULT_CHUNK if chunk is None else int(chunk)
+    if chunk < 1:
+        raise lib.NrpnError(f"nerf_camopt_prepare: chunk {chunk}")
+    sizes = [lib.query("nerfcamopt_work_bytes", what, n, chunk, s1, s2) for what in range(3)]
+    if min(sizes) < 0:
+        raise lib.NrpnError(f"nerf_camopt_prepare: chunk {chunk} with {s1} + {s2} samples is outside the supported range")
+    chunks = -(-n // min(chunk, n))
+    if cache_bytes is None:       # free on the device, plus what torch's allocator holds but has not handed out
+        free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+        cache_bytes = min(chunks * sizes[2], free // 2)
+    cached = max(0, min(chunks, int(cache_bytes) // sizes[2]))
+    st = NerfCamoptState(inputs=a, n=n, lead=a.lead, chunk=chunk, chunks=chunks, cached_chunks=cached, g_bytes=cached * sizes[2],
+                         eval_bytes=sizes[1], target=target, rw=rw, work=None)
+    st.rays = a.rays_t if a.rays_t is not None else torch.empty((n, 6), dtype=torch.float32, device=dev)
+    st.z2 = a.z2_t if a.mode == 2 else torch.empty((n, s2), dtype=torch.float32, device=dev) if a.mode == 1 else None
+    st.w1 = torch.empty((n, s1), dtype=torch.float64, device=dev)
+    st.w2 = torch.empty((n, s2), dtype=torch.float64, device=dev) if s2 else None
+    st.g = torch.empty(cached * sizes[2] // 4, dtype=torch.float32, device=dev) if cached else None
+    work = torch.empty(sizes[0], dtype=torch.uint8, device=dev)
+    frame = a.camera is not None
+    call("nerfcamopt_prepare", None if frame else _p(st.rays), a.lead[0] if frame else 0, a.lead[1] if frame else 0,
+         _p(a.camera) if frame else None, n, a.near, a.far, *a.center, a.scale, a.c["multires"], _p(a.packed), _p(a.z1), s1, a.mode,
+         _p(a.z2_t) if a.mode == 2 else None, s2, chunk, _p(work), sizes[0], _p(st.rays) if frame else None,
+         _p(st.z2) if a.mode == 1 else None, _p(st.w1), _p(st.w2) if s2 else None, _p(st.g) if cached else None, cached, _s())
+    return st
+
+
+def nerf_camopt_eval(state, cam, return_rgb=False):
+    """The objective of optimize_camera_embedding at the embedding ``cam`` [input_ch_cam] for a prepared image: -> (loss, grad) or
+    (loss, grad, rgb_map).  loss (a Python float) = sum_r rw[r] sum_ch (rgb_map - target)^2 and grad (float64 [input_ch_cam], on the
+    device) its derivative; rgb_map (float32, shaped like nerf_render's) is bit-equal to nerf_render's at this embedding.  float64
+    after the head's raw rgb, fixed-order sums: repeated calls are bit-equal, and so are different cache budgets."""
+    st, a = state, state.inputs
+    dev = a.dev
+    cam = a.f32(cam, -1)
+    if cam.numel() != a.cam_ch:
+        raise lib.NrpnError(f"nerf_camopt_eval: cam has {cam.numel()} values, input_ch_cam is {a.cam_ch}")
+    if st.work is None:
+        st.work = torch.empty(st.eval_bytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(1 + a.cam_ch, dtype=torch.float64, device=dev)
+    rgb = torch.empty((st.n, 3), dtype=torch.float32, device=dev) if return_rgb else None
+    call("nerfcamopt_eval", _p(st.rays), st.n, *a.center, a.scale, a.c["multires"], a.c["multires_views"], a.cam_ch, _p(a.packed),
+         _p(a.weights.w_view), _p(a.weights.b_views), _p(cam), _p(a.z1), a.s1, _p(st.z2) if a.s2 else None, a.s2, _p(st.w1),
+         _p(st.w2) if a.s2 else None, _p(st.target), _p(st.rw), st.chunk, _p(st.g) if st.cached_chunks else None, st.cached_chunks,
+         _p(st.work), st.eval_bytes, _p(out), _p(rgb) if return_rgb else None, _s())
+    loss = float(out[0].item())
+    return (loss, out[1:], rgb.reshape(*st.lead, 3)) if return_rgb else (loss, out[1:])
 
 
 # ======================================================================================================================

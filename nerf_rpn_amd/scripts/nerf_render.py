@@ -126,12 +126,12 @@ def prepare(args, tool='nerf_render', transforms_name='transforms_test.json'):
                            n_samples=n_samples, lindisp=lindisp)
 
 
-def render_frame(run, i, chunk=None):
-    """ops.nerf_render of frame i of a prepared run."""
+def render_frame(run, i, chunk=None, embedded_cam=None):
+    """ops.nerf_render of frame i of a prepared run (embedded_cam None: the zero embedding)."""
     from nerf_rpn_amd import ops
     return ops.nerf_render(run.weights, run.cfg, H=run.H, W=run.W, intrinsic=run.intrinsics[i], c2w=run.poses[i][:3, :4], near=run.near,
                            far=run.far, bb_center=run.bb_center, bb_scale=run.bb_scale, z_samples=run.z_samples, n_samples=run.n_samples,
-                           lindisp=run.lindisp, chunk=chunk)
+                           lindisp=run.lindisp, chunk=chunk, embedded_cam=embedded_cam)
 
 
 def main(argv=None):
