@@ -182,6 +182,43 @@ __device__ __forceinline__ double sample_weight(float sigma, double dist, double
   return w;
 }
 
+struct MergeCursor {      // the order of a ray's two non-decreasing sample lists: the smaller head first, list 1 on a tie
+  const float *za, *zb;
+  int S1, S2, ia, ib;
+  __device__ __forceinline__ bool next(int &i) {
+    const bool a = ib >= S2 || (ia < S1 && za[ia] <= zb[ib]);
+    i = a ? ia++ : ib++;
+    return a;
+  }
+};
+
+// One ray's samples in merged order: visit(from list 1?, index in that list, z, weight).  The weight is compute_weights' of the sample
+// in the merged list: dist to the next sample times |d| = nd, 1e10 after the last.  sa / sb: the lists' sigma, 4 floats apart; it is
+// loaded with its z, one sample ahead of its use: a thread's loop waits on these loads and on little else
+template <class Visit>
+__device__ __forceinline__ void merged_walk(const float *za, const float *sa, int S1, const float *zb, const float *sb, int S2,
+                                            double nd, Visit &&visit) {
+  MergeCursor m{za, zb, S1, S2, 0, 0};
+  const int S = S1 + S2;
+  int i;
+  bool a = m.next(i);
+  float zc = a ? za[i] : zb[i], sg = a ? sa[4 * i] : sb[4 * i];
+  double T = 1.0;
+  for (int s = 0; s < S; ++s) {
+    int in = i;
+    bool an = a;
+    float zn = zc, sn = sg;
+    if (s + 1 < S) {
+      an = m.next(in);
+      zn = an ? za[in] : zb[in];
+      sn = an ? sa[4 * in] : sb[4 * in];
+    }
+    const double dist = (s + 1 < S ? (double)zn - (double)zc : 1e10) * nd;
+    visit(a, i, zc, sample_weight(sg, dist, T));
+    a = an, i = in, zc = zn, sg = sn;
+  }
+}
+
 struct Bins {           // sample_3sigma (:471-478): edges and weights of the N - 1 bins between depth -+ 3 std, clamped to [near, far]
   double lo, hi, step, near, far;
   int N;
@@ -204,18 +241,12 @@ __global__ void nerfrender_sample_kernel(const float *__restrict__ raw, const fl
   if (r >= num_rays) return;
   const double nd = ray_norm(rays + (int64_t)r * 6 + 3);
   const float *sg = raw + (int64_t)r * S * 4 + 3;
-  double T = 1.0, depth = 0.0;
-  for (int s = 0; s < S; ++s) {
-    const double dist = (s + 1 < S ? (double)z[s + 1] - (double)z[s] : 1e10) * nd;
-    depth += sample_weight(sg[4 * s], dist, T) * (double)z[s];
-  }
-  T = 1.0;
-  double var = 0.0;
-  for (int s = 0; s < S; ++s) {
-    const double dist = (s + 1 < S ? (double)z[s + 1] - (double)z[s] : 1e10) * nd;
-    const double dz = (double)z[s] - depth;
-    var += dz * dz * sample_weight(sg[4 * s], dist, T);
-  }
+  double depth = 0.0, var = 0.0;         // two walks of the one list: the depth, then the variance about it
+  merged_walk(z, sg, S, nullptr, nullptr, 0, nd, [&](bool, int, float zv, double w) { depth += w * (double)zv; });
+  merged_walk(z, sg, S, nullptr, nullptr, 0, nd, [&](bool, int, float zv, double w) {
+    const double dz = (double)zv - depth;
+    var += dz * dz * w;
+  });
   const double std = fmax(sqrt(var), (double)z[S - 1] - (double)z[S - 2]);
   Bins b;
   b.lo = depth - 3.0 * std, b.hi = depth + 3.0 * std, b.N = S, b.near = near, b.far = far;
@@ -260,24 +291,11 @@ __global__ void nerfrender_composite_kernel(const float *__restrict__ raw1, cons
   const float *ra = raw1 + (int64_t)r * S1 * 4, *rb = raw2 + (int64_t)r * S2 * 4;
   const int S = S1 + S2;
   const int64_t gr = ray0 + r;
-  int ia = 0, ib = 0;
-  // the current sample: the smaller head of the two lists, list 1 first on a tie
-  auto take = [&](const float *&rw) {
-    const bool a = ib >= S2 || (ia < S1 && za[ia] <= zb[ib]);
-    const float zv = a ? za[ia] : zb[ib];
-    rw = a ? ra + 4 * ia : rb + 4 * ib;
-    a ? ++ia : ++ib;
-    return zv;
-  };
-  const float *rw;
-  float zc = take(rw);
-  const double shift = zc;
-  double T = 1.0, acc = 0.0, m1 = 0.0, m2 = 0.0, c0 = 0.0, c1 = 0.0, c2 = 0.0;
-  for (int s = 0; s < S; ++s) {
-    const float *rnext = rw;
-    const float zn = s + 1 < S ? take(rnext) : zc;
-    const double dist = (s + 1 < S ? (double)zn - (double)zc : 1e10) * nd;
-    const double w = sample_weight(rw[3], dist, T);
+  int s = 0;
+  double shift = 0.0, acc = 0.0, m1 = 0.0, m2 = 0.0, c0 = 0.0, c1 = 0.0, c2 = 0.0;
+  merged_walk(za, ra + 3, S1, zb, rb + 3, S2, nd, [&](bool a, int i, float zc, double w) {
+    const float *rw = a ? ra + 4 * i : rb + 4 * i;
+    if (s == 0) shift = zc;
     const double dz = (double)zc - shift;
     acc += w;
     m1 += w * dz;
@@ -287,9 +305,8 @@ __global__ void nerfrender_composite_kernel(const float *__restrict__ raw1, cons
     c2 += w / (1.0 + exp(-(double)rw[2]));
     if (o.z_vals) o.z_vals[gr * S + s] = zc;
     if (o.weights) o.weights[gr * S + s] = (float)w;
-    zc = zn;
-    rw = rnext;
-  }
+    ++s;
+  });
   const double depth = shift * acc + m1;
   // sum w (z - depth)^2 with z - depth = dz - e, e = depth - shift
   const double e = depth - shift;
@@ -305,101 +322,157 @@ __global__ void nerfrender_composite_kernel(const float *__restrict__ raw1, cons
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
-struct Layout {           // of the work buffer, in bytes; every part 16-byte aligned
-  int64_t rays, raw1, raw2, z2, gbuf, total;
-};
-Layout work_layout(int64_t chunk, int s1, int s2) {
-  auto al = [](int64_t b) { return (b + 15) / 16 * 16; };
-  Layout l{};
-  const int smax = s1 > s2 ? s1 : s2;
-  l.rays = 0;
-  l.raw1 = l.rays + al(chunk * 6 * 4);
-  l.raw2 = l.raw1 + al(chunk * s1 * 16);
-  l.z2 = l.raw2 + al(chunk * s2 * 16);
-  l.gbuf = l.z2 + al(chunk * s2 * 4);
-  l.total = l.gbuf + cdiv64(chunk * smax, kTile) * kTile * kHalf * 4;
-  return l;
+constexpr int64_t kMaxRenderRays = (int64_t)1 << 40, kMaxCamoptRays = (int64_t)1 << 31;
+
+// The limits every size query and entry point shares: num_rays rays (below max_rays) in chunks of ``chunk`` with s1 + s2 samples per
+// ray; the points of a chunk's pass, rounded up to tiles, are counted in an int
+bool sizes_ok(int64_t num_rays, int64_t max_rays, int64_t chunk, int s1, int s2) {
+  if (num_rays < 1 || num_rays >= max_rays || chunk < 1 || s1 < 1 || s2 < 0 || s1 > 65536 || s2 > 65536) return false;
+  const int64_t n = chunk < num_rays ? chunk : num_rays;
+  return n < ((int64_t)1 << 31) && n * (s1 > s2 ? s1 : s2) < ((int64_t)1 << 31) - kTile;
 }
 
-struct RenderCall {
-  const float *rays, *camera;       // one of them
-  int W;
+int check_model(const char *who, int multires, int multires_views, int cam_ch) {
+  NRPN_REQUIRE(multires >= 0 && 3 + 6 * multires <= kEnc, "%s: multires %d does not fit %d encoding columns", who, multires, kEnc);
+  NRPN_REQUIRE(multires_views >= 0 && 3 + 6 * multires_views <= kMaxViewsCh && cam_ch >= 0 && cam_ch <= 65536,
+               "%s: multires_views %d / input_ch_cam %d", who, multires_views, cam_ch);
+  return NRPN_OK;
+}
+
+// z2_mode 0: one pass; 1: s2 = s1 samples drawn around the first pass's depth; 2: the s2 samples of z2_in
+int check_samples(const char *who, int z2_mode, int s1, int s2, const float *z2_in) {
+  NRPN_REQUIRE(z2_mode >= 0 && z2_mode <= 2 && (z2_mode == 0) == (s2 == 0), "%s: z2 mode %d with %d second-pass samples", who, z2_mode, s2);
+  NRPN_REQUIRE(z2_mode != 1 || (s2 == s1 && s1 >= 3), "%s: depth-guided sampling draws as many samples as pass 1 has, >= 3", who);
+  NRPN_REQUIRE(z2_mode != 2 || z2_in, "%s: z2 mode 2 without z2", who);
+  return NRPN_OK;
+}
+
+struct RayCall {          // what a render and the camera-embedding objective share
   int64_t num_rays;
-  float near, far, cx, cy, cz, scale;
-  int multires, multires_views, cam_ch;
-  const float *packed, *w_view, *b_view, *cam, *z1;
-  int s1, z2_mode;
-  const float *z2_in;
-  int s2;
+  float cx, cy, cz, scale;
+  int multires;
+  const float *packed, *z1;
+  int s1, s2;
   int64_t chunk;
   void *work;
   int64_t work_bytes;
-  CompositeOut out;
-  float *raw1_out, *z2_out;
   hipStream_t stream;
+  int64_t chunk_rays() const { return chunk < num_rays ? chunk : num_rays; }
+  int64_t chunks() const { return cdiv64(num_rays, chunk_rays()); }
 };
 
-int mlp_pass(const RenderCall &c, RayPoints rp, float *gbuf, float *raw) {
-  const int tiles = (int)cdiv64(rp.num_points, kTile);
-  nerfrender_trunk_kernel<<<tiles, 256, kLdsBytes, c.stream>>>(rp, c.multires, c.packed, gbuf, raw);
+int check_call(const char *who, const RayCall &c, int64_t max_rays) {
+  NRPN_REQUIRE(c.packed && c.z1 && c.work, "%s: null pointer", who);
+  NRPN_REQUIRE(sizes_ok(c.num_rays, max_rays, c.chunk, c.s1, c.s2), "%s: %lld rays in chunks of %lld with %d + %d samples", who,
+               (long long)c.num_rays, (long long)c.chunk, c.s1, c.s2);
+  return NRPN_OK;
+}
+
+// after check_call: the work buffer holds ``need`` bytes and the trunk may have its LDS
+int check_work(const char *who, const RayCall &c, int64_t need) {
+  NRPN_REQUIRE(c.work_bytes >= need, "%s: work buffer of %lld bytes is too small", who, (long long)c.work_bytes);
+  NRPN_LDS(nerfrender_trunk_kernel, kLdsBytes);
+  return NRPN_OK;
+}
+
+int64_t align16(int64_t b) { return (b + 15) / 16 * 16; }
+
+struct PassLayout {       // of a chunk's two passes in the work buffer, in bytes; every part 16-byte aligned
+  int64_t raw1, raw2, z2, gbuf, end;      // z2: the drawn samples, where the caller keeps them here
+};
+PassLayout pass_layout(int64_t at, int64_t chunk, int s1, int s2, bool with_z2) {
+  PassLayout l{};
+  const int smax = s1 > s2 ? s1 : s2;
+  l.raw1 = at;
+  l.raw2 = l.raw1 + align16(chunk * s1 * 16);
+  l.z2 = l.raw2 + align16(chunk * s2 * 16);
+  l.gbuf = l.z2 + (with_z2 ? align16(chunk * s2 * 4) : 0);
+  l.end = l.gbuf + cdiv64(chunk * smax, kTile) * kTile * kHalf * 4;
+  return l;
+}
+// a render's work buffer: the chunk's generated rays at byte 0, then the passes
+PassLayout render_layout(int64_t chunk, int s1, int s2) { return pass_layout(align16(chunk * 6 * 4), chunk, s1, s2, true); }
+
+struct Chunk {
+  int64_t r0;               // its first ray
+  int n, blocks;            // rays; workgroups of the one-thread-per-ray kernels
+  const float *rays, *z2;   // of its rays; z2 null without a second pass
+  const float *zb;          // z2, or z1 without a second pass: the per-ray kernels then read nothing of it
+  RayPoints rp[2];          // pass 1 over the shared z1, pass 2 over z2
+  int tiles[2];
+};
+// rays / z2: the call's arrays (whole: the chunk starts at ray r0 of them) or buffers that hold one chunk
+Chunk chunk_at(const RayCall &c, int64_t ci, const float *rays, bool rays_whole, const float *z2, bool z2_whole) {
+  Chunk k{};
+  k.r0 = ci * c.chunk_rays();
+  k.n = (int)(c.num_rays - k.r0 < c.chunk_rays() ? c.num_rays - k.r0 : c.chunk_rays());
+  k.blocks = (k.n + 63) / 64;
+  k.rays = rays + (rays_whole ? k.r0 * 6 : 0);
+  k.z2 = c.s2 ? z2 + (z2_whole ? k.r0 * c.s2 : 0) : nullptr;
+  k.zb = k.z2 ? k.z2 : c.z1;
+  k.rp[0] = RayPoints{k.rays, c.z1, 0, c.s1, (int64_t)k.n * c.s1, c.cx, c.cy, c.cz, c.scale};
+  k.rp[1] = RayPoints{k.rays, k.z2, c.s2, c.s2, (int64_t)k.n * c.s2, c.cx, c.cy, c.cz, c.scale};
+  for (int pass = 0; pass < 2; ++pass) k.tiles[pass] = (int)cdiv64(k.rp[pass].num_points, kTile);
+  return k;
+}
+
+int launch_trunk(const RayCall &c, const RayPoints &rp, float *gbuf, float *raw) {
+  nerfrender_trunk_kernel<<<(int)cdiv64(rp.num_points, kTile), 256, kLdsBytes, c.stream>>>(rp, c.multires, c.packed, gbuf, raw);
   NRPN_LAUNCH_CHECK("nerfrender_trunk_kernel");
-  nerfrender_head_kernel<<<tiles, kTile, 0, c.stream>>>(rp, c.packed, c.w_view, c.b_view, c.cam, c.multires_views, c.cam_ch, gbuf, raw);
+  return NRPN_OK;
+}
+
+struct RenderCall : RayCall {
+  const float *rays, *camera;       // one of them
+  int W;
+  float near, far;
+  int multires_views, cam_ch;
+  const float *w_view, *b_view, *cam;
+  int z2_mode;
+  const float *z2_in;
+  CompositeOut out;
+  float *raw1_out, *z2_out;
+};
+
+int mlp_pass(const RenderCall &c, const Chunk &k, int pass, float *gbuf, float *raw) {
+  if (int rc = launch_trunk(c, k.rp[pass], gbuf, raw)) return rc;
+  nerfrender_head_kernel<<<k.tiles[pass], kTile, 0, c.stream>>>(k.rp[pass], c.packed, c.w_view, c.b_view, c.cam, c.multires_views,
+                                                                c.cam_ch, gbuf, raw);
   NRPN_LAUNCH_CHECK("nerfrender_head_kernel");
   return NRPN_OK;
 }
 
 int render(const RenderCall &c) {
-  NRPN_REQUIRE(c.packed && c.w_view && c.b_view && c.z1 && c.work, "nerfrender: null pointer");
+  if (int rc = check_call("nerfrender", c, kMaxRenderRays)) return rc;
+  NRPN_REQUIRE(c.w_view && c.b_view, "nerfrender: null pointer");
   NRPN_REQUIRE(c.cam_ch == 0 || c.cam, "nerfrender: input_ch_cam %d without an embedded_cam", c.cam_ch);
   NRPN_REQUIRE(c.out.rgb && c.out.depth && c.out.acc && c.out.disp && c.out.depth_std, "nerfrender: null output");
-  NRPN_REQUIRE(c.num_rays >= 1 && c.num_rays < ((int64_t)1 << 40), "nerfrender: %lld rays", (long long)c.num_rays);
-  NRPN_REQUIRE(c.multires >= 0 && 3 + 6 * c.multires <= kEnc, "nerfrender: multires %d does not fit %d encoding columns", c.multires, kEnc);
-  NRPN_REQUIRE(c.multires_views >= 0 && 3 + 6 * c.multires_views <= kMaxViewsCh && c.cam_ch >= 0,
-               "nerfrender: multires_views %d / input_ch_cam %d", c.multires_views, c.cam_ch);
-  NRPN_REQUIRE(c.z2_mode >= 0 && c.z2_mode <= 2, "nerfrender: z2 mode %d", c.z2_mode);
-  NRPN_REQUIRE(c.s1 >= 1 && c.s1 <= 65536 && c.s2 >= 0 && c.s2 <= 65536, "nerfrender: %d + %d samples", c.s1, c.s2);
-  NRPN_REQUIRE((c.z2_mode == 0) == (c.s2 == 0), "nerfrender: z2 mode %d with %d second-pass samples", c.z2_mode, c.s2);
-  NRPN_REQUIRE(c.z2_mode != 1 || (c.s2 == c.s1 && c.s1 >= 3), "nerfrender: depth-guided sampling draws as many samples as pass 1 has, >= 3");
-  NRPN_REQUIRE(c.z2_mode != 2 || c.z2_in, "nerfrender: z2 mode 2 without z2");
-  NRPN_REQUIRE(c.chunk >= 1, "nerfrender: chunk %lld", (long long)c.chunk);
-  const int64_t chunk = c.chunk < c.num_rays ? c.chunk : c.num_rays;
-  const int smax = c.s1 > c.s2 ? c.s1 : c.s2;
-  NRPN_REQUIRE(chunk * smax < ((int64_t)1 << 31) - kTile, "nerfrender: chunk too large");
-  const Layout lay = work_layout(chunk, c.s1, c.s2);
-  NRPN_REQUIRE(c.work_bytes >= lay.total, "nerfrender: work buffer of %lld bytes is too small", (long long)c.work_bytes);
-  NRPN_LDS(nerfrender_trunk_kernel, kLdsBytes);
+  if (int rc = check_model("nerfrender", c.multires, c.multires_views, c.cam_ch)) return rc;
+  if (int rc = check_samples("nerfrender", c.z2_mode, c.s1, c.s2, c.z2_in)) return rc;
+  const PassLayout lay = render_layout(c.chunk_rays(), c.s1, c.s2);
+  if (int rc = check_work("nerfrender", c, lay.end)) return rc;
   char *wk = static_cast<char *>(c.work);
-  float *gbuf = reinterpret_cast<float *>(wk + lay.gbuf);
-  for (int64_t r0 = 0; r0 < c.num_rays; r0 += chunk) {
-    const int n = (int)(c.num_rays - r0 < chunk ? c.num_rays - r0 : chunk);
-    const int blocks = (n + 63) / 64;
-    const float *rays;
-    if (c.rays) {
-      rays = c.rays + r0 * 6;
-    } else {
-      float *gen = reinterpret_cast<float *>(wk + lay.rays);
-      nerfrender_rays_kernel<<<blocks, 64, 0, c.stream>>>(c.camera, c.W, r0, n, gen);
+  float *gen = reinterpret_cast<float *>(wk), *gbuf = reinterpret_cast<float *>(wk + lay.gbuf);
+  float *raw2 = reinterpret_cast<float *>(wk + lay.raw2);
+  // drawn samples go to z2_out or, a chunk at a time, to the work buffer
+  float *z2_drawn = c.z2_out ? c.z2_out : reinterpret_cast<float *>(wk + lay.z2);
+  for (int64_t ci = 0; ci < c.chunks(); ++ci) {
+    const Chunk k = chunk_at(c, ci, c.rays ? c.rays : gen, c.rays != nullptr, c.z2_mode == 1 ? z2_drawn : c.z2_in,
+                             c.z2_mode == 2 || c.z2_out);
+    if (!c.rays) {
+      nerfrender_rays_kernel<<<k.blocks, 64, 0, c.stream>>>(c.camera, c.W, k.r0, k.n, gen);
       NRPN_LAUNCH_CHECK("nerfrender_rays_kernel");
-      rays = gen;
     }
-    float *raw1 = c.raw1_out ? c.raw1_out + r0 * c.s1 * 4 : reinterpret_cast<float *>(wk + lay.raw1);
-    float *raw2 = reinterpret_cast<float *>(wk + lay.raw2);
-    RayPoints rp{rays, c.z1, 0, c.s1, (int64_t)n * c.s1, c.cx, c.cy, c.cz, c.scale};
-    if (int rc = mlp_pass(c, rp, gbuf, raw1)) return rc;
-    const float *z2 = nullptr;
+    float *raw1 = c.raw1_out ? c.raw1_out + k.r0 * c.s1 * 4 : reinterpret_cast<float *>(wk + lay.raw1);
+    if (int rc = mlp_pass(c, k, 0, gbuf, raw1)) return rc;
     if (c.z2_mode == 1) {
-      float *zs = c.z2_out ? c.z2_out + r0 * c.s2 : reinterpret_cast<float *>(wk + lay.z2);
-      nerfrender_sample_kernel<<<blocks, 64, 0, c.stream>>>(raw1, rays, c.z1, c.s1, c.near, c.far, n, zs);
+      nerfrender_sample_kernel<<<k.blocks, 64, 0, c.stream>>>(raw1, k.rays, c.z1, c.s1, c.near, c.far, k.n,
+                                                              const_cast<float *>(k.z2));      // in z2_drawn
       NRPN_LAUNCH_CHECK("nerfrender_sample_kernel");
-      z2 = zs;
-    } else if (c.z2_mode == 2) {
-      z2 = c.z2_in + r0 * c.s2;
     }
-    if (z2) {
-      RayPoints rp2{rays, z2, c.s2, c.s2, (int64_t)n * c.s2, c.cx, c.cy, c.cz, c.scale};
-      if (int rc = mlp_pass(c, rp2, gbuf, raw2)) return rc;
-    }
-    nerfrender_composite_kernel<<<blocks, 64, 0, c.stream>>>(raw1, c.z1, 0, c.s1, raw2, z2 ? z2 : c.z1, c.s2, rays, n, r0, c.out);
+    if (k.z2)
+      if (int rc = mlp_pass(c, k, 1, gbuf, raw2)) return rc;
+    nerfrender_composite_kernel<<<k.blocks, 64, 0, c.stream>>>(raw1, c.z1, 0, c.s1, raw2, k.zb, c.s2, k.rays, k.n, k.r0, c.out);
     NRPN_LAUNCH_CHECK("nerfrender_composite_kernel");
   }
   return NRPN_OK;
@@ -427,16 +500,6 @@ __global__ __launch_bounds__(kTile) void nerfcamopt_head_kernel(RayPoints rp, co
   head_tile<true>(rp, packed, w_view, b_view, cam, multires_views, cam_ch, gbuf, raw, mask);
 }
 
-struct MergeCursor {      // the composite kernel's order: the smaller head of the two lists, list 1 first on a tie
-  const float *za, *zb;
-  int S1, S2, ia, ib;
-  __device__ __forceinline__ bool next(int &i) {
-    const bool a = ib >= S2 || (ia < S1 && za[ia] <= zb[ib]);
-    i = a ? ia++ : ib++;
-    return a;
-  }
-};
-
 // raw1 [rays][S1][4], raw2 [rays][S2][4] (sigma only), z1 [S1] shared, z2 [rays][S2] -> w1 [rays][S1], w2 [rays][S2]: the weight the
 // composite kernel gives each sample, in the sample's own list
 __global__ void nerfcamopt_weights_kernel(const float *__restrict__ raw1, const float *__restrict__ z1, int S1,
@@ -445,29 +508,9 @@ __global__ void nerfcamopt_weights_kernel(const float *__restrict__ raw1, const 
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= num_rays) return;
   const double nd = ray_norm(rays + (int64_t)r * 6 + 3);
-  const float *zb = z2 + (int64_t)r * S2;
-  const float *ra = raw1 + (int64_t)r * S1 * 4 + 3, *rb = raw2 + (int64_t)r * S2 * 4 + 3;
   double *wa = w1 + (int64_t)r * S1, *wb = w2 + (int64_t)r * S2;
-  const int S = S1 + S2;
-  MergeCursor m{z1, zb, S1, S2, 0, 0};
-  int i;
-  bool a = m.next(i);
-  float zc = a ? z1[i] : zb[i], sg = a ? ra[4 * i] : rb[4 * i];
-  double *dst = a ? wa + i : wb + i;
-  double T = 1.0;
-  for (int s = 0; s < S; ++s) {
-    float zn = zc, sn = sg;
-    double *dn = dst;
-    if (s + 1 < S) {
-      a = m.next(i);
-      zn = a ? z1[i] : zb[i];
-      sn = a ? ra[4 * i] : rb[4 * i];
-      dn = a ? wa + i : wb + i;
-    }
-    const double dist = (s + 1 < S ? (double)zn - (double)zc : 1e10) * nd;
-    *dst = sample_weight(sg, dist, T);
-    zc = zn, sg = sn, dst = dn;
-  }
+  merged_walk(z1, raw1 + (int64_t)r * S1 * 4 + 3, S1, z2 + (int64_t)r * S2, raw2 + (int64_t)r * S2 * 4 + 3, S2, nd,
+              [&](bool a, int i, float, double w) { (a ? wa : wb)[i] = w; });
 }
 
 // raw1 / raw2: the heads' rgb; w1 / w2, z2, target [rays][3] and rw [rays] start at the chunk's first ray, terms and rgb likewise
@@ -596,60 +639,42 @@ int sum_rows(double *buf, int64_t n, int width, hipStream_t stream, const double
   return NRPN_OK;
 }
 
-struct CamoptLayout {     // of the work buffer, in bytes; every part 16-byte aligned.  prepare uses raw1 .. gbuf only
-  int64_t raw1, raw2, gbuf, prepare_total, mask1, mask2, dl, partial, chunk_a, terms, total;
+struct CamoptLayout : PassLayout {      // of the work buffer, in bytes; every part 16-byte aligned.  prepare uses the passes' part only
+  int64_t mask1, mask2, dl, partial, chunk_a, terms, total;
   int64_t tiles1, tiles2, slot_floats;      // g tiles of a full chunk per pass; floats of a chunk's slot in the g cache
 };
 CamoptLayout camopt_layout(int64_t num_rays, int64_t chunk, int s1, int s2) {
-  auto al = [](int64_t b) { return (b + 15) / 16 * 16; };
-  CamoptLayout l{};
-  const int smax = s1 > s2 ? s1 : s2;
+  CamoptLayout l{pass_layout(0, chunk, s1, s2, false)};
   l.tiles1 = cdiv64(chunk * s1, kTile);
   l.tiles2 = cdiv64(chunk * s2, kTile);
   l.slot_floats = (l.tiles1 + l.tiles2) * kTile * kHalf;
-  l.raw1 = 0;
-  l.raw2 = l.raw1 + al(chunk * s1 * 16);
-  l.gbuf = l.raw2 + al(chunk * s2 * 16);
-  l.prepare_total = l.gbuf + cdiv64(chunk * smax, kTile) * kTile * kHalf * 4;
-  l.mask1 = l.prepare_total;
-  l.mask2 = l.mask1 + al(chunk * s1 * 16);
-  l.dl = l.mask2 + al(chunk * s2 * 16);
-  l.partial = l.dl + al(chunk * 3 * 8);
+  l.mask1 = l.end;
+  l.mask2 = l.mask1 + align16(chunk * s1 * 16);
+  l.dl = l.mask2 + align16(chunk * s2 * 16);
+  l.partial = l.dl + align16(chunk * 3 * 8);
   const int64_t tiles = l.tiles1 + l.tiles2, chunks = cdiv64(num_rays, chunk);
   l.chunk_a = l.partial + (tiles + sum_rows_extra(tiles)) * kAcols * 8;
   l.terms = l.chunk_a + (chunks + sum_rows_extra(chunks)) * kAcols * 8;
-  l.total = l.terms + al((num_rays + sum_rows_extra(num_rays)) * 8);
+  l.total = l.terms + align16((num_rays + sum_rows_extra(num_rays)) * 8);
   return l;
 }
 
-bool camopt_sizes_ok(int64_t num_rays, int64_t chunk, int s1, int s2) {
-  if (num_rays < 1 || num_rays >= ((int64_t)1 << 31) || chunk < 1 || s1 < 1 || s2 < 0 || s1 > 65536 || s2 > 65536) return false;
-  return (chunk < num_rays ? chunk : num_rays) * (s1 > s2 ? s1 : s2) < ((int64_t)1 << 31) - kTile;
-}
-
-struct CamoptCall {
+struct CamoptCall : RayCall {
   const float *rays;        // [num_rays][6]
-  int64_t num_rays;
-  float cx, cy, cz, scale;
-  int multires;
-  const float *packed, *z1;
-  int s1;
   const float *z2;          // [num_rays][s2]
-  int s2;
-  int64_t chunk;
   float *gcache;
   int64_t cached_chunks;
-  void *work;
-  int64_t work_bytes;
-  hipStream_t stream;
+  // where the trunk's g of chunk ci, pass 0 / 1, lives: its slot of the cache, or the scratch every other chunk shares
+  float *g_of(const CamoptLayout &lay, int64_t ci, int pass) const {
+    if (ci >= cached_chunks) return reinterpret_cast<float *>(static_cast<char *>(work) + lay.gbuf);
+    return gcache + ci * lay.slot_floats + (pass ? lay.tiles1 * kTile * kHalf : 0);
+  }
 };
 
-int camopt_check(const CamoptCall &c, const char *who) {
-  NRPN_REQUIRE(c.rays && c.packed && c.z1 && c.work, "%s: null pointer", who);
-  NRPN_REQUIRE(c.multires >= 0 && 3 + 6 * c.multires <= kEnc, "%s: multires %d does not fit %d encoding columns", who, c.multires, kEnc);
-  NRPN_REQUIRE(camopt_sizes_ok(c.num_rays, c.chunk, c.s1, c.s2), "%s: %lld rays in chunks of %lld with %d + %d samples", who,
-               (long long)c.num_rays, (long long)c.chunk, c.s1, c.s2);
-  NRPN_REQUIRE(c.s2 == 0 || c.z2, "%s: %d second-pass samples without z2", who, c.s2);
+int camopt_check(const CamoptCall &c, const char *who, int multires_views, int cam_ch) {
+  if (int rc = check_call(who, c, kMaxCamoptRays)) return rc;
+  if (int rc = check_model(who, c.multires, multires_views, cam_ch)) return rc;
+  NRPN_REQUIRE(c.rays && (c.s2 == 0 || c.z2), "%s: null rays, or %d second-pass samples without z2", who, c.s2);
   NRPN_REQUIRE(c.cached_chunks >= 0 && (c.cached_chunks == 0 || c.gcache), "%s: %lld cached chunks without a cache", who,
                (long long)c.cached_chunks);
   return NRPN_OK;
@@ -657,42 +682,27 @@ int camopt_check(const CamoptCall &c, const char *who) {
 
 int camopt_prepare(const CamoptCall &c, const float *camera, int W, float near, float far, bool draw_z2, float *rays_out, float *z2_out,
                    double *w1, double *w2) {
-  if (int rc = camopt_check(c, "nerfcamopt_prepare")) return rc;
-  NRPN_REQUIRE(w1 && (c.s2 == 0 || w2), "nerfcamopt_prepare: null output");
-  NRPN_REQUIRE(!draw_z2 || (c.s2 == c.s1 && c.s1 >= 3 && z2_out), "nerfcamopt_prepare: depth-guided sampling draws as many samples as pass 1 has, >= 3");
-  const int64_t chunk = c.chunk < c.num_rays ? c.chunk : c.num_rays;
-  const CamoptLayout lay = camopt_layout(c.num_rays, chunk, c.s1, c.s2);
-  NRPN_REQUIRE(c.work_bytes >= lay.prepare_total, "nerfcamopt_prepare: work buffer of %lld bytes is too small", (long long)c.work_bytes);
-  NRPN_LDS(nerfrender_trunk_kernel, kLdsBytes);
+  if (int rc = camopt_check(c, "nerfcamopt_prepare", 0, 0)) return rc;
+  NRPN_REQUIRE(w1 && (c.s2 == 0 || w2) && (!draw_z2 || z2_out), "nerfcamopt_prepare: null output");
+  const CamoptLayout lay = camopt_layout(c.num_rays, c.chunk_rays(), c.s1, c.s2);
+  if (int rc = check_work("nerfcamopt_prepare", c, lay.end)) return rc;
   char *wk = static_cast<char *>(c.work);
   float *raw1 = reinterpret_cast<float *>(wk + lay.raw1), *raw2 = reinterpret_cast<float *>(wk + lay.raw2);
-  int64_t ci = 0;
-  for (int64_t r0 = 0; r0 < c.num_rays; r0 += chunk, ++ci) {
-    const int n = (int)(c.num_rays - r0 < chunk ? c.num_rays - r0 : chunk);
-    const int blocks = (n + 63) / 64;
-    const float *rays = c.rays + r0 * 6;
+  for (int64_t ci = 0; ci < c.chunks(); ++ci) {
+    const Chunk k = chunk_at(c, ci, c.rays, true, c.z2, true);
     if (camera) {
-      nerfrender_rays_kernel<<<blocks, 64, 0, c.stream>>>(camera, W, r0, n, rays_out + r0 * 6);
+      nerfrender_rays_kernel<<<k.blocks, 64, 0, c.stream>>>(camera, W, k.r0, k.n, rays_out + k.r0 * 6);
       NRPN_LAUNCH_CHECK("nerfrender_rays_kernel");
     }
-    float *scratch = reinterpret_cast<float *>(wk + lay.gbuf);
-    float *g1 = ci < c.cached_chunks ? c.gcache + ci * lay.slot_floats : scratch;
-    float *g2 = ci < c.cached_chunks ? g1 + lay.tiles1 * kTile * kHalf : scratch;
-    RayPoints rp{rays, c.z1, 0, c.s1, (int64_t)n * c.s1, c.cx, c.cy, c.cz, c.scale};
-    nerfrender_trunk_kernel<<<(int)cdiv64(rp.num_points, kTile), 256, kLdsBytes, c.stream>>>(rp, c.multires, c.packed, g1, raw1);
-    NRPN_LAUNCH_CHECK("nerfrender_trunk_kernel");
-    const float *z2 = c.s2 ? c.z2 + r0 * c.s2 : nullptr;
+    if (int rc = launch_trunk(c, k.rp[0], c.g_of(lay, ci, 0), raw1)) return rc;
     if (draw_z2) {
-      nerfrender_sample_kernel<<<blocks, 64, 0, c.stream>>>(raw1, rays, c.z1, c.s1, near, far, n, z2_out + r0 * c.s2);
+      nerfrender_sample_kernel<<<k.blocks, 64, 0, c.stream>>>(raw1, k.rays, c.z1, c.s1, near, far, k.n, z2_out + k.r0 * c.s2);
       NRPN_LAUNCH_CHECK("nerfrender_sample_kernel");
     }
-    if (z2) {
-      RayPoints rp2{rays, z2, c.s2, c.s2, (int64_t)n * c.s2, c.cx, c.cy, c.cz, c.scale};
-      nerfrender_trunk_kernel<<<(int)cdiv64(rp2.num_points, kTile), 256, kLdsBytes, c.stream>>>(rp2, c.multires, c.packed, g2, raw2);
-      NRPN_LAUNCH_CHECK("nerfrender_trunk_kernel");
-    }
-    nerfcamopt_weights_kernel<<<blocks, 64, 0, c.stream>>>(raw1, c.z1, c.s1, raw2, z2 ? z2 : c.z1, c.s2, rays, n, w1 + r0 * c.s1,
-                                                           c.s2 ? w2 + r0 * c.s2 : w1);
+    if (k.z2)
+      if (int rc = launch_trunk(c, k.rp[1], c.g_of(lay, ci, 1), raw2)) return rc;
+    nerfcamopt_weights_kernel<<<k.blocks, 64, 0, c.stream>>>(raw1, c.z1, c.s1, raw2, k.zb, c.s2, k.rays, k.n, w1 + k.r0 * c.s1,
+                                                             c.s2 ? w2 + k.r0 * c.s2 : w1);
     NRPN_LAUNCH_CHECK("nerfcamopt_weights_kernel");
   }
   return NRPN_OK;
@@ -700,63 +710,42 @@ int camopt_prepare(const CamoptCall &c, const float *camera, int W, float near, 
 
 int camopt_eval(const CamoptCall &c, int multires_views, int cam_ch, const float *w_view, const float *b_view, const float *cam,
                 const double *w1, const double *w2, const float *target, const double *rw, double *out, float *rgb) {
-  if (int rc = camopt_check(c, "nerfcamopt_eval")) return rc;
-  NRPN_REQUIRE(w_view && b_view && cam && w1 && (c.s2 == 0 || w2) && target && rw && out, "nerfcamopt_eval: null pointer");
-  NRPN_REQUIRE(multires_views >= 0 && 3 + 6 * multires_views <= kMaxViewsCh && cam_ch >= 1 && cam_ch <= 65536,
-               "nerfcamopt_eval: multires_views %d / input_ch_cam %d", multires_views, cam_ch);
-  const int64_t chunk = c.chunk < c.num_rays ? c.chunk : c.num_rays;
-  const CamoptLayout lay = camopt_layout(c.num_rays, chunk, c.s1, c.s2);
-  NRPN_REQUIRE(c.work_bytes >= lay.total, "nerfcamopt_eval: work buffer of %lld bytes is too small", (long long)c.work_bytes);
-  NRPN_LDS(nerfrender_trunk_kernel, kLdsBytes);
+  if (int rc = camopt_check(c, "nerfcamopt_eval", multires_views, cam_ch)) return rc;
+  NRPN_REQUIRE(w_view && b_view && cam && cam_ch >= 1 && w1 && (c.s2 == 0 || w2) && target && rw && out,
+               "nerfcamopt_eval: null pointer, or no camera embedding");
+  const CamoptLayout lay = camopt_layout(c.num_rays, c.chunk_rays(), c.s1, c.s2);
+  if (int rc = check_work("nerfcamopt_eval", c, lay.total)) return rc;
   char *wk = static_cast<char *>(c.work);
-  float *raw1 = reinterpret_cast<float *>(wk + lay.raw1), *raw2 = reinterpret_cast<float *>(wk + lay.raw2);
-  float *scratch = reinterpret_cast<float *>(wk + lay.gbuf);
-  uint32_t *mask1 = reinterpret_cast<uint32_t *>(wk + lay.mask1), *mask2 = reinterpret_cast<uint32_t *>(wk + lay.mask2);
+  float *const raws[2] = {reinterpret_cast<float *>(wk + lay.raw1), reinterpret_cast<float *>(wk + lay.raw2)};
+  uint32_t *const masks[2] = {reinterpret_cast<uint32_t *>(wk + lay.mask1), reinterpret_cast<uint32_t *>(wk + lay.mask2)};
   double *dl = reinterpret_cast<double *>(wk + lay.dl), *partial = reinterpret_cast<double *>(wk + lay.partial);
   double *chunk_a = reinterpret_cast<double *>(wk + lay.chunk_a), *terms = reinterpret_cast<double *>(wk + lay.terms);
-  int64_t ci = 0;
-  for (int64_t r0 = 0; r0 < c.num_rays; r0 += chunk, ++ci) {
-    const int n = (int)(c.num_rays - r0 < chunk ? c.num_rays - r0 : chunk);
-    const int blocks = (n + 63) / 64;
-    const float *rays = c.rays + r0 * 6;
-    const bool cached = ci < c.cached_chunks;
-    const float *z2 = c.s2 ? c.z2 + r0 * c.s2 : nullptr;
-    const RayPoints rps[2] = {{rays, c.z1, 0, c.s1, (int64_t)n * c.s1, c.cx, c.cy, c.cz, c.scale},
-                              {rays, z2, c.s2, c.s2, (int64_t)n * c.s2, c.cx, c.cy, c.cz, c.scale}};
-    float *const raws[2] = {raw1, raw2};
-    uint32_t *const masks[2] = {mask1, mask2};
-    int tiles[2] = {0, 0};
+  for (int64_t ci = 0; ci < c.chunks(); ++ci) {
+    const Chunk k = chunk_at(c, ci, c.rays, true, c.z2, true);
+    const double *const ws[2] = {w1 + k.r0 * c.s1, c.s2 ? w2 + k.r0 * c.s2 : w1};
     for (int pass = 0; pass < (c.s2 ? 2 : 1); ++pass) {
-      const RayPoints &rp = rps[pass];
-      tiles[pass] = (int)cdiv64(rp.num_points, kTile);
-      const float *g = scratch;
-      if (cached) {
-        g = c.gcache + ci * lay.slot_floats + (pass ? lay.tiles1 * kTile * kHalf : 0);
-      } else {      // the same kernel on the same points as in prepare: the same g
-        nerfrender_trunk_kernel<<<tiles[pass], 256, kLdsBytes, c.stream>>>(rp, c.multires, c.packed, scratch, raws[pass]);
-        NRPN_LAUNCH_CHECK("nerfrender_trunk_kernel");
-      }
-      nerfcamopt_head_kernel<<<tiles[pass], kTile, 0, c.stream>>>(rp, c.packed, w_view, b_view, cam, multires_views, cam_ch, g,
-                                                                  raws[pass], masks[pass]);
+      float *g = c.g_of(lay, ci, pass);
+      if (ci >= c.cached_chunks)        // the same kernel on the same points as in prepare: the same g
+        if (int rc = launch_trunk(c, k.rp[pass], g, raws[pass])) return rc;
+      nerfcamopt_head_kernel<<<k.tiles[pass], kTile, 0, c.stream>>>(k.rp[pass], c.packed, w_view, b_view, cam, multires_views, cam_ch, g,
+                                                                    raws[pass], masks[pass]);
       NRPN_LAUNCH_CHECK("nerfcamopt_head_kernel");
     }
-    const double *wc1 = w1 + r0 * c.s1, *wc2 = c.s2 ? w2 + r0 * c.s2 : w1;
-    nerfcamopt_colour_kernel<<<blocks, 64, 0, c.stream>>>(raw1, c.z1, c.s1, raw2, z2 ? z2 : c.z1, c.s2, wc1, wc2, target + r0 * 3,
-                                                          rw + r0, n, dl, terms + r0, rgb ? rgb + r0 * 3 : nullptr);
+    nerfcamopt_colour_kernel<<<k.blocks, 64, 0, c.stream>>>(raws[0], c.z1, c.s1, raws[1], k.zb, c.s2, ws[0], ws[1], target + k.r0 * 3,
+                                                            rw + k.r0, k.n, dl, terms + k.r0, rgb ? rgb + k.r0 * 3 : nullptr);
     NRPN_LAUNCH_CHECK("nerfcamopt_colour_kernel");
-    nerfcamopt_backward_kernel<<<tiles[0], kHalf, 0, c.stream>>>(raw1, mask1, wc1, dl, c.s1, rps[0].num_points, partial);
-    NRPN_LAUNCH_CHECK("nerfcamopt_backward_kernel");
-    if (c.s2) {
-      nerfcamopt_backward_kernel<<<tiles[1], kHalf, 0, c.stream>>>(raw2, mask2, wc2, dl, c.s2, rps[1].num_points,
-                                                                   partial + (int64_t)tiles[0] * kAcols);
+    for (int pass = 0; pass < (c.s2 ? 2 : 1); ++pass) {
+      nerfcamopt_backward_kernel<<<k.tiles[pass], kHalf, 0, c.stream>>>(raws[pass], masks[pass], ws[pass], dl, k.rp[pass].S,
+                                                                        k.rp[pass].num_points,
+                                                                        partial + (int64_t)(pass ? k.tiles[0] : 0) * kAcols);
       NRPN_LAUNCH_CHECK("nerfcamopt_backward_kernel");
     }
     const double *a;
-    if (int rc = sum_rows(partial, tiles[0] + tiles[1], kAcols, c.stream, &a)) return rc;
+    if (int rc = sum_rows(partial, k.tiles[0] + k.tiles[1], kAcols, c.stream, &a)) return rc;
     NRPN_HIP(hipMemcpyAsync(chunk_a + ci * kAcols, a, kAcols * sizeof(double), hipMemcpyDeviceToDevice, c.stream));
   }
   const double *a, *loss;
-  if (int rc = sum_rows(chunk_a, ci, kAcols, c.stream, &a)) return rc;
+  if (int rc = sum_rows(chunk_a, c.chunks(), kAcols, c.stream, &a)) return rc;
   if (int rc = sum_rows(terms, c.num_rays, 1, c.stream, &loss)) return rc;
   nerfcamopt_finish_kernel<<<1, kHalf, 0, c.stream>>>(a, loss, c.packed, w_view, 3 + 6 * multires_views, cam_ch, out);
   NRPN_LAUNCH_CHECK("nerfcamopt_finish_kernel");
@@ -768,9 +757,8 @@ int camopt_eval(const CamoptCall &c, int multires_views, int cam_ch, const float
 extern "C" {
 
 int64_t nrpn_nerfrender_work_bytes(int64_t chunk_rays, int s1, int s2) {
-  if (chunk_rays < 1 || s1 < 1 || s2 < 0 || s1 > 65536 || s2 > 65536) return -1;
-  if (chunk_rays * (s1 > s2 ? s1 : s2) >= ((int64_t)1 << 31) - kTile) return -1;
-  return work_layout(chunk_rays, s1, s2).total;
+  if (!sizes_ok(chunk_rays, kMaxRenderRays, chunk_rays, s1, s2)) return -1;
+  return render_layout(chunk_rays, s1, s2).end;
 }
 
 int nrpn_nerfrender_samples(const float *raw, const float *rays, const float *z, int num_samples, float near, float far,
@@ -789,9 +777,9 @@ int nrpn_nerfrender_rays(const float *rays, int64_t num_rays, float near, float 
                          int64_t chunk, void *work, int64_t work_bytes, float *rgb, float *depth, float *acc, float *disp,
                          float *depth_std, float *z_vals, float *weights, float *raw1_out, float *z2_out, nrpn_stream_t stream) {
   NRPN_REQUIRE(rays, "nerfrender_rays: null rays");
-  RenderCall c{rays, nullptr, 0, num_rays, near, far, center_x, center_y, center_z, bb_scale, multires, multires_views, input_ch_cam,
-               packed, w_view, b_view, embedded_cam, z1, s1, z2_mode, z2_in, s2, chunk, work, work_bytes,
-               CompositeOut{rgb, depth, acc, disp, depth_std, z_vals, weights}, raw1_out, z2_out, as_stream(stream)};
+  RenderCall c{{num_rays, center_x, center_y, center_z, bb_scale, multires, packed, z1, s1, s2, chunk, work, work_bytes, as_stream(stream)},
+               rays, nullptr, 0, near, far, multires_views, input_ch_cam, w_view, b_view, embedded_cam, z2_mode, z2_in,
+               CompositeOut{rgb, depth, acc, disp, depth_std, z_vals, weights}, raw1_out, z2_out};
   return render(c);
 }
 
@@ -802,16 +790,17 @@ int nrpn_nerfrender_frame(int height, int width, const float *camera, float near
                           float *disp, float *depth_std, float *z_vals, float *weights, float *raw1_out, float *z2_out,
                           nrpn_stream_t stream) {
   NRPN_REQUIRE(camera && height >= 1 && width >= 1, "nerfrender_frame: camera / %d x %d", height, width);
-  RenderCall c{nullptr, camera, width, (int64_t)height * width, near, far, center_x, center_y, center_z, bb_scale, multires,
-               multires_views, input_ch_cam, packed, w_view, b_view, embedded_cam, z1, s1, z2_mode, z2_in, s2, chunk, work, work_bytes,
-               CompositeOut{rgb, depth, acc, disp, depth_std, z_vals, weights}, raw1_out, z2_out, as_stream(stream)};
+  RenderCall c{{(int64_t)height * width, center_x, center_y, center_z, bb_scale, multires, packed, z1, s1, s2, chunk, work, work_bytes,
+                as_stream(stream)},
+               nullptr, camera, width, near, far, multires_views, input_ch_cam, w_view, b_view, embedded_cam, z2_mode, z2_in,
+               CompositeOut{rgb, depth, acc, disp, depth_std, z_vals, weights}, raw1_out, z2_out};
   return render(c);
 }
 
 int64_t nrpn_nerfcamopt_work_bytes(int what, int64_t num_rays, int64_t chunk_rays, int s1, int s2) {
-  if (what < 0 || what > 2 || !camopt_sizes_ok(num_rays, chunk_rays, s1, s2)) return -1;
+  if (what < 0 || what > 2 || !sizes_ok(num_rays, kMaxCamoptRays, chunk_rays, s1, s2)) return -1;
   const CamoptLayout l = camopt_layout(num_rays, chunk_rays < num_rays ? chunk_rays : num_rays, s1, s2);
-  return what == 0 ? l.prepare_total : what == 1 ? l.total : l.slot_floats * 4;
+  return what == 0 ? l.end : what == 1 ? l.total : l.slot_floats * 4;
 }
 
 int nrpn_nerfcamopt_prepare(const float *rays, int height, int width, const float *camera, int64_t num_rays, float near, float far,
@@ -822,11 +811,9 @@ int nrpn_nerfcamopt_prepare(const float *rays, int height, int width, const floa
   NRPN_REQUIRE((rays != nullptr) != (camera != nullptr), "nerfcamopt_prepare: give rays or a camera");
   NRPN_REQUIRE(!camera || (rays_out && height >= 1 && width >= 1 && (int64_t)height * width == num_rays),
                "nerfcamopt_prepare: camera / %d x %d for %lld rays", height, width, (long long)num_rays);
-  NRPN_REQUIRE(z2_mode >= 0 && z2_mode <= 2 && (z2_mode == 0) == (s2 == 0), "nerfcamopt_prepare: z2 mode %d with %d second-pass samples",
-               z2_mode, s2);
-  NRPN_REQUIRE(z2_mode != 2 || z2_in, "nerfcamopt_prepare: z2 mode 2 without z2");
-  CamoptCall c{camera ? rays_out : rays, num_rays, center_x, center_y, center_z, bb_scale, multires, packed, z1, s1,
-               z2_mode == 1 ? z2_out : z2_in, s2, chunk, g_cache, cached_chunks, work, work_bytes, as_stream(stream)};
+  if (int rc = check_samples("nerfcamopt_prepare", z2_mode, s1, s2, z2_in)) return rc;
+  CamoptCall c{{num_rays, center_x, center_y, center_z, bb_scale, multires, packed, z1, s1, s2, chunk, work, work_bytes, as_stream(stream)},
+               camera ? rays_out : rays, z2_mode == 1 ? z2_out : z2_in, g_cache, cached_chunks};
   return camopt_prepare(c, camera, width, near, far, z2_mode == 1, rays_out, z2_out, w1, w2);
 }
 
@@ -836,8 +823,8 @@ int nrpn_nerfcamopt_eval(const float *rays, int64_t num_rays, float center_x, fl
                          const double *w1, const double *w2, const float *target, const double *ray_weight, int64_t chunk,
                          const float *g_cache, int64_t cached_chunks, void *work, int64_t work_bytes, double *loss_grad, float *rgb,
                          nrpn_stream_t stream) {
-  CamoptCall c{rays, num_rays, center_x, center_y, center_z, bb_scale, multires, packed, z1, s1, z2, s2, chunk,
-               const_cast<float *>(g_cache), cached_chunks, work, work_bytes, as_stream(stream)};
+  CamoptCall c{{num_rays, center_x, center_y, center_z, bb_scale, multires, packed, z1, s1, s2, chunk, work, work_bytes, as_stream(stream)},
+               rays, z2, const_cast<float *>(g_cache), cached_chunks};
   return camopt_eval(c, multires_views, input_ch_cam, w_view, b_view, embedded_cam, w1, w2, target, ray_weight, loss_grad, rgb);
 }
 

@@ -2575,6 +2575,20 @@ def nerf_grid_pack(state_dict, cfg):
     return NerfGridWeights(packed, wv[:, W:W + views_ch].contiguous(), t["views_linears.0.bias"], c, wv[:, W:].contiguous())
 
 
+def _nerf_weights(who, weights_or_state, cfg):
+    """The NerfGridWeights given, or those of a given network_fn_state_dict; either way they must fit cfg -> NerfGridWeights."""
+    weights = weights_or_state if isinstance(weights_or_state, NerfGridWeights) else nerf_grid_pack(weights_or_state, cfg)
+    if weights.config != nerf_grid_config(cfg):
+        raise lib.NrpnError(f"{who}: the weights were packed for other options")
+    return weights
+
+
+def _nerf_bounds(bb_center, bb_scale):
+    """The scene normalisation as the kernels take it: the float32 values of bb_center [3] and bb_scale -> (cx, cy, cz, scale)."""
+    center, scale = (torch.as_tensor(x, dtype=torch.float32) for x in (bb_center, bb_scale))
+    return (*center.reshape(3).tolist(), scale.reshape(()).item())
+
+
 def nerf_grid_query(state_dict, cfg, xs, ys, zs, bb_center, bb_scale, poses, layout="flat", chunk=None):
     """extract_nerf of the reference's run_nerf.py (:1157-1194) for the NeRF MLP of DESIGN.md 3.16.
 
@@ -2588,10 +2602,8 @@ def nerf_grid_query(state_dict, cfg, xs, ys, zs, bb_center, bb_scale, poses, lay
     and never changes the result."""
     if layout not in _NERF_LAYOUTS:
         raise ValueError(f"layout {layout!r}: expected 'flat' or 'wlh'")
-    weights = state_dict if isinstance(state_dict, NerfGridWeights) else nerf_grid_pack(state_dict, cfg)
+    weights = _nerf_weights("nerf_grid_query", state_dict, cfg)
     c, packed, dev = weights.config, weights.packed, weights.packed.device
-    if c != nerf_grid_config(cfg):
-        raise lib.NrpnError("nerf_grid_query: the weights were packed for other options")
     # c_p = W_d embed_dirs(d_p) + b: the camera embedding is zero at extraction (run_nerf.py:1177), its columns drop out
     poses = torch.as_tensor(poses, dtype=torch.float32).to(dev)
     if poses.dim() != 3 or poses.shape[0] < 1 or poses.shape[1] < 3 or poses.shape[2] < 3:
@@ -2613,10 +2625,8 @@ def nerf_grid_query(state_dict, cfg, xs, ys, zs, bb_center, bb_scale, poses, lay
     nbytes = lib.query("nerfgrid_work_bytes", 1, min(chunk, n))
     work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     out = torch.empty((n, 4) if layout == "flat" else (rx, ry, rz, 4), dtype=torch.float32, device=dev)
-    cx, cy, cz = (float(v) for v in torch.as_tensor(bb_center, dtype=torch.float32).reshape(3).tolist())
-    scale = float(torch.as_tensor(bb_scale, dtype=torch.float32).reshape(()).item())
-    call("nerfgrid_query", _p(axes[0]), _p(axes[1]), _p(axes[2]), rx, ry, rz, cx, cy, cz, scale, c["multires"], _p(packed), _p(ctab),
-         int(ctab.shape[0]), _NERF_LAYOUTS[layout], chunk, _p(work), nbytes, _p(out), _s())
+    call("nerfgrid_query", _p(axes[0]), _p(axes[1]), _p(axes[2]), rx, ry, rz, *_nerf_bounds(bb_center, bb_scale), c["multires"], _p(packed),
+         _p(ctab), int(ctab.shape[0]), _NERF_LAYOUTS[layout], chunk, _p(work), nbytes, _p(out), _s())
     return out
 
 
@@ -2627,12 +2637,10 @@ NERF_RENDER_DEFAULT_CHUNK = 4096       # rays per launch group: 256 MiB of g scr
 
 
 def _nerf_render_inputs(who, weights_or_state, cfg, H, W, intrinsic, c2w, rays, near, far, bb_center, bb_scale, z_samples, n_samples,
-                        lindisp, embedded_cam, z2):
+                        lindisp, embedded_cam, z2, chunk):
     """The arguments nerf_render and nerf_camopt_prepare share, checked and on the device -> namespace."""
-    weights = weights_or_state if isinstance(weights_or_state, NerfGridWeights) else nerf_grid_pack(weights_or_state, cfg)
+    weights = _nerf_weights(who, weights_or_state, cfg)
     c, packed, dev = weights.config, weights.packed, weights.packed.device
-    if c != nerf_grid_config(cfg):
-        raise lib.NrpnError(f"{who}: the weights were packed for other options")
 
     def f32(x, shape=None):
         x = torch.as_tensor(x, dtype=torch.float32).to(dev)
@@ -2683,11 +2691,13 @@ def _nerf_render_inputs(who, weights_or_state, cfg, H, W, intrinsic, c2w, rays, 
         z2_t = f32(z2)
         if tuple(z2_t.shape) != (n, s2) or s2 < 1:
             raise lib.NrpnError(f"{who} expects z2 [{n}, S2], got {tuple(z2_t.shape)}")
-    cx, cy, cz = (float(v) for v in torch.as_tensor(bb_center, dtype=torch.float32).reshape(3).tolist())
-    scale = float(torch.as_tensor(bb_scale, dtype=torch.float32).reshape(()).item())
+    chunk = NERF_RENDER_DEFAULT_CHUNK if chunk is None else int(chunk)
+    if chunk < 1:
+        raise lib.NrpnError(f"{who}: chunk {chunk}")
+    *center, scale = _nerf_bounds(bb_center, bb_scale)
     return SimpleNamespace(weights=weights, c=c, packed=packed, dev=dev, cam_ch=cam_ch, cam=cam, near=near, far=far, z1=z1, s1=s1, mode=mode,
                            s2=s2, rays_t=rays_t if rays is not None else None, camera=camera if rays is None else None, lead=lead, n=n,
-                           z2_t=z2_t, center=(cx, cy, cz), scale=scale, f32=f32)
+                           z2_t=z2_t, center=center, scale=scale, chunk=chunk, f32=f32)
 
 
 def nerf_render(weights_or_state, cfg, H=None, W=None, intrinsic=None, c2w=None, rays=None, near=None, far=None, bb_center=(0., 0., 0.),
@@ -2710,40 +2720,34 @@ def nerf_render(weights_or_state, cfg, H=None, W=None, intrinsic=None, c2w=None,
     return_samples adds z_vals and weights [.., S].  z2 [R, S2]: run the second pass on these samples instead of drawing them;
     return_stages adds raw1 [R, S1, 4] (the first pass's rgb before the sigmoid and sigma) and z2 (the drawn samples)."""
     a = _nerf_render_inputs("nerf_render", weights_or_state, cfg, H, W, intrinsic, c2w, rays, near, far, bb_center, bb_scale, z_samples,
-                            n_samples, lindisp, embedded_cam, z2)
-    weights, c, packed, dev, cam_ch, cam, near, far = a.weights, a.c, a.packed, a.dev, a.cam_ch, a.cam, a.near, a.far
-    z1, s1, mode, s2, rays_t, camera, lead, n, z2_t = a.z1, a.s1, a.mode, a.s2, a.rays_t, a.camera, a.lead, a.n, a.z2_t
-    chunk = NERF_RENDER_DEFAULT_CHUNK if chunk is None else int(chunk)
-    if chunk < 1:
-        raise lib.NrpnError(f"nerf_render: chunk {chunk}")
-    nbytes = lib.query("nerfrender_work_bytes", min(chunk, n), s1, s2)
+                            n_samples, lindisp, embedded_cam, z2, chunk)
+    c, n, s1, s2 = a.c, a.n, a.s1, a.s2
+    nbytes = lib.query("nerfrender_work_bytes", min(a.chunk, n), s1, s2)
     if nbytes < 0:
-        raise lib.NrpnError(f"nerf_render: chunk {chunk} with {s1} + {s2} samples is outside the supported range")
-    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        raise lib.NrpnError(f"nerf_render: chunk {a.chunk} with {s1} + {s2} samples is outside the supported range")
+    work = torch.empty(nbytes, dtype=torch.uint8, device=a.dev)
 
     def new(*shape):
-        return torch.empty(shape, dtype=torch.float32, device=dev)
+        return torch.empty(shape, dtype=torch.float32, device=a.dev)
     out = {"rgb_map": new(n, 3), "depth_map": new(n), "acc_map": new(n), "disp_map": new(n), "depth_std": new(n)}
     if return_samples:
         out["z_vals"], out["weights"] = new(n, s1 + s2), new(n, s1 + s2)
     if return_stages:
         out["raw1"] = new(n, s1, 4)
-        if mode == 1:
+        if a.mode == 1:
             out["z2"] = new(n, s2)
 
     def opt(k):
         return _p(out[k]) if k in out else None
-    cx, cy, cz = (float(v) for v in torch.as_tensor(bb_center, dtype=torch.float32).reshape(3).tolist())
-    scale = float(torch.as_tensor(bb_scale, dtype=torch.float32).reshape(()).item())
-    common = (near, far, cx, cy, cz, scale, c["multires"], c["multires_views"], cam_ch, _p(packed), _p(weights.w_view),
-              _p(weights.b_views), _p(cam) if cam_ch else None, _p(z1), s1, mode, _p(z2_t) if z2_t is not None else None, s2, chunk,
-              _p(work), nbytes, _p(out["rgb_map"]), _p(out["depth_map"]), _p(out["acc_map"]), _p(out["disp_map"]), _p(out["depth_std"]),
-              opt("z_vals"), opt("weights"), opt("raw1"), opt("z2"), _s())
-    if rays is not None:
-        call("nerfrender_rays", _p(rays_t), n, *common)
+    common = (a.near, a.far, *a.center, a.scale, c["multires"], c["multires_views"], a.cam_ch, _p(a.packed), _p(a.weights.w_view),
+              _p(a.weights.b_views), _p(a.cam) if a.cam_ch else None, _p(a.z1), s1, a.mode, _p(a.z2_t) if a.z2_t is not None else None,
+              s2, a.chunk, _p(work), nbytes, _p(out["rgb_map"]), _p(out["depth_map"]), _p(out["acc_map"]), _p(out["disp_map"]),
+              _p(out["depth_std"]), opt("z_vals"), opt("weights"), opt("raw1"), opt("z2"), _s())
+    if a.rays_t is not None:
+        call("nerfrender_rays", _p(a.rays_t), n, *common)
     else:
-        call("nerfrender_frame", lead[0], lead[1], _p(camera), *common)
-    return {k: (v if k in ("raw1", "z2") else v.reshape(*lead, *v.shape[1:])) for k, v in out.items()}
+        call("nerfrender_frame", a.lead[0], a.lead[1], _p(a.camera), *common)
+    return {k: (v if k in ("raw1", "z2") else v.reshape(*a.lead, *v.shape[1:])) for k, v in out.items()}
 
 
 def nerf_render_samples(raw, rays, z_samples, near, far):
@@ -2785,10 +2789,10 @@ def nerf_camopt_prepare(weights_or_state, cfg, target, H=None, W=None, intrinsic
     device memory, torch's unused reserve included) decides how many chunks also keep the trunk's output g, 512 bytes per sample -- the others re-run the trunk at
     every evaluation, to the same bits.  ``chunk`` fixes the chunks (default 4096 rays).  -> NerfCamoptState"""
     a = _nerf_render_inputs("nerf_camopt_prepare", weights_or_state, cfg, H, W, intrinsic, c2w, rays, near, far, bb_center, bb_scale,
-                            z_samples, n_samples, lindisp, None, z2)
+                            z_samples, n_samples, lindisp, None, z2, chunk)
     if a.cam_ch < 1:
         raise lib.NrpnError("nerf_camopt_prepare: the model has no camera embedding (input_ch_cam is 0)")
-    dev, n, s1, s2 = a.dev, a.n, a.s1, a.s2
+    dev, n, s1, s2, chunk = a.dev, a.n, a.s1, a.s2, a.chunk
     target = a.f32(target, (-1, 3))
     if target.shape[0] != n:
         raise lib.NrpnError(f"nerf_camopt_prepare: target has {target.shape[0]} pixels, there are {n} rays")
@@ -2798,9 +2802,6 @@ def nerf_camopt_prepare(weights_or_state, cfg, target, H=None, W=None, intrinsic
         rw = torch.as_tensor(ray_weight, dtype=torch.float64).to(dev).reshape(-1).contiguous()
         if rw.numel() != n:
             raise lib.NrpnError(f"nerf_camopt_prepare: ray_weight has {rw.numel()} values, there are {n} rays")
-    chunk = NERF_RENDER_DEFAULT_CHUNK if chunk is None else int(chunk)
-    if chunk < 1:
-        raise lib.NrpnError(f"nerf_camopt_prepare: chunk {chunk}")
     sizes = [lib.query("nerfcamopt_work_bytes", what, n, chunk, s1, s2) for what in range(3)]
     if min(sizes) < 0:
         raise lib.NrpnError(f"nerf_camopt_prepare: chunk {chunk} with {s1} + {s2} samples is outside the supported range")

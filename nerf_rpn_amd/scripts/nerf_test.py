@@ -91,32 +91,37 @@ def write_images(out_dir, n, rgb8, depth16):
     return jpg, png
 
 
-def main(argv=None):
-    args = build_parser().parse_args(argv)
-    run = NR.prepare(args, tool='nerf_test', transforms_name=TASKS[args.task][0])
+def run_frames(args, run, out_dir, tool='nerf_test', embedding=None):
+    """The frame loop of every task: targets, render, metrics, images, then the means and metrics.txt -> main's result.
+    ``embedding(run, i, image)``, if given, returns the camera embedding frame i is rendered with (None: the zero embedding)."""
     from nerf_rpn_amd import ops
     H, W = run.H, run.W
     scene_dir = os.path.dirname(os.path.abspath(run.transforms))
-    out_dir = result_dir(args)
     os.makedirs(out_dir, exist_ok=True)
     per_frame = []
     for n, i in enumerate(run.frames):
         image, depth, valid = load_targets(scene_dir, run.meta['frames'][i], H, W, run.meta.get('depth_scaling_factor'))
         if depth is None:      # no depth metric for this frame; the rendered depth is still written
             depth, valid = np.zeros((H, W), np.float32), np.zeros((H, W), bool)
-        out = NR.render_frame(run, i, args.chunk)
+        out = NR.render_frame(run, i, args.chunk, embedding(run, i, image) if embedding else None)
         m = ops.nerf_view_metrics(out['rgb_map'], torch.from_numpy(image), out['depth_map'], torch.from_numpy(depth),
                                   torch.from_numpy(valid), far=run.far, return_images=True)
         write_images(out_dir, n, m.pop('rgb8').cpu().numpy(), m.pop('depth16').cpu().numpy())
         per_frame.append(m)
-        print('nerf_test: frame {} ({}/{}): PSNR {}'.format(i, n + 1, len(run.frames), m['psnr']))
+        print('{}: frame {} ({}/{}): PSNR {}'.format(tool, i, n + 1, len(run.frames), m['psnr']))
     means = mean_metrics(per_frame)
     text = format_metrics(means)
     with open(os.path.join(out_dir, 'metrics.txt'), 'w') as f:
         f.write(text)
     print(text, end='')
-    print(f'nerf_test: {len(per_frame)} frames of {H} x {W} in {out_dir}')
+    print(f'{tool}: {len(per_frame)} frames of {H} x {W} in {out_dir}')
     return {'dir': out_dir, 'frames': per_frame, 'mean': means}
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    run = NR.prepare(args, tool='nerf_test', transforms_name=TASKS[args.task][0])
+    return run_frames(args, run, result_dir(args))
 
 
 if __name__ == '__main__':

@@ -58,10 +58,8 @@ def optimize_frame(run, i, image, args):
         raise SystemExit(f'nerf_test_opt: --N_rand {n_rand}, --opt_steps {args.opt_steps}')
     batches = camopt.random_subsets(n, 2 * n_rand, torch.Generator().manual_seed(args.opt_seed))
     cache = None if args.opt_cache_gib is None else int(args.opt_cache_gib * 2 ** 30)
-    state = ops.nerf_camopt_prepare(run.weights, run.cfg, torch.from_numpy(image), H=run.H, W=run.W, intrinsic=run.intrinsics[i],
-                                    c2w=run.poses[i][:3, :4], near=run.near, far=run.far, bb_center=run.bb_center,
-                                    bb_scale=run.bb_scale, z_samples=run.z_samples, n_samples=run.n_samples, lindisp=run.lindisp,
-                                    chunk=args.chunk, ray_weight=camopt.ray_weights(batches, n), cache_bytes=cache)
+    state = ops.nerf_camopt_prepare(run.weights, run.cfg, torch.from_numpy(image), chunk=args.chunk,
+                                    ray_weight=camopt.ray_weights(batches, n), cache_bytes=cache, **NR.frame_kwargs(run, i))
 
     def value_and_grad(cam):
         loss, grad = ops.nerf_camopt_eval(state, cam)
@@ -75,31 +73,13 @@ def main(argv=None):
     from nerf_rpn_amd import ops
     if ops.nerf_grid_config(run.cfg)['input_ch_cam'] == 0:
         raise SystemExit('nerf_test_opt: the model has no camera embedding to optimise (input_ch_cam is 0)')
-    H, W = run.H, run.W
-    scene_dir = os.path.dirname(os.path.abspath(run.transforms))
-    out_dir = result_dir(args)
-    os.makedirs(out_dir, exist_ok=True)
     os.makedirs(latent_code_dir(args), exist_ok=True)
-    per_frame = []
-    for n, i in enumerate(run.frames):
-        image, depth, valid = NT.load_targets(scene_dir, run.meta['frames'][i], H, W, run.meta.get('depth_scaling_factor'))
-        if depth is None:      # no depth metric for this frame; the rendered depth is still written
-            depth, valid = np.zeros((H, W), np.float32), np.zeros((H, W), bool)
+
+    def embedding(run, i, image):
         cam = optimize_frame(run, i, image, args)
         np.savetxt(os.path.join(latent_code_dir(args), f'{i}.txt'), cam.numpy())
-        out = NR.render_frame(run, i, args.chunk, cam)
-        m = ops.nerf_view_metrics(out['rgb_map'], torch.from_numpy(image), out['depth_map'], torch.from_numpy(depth),
-                                  torch.from_numpy(valid), far=run.far, return_images=True)
-        NT.write_images(out_dir, n, m.pop('rgb8').cpu().numpy(), m.pop('depth16').cpu().numpy())
-        per_frame.append(m)
-        print('nerf_test_opt: frame {} ({}/{}): PSNR {}'.format(i, n + 1, len(run.frames), m['psnr']))
-    means = NT.mean_metrics(per_frame)
-    text = NT.format_metrics(means)
-    with open(os.path.join(out_dir, 'metrics.txt'), 'w') as f:
-        f.write(text)
-    print(text, end='')
-    print(f'nerf_test_opt: {len(per_frame)} frames of {H} x {W} in {out_dir}')
-    return {'dir': out_dir, 'frames': per_frame, 'mean': means}
+        return cam
+    return NT.run_frames(args, run, result_dir(args), tool='nerf_test_opt', embedding=embedding)
 
 
 if __name__ == '__main__':

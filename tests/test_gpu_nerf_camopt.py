@@ -82,6 +82,27 @@ def test_rgb_map_is_bit_equal_to_nerf_render(dev, camopt_refs, name):
         assert np.array_equal(rgb, want), (name, cam, float(np.abs(rgb - want).max()))
 
 
+@pytest.mark.parametrize("name", ["odd_5x7", "clamped_4x4", "plain_4x6"])
+def test_weights_kernel_agrees_with_the_composite_kernel(dev, name):
+    """prepare's per-list float64 weights, merged (list 1 first on equal z) and rounded, are nerf_render's weights bit for bit: tiles
+    that straddle rays and a partial last tile, ties between the lists, no second list; chunks of 3 rays end mid-frame."""
+    c = C.case(name)
+    st = ops.nerf_camopt_prepare(c.state, c.cfg, C.target_for(c), chunk=3, **frame_args(c))
+    out = ops.nerf_render(c.state, c.cfg, return_samples=True, chunk=3, **frame_args(c))
+    n = st.n
+    z_vals, weights = (out[k].reshape(n, -1).cpu().numpy() for k in ("z_vals", "weights"))
+    z1, w1 = st.inputs.z1.cpu().numpy(), st.w1.cpu().numpy()
+    assert (st.z2 is None) == (st.w2 is None) == c.plain
+    z2 = np.zeros((n, 0), np.float32) if c.plain else st.z2.cpu().numpy()
+    w2 = np.zeros((n, 0), np.float64) if c.plain else st.w2.cpu().numpy()
+    assert w1.dtype == w2.dtype == np.float64 and weights.dtype == z_vals.dtype == np.float32
+    for r in range(n):
+        z_cat = np.concatenate([z1, z2[r]])
+        order = np.argsort(z_cat, kind="stable")
+        assert np.array_equal(z_vals[r], z_cat[order]), (name, r)
+        assert np.array_equal(weights[r], np.concatenate([w1[r], w2[r]])[order].astype(np.float32)), (name, r)
+
+
 @pytest.mark.parametrize("name", ["full_3x3", "odd_5x7", "plain_4x6"])
 def test_chunk_and_cache_do_not_change_the_result(dev, camopt_refs, name):
     r = camopt_refs(name, "far", "remainder")

@@ -24,24 +24,12 @@ for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
         sys.path.insert(0, p)
 
 import nerf_extract_ref as R  # noqa: E402
-from nerf_render_profile import FRAME, N_SAMPLES, timed  # noqa: E402
+from nerf_profile import kernel_times, timed  # noqa: E402
+from nerf_render_profile import FRAME, N_SAMPLES  # noqa: E402
 
 ATTAINABLE_TBPS = (6.0, 6.3)
 KERNELS = ("nerfcamopt_head_kernel", "nerfcamopt_colour_kernel", "nerfcamopt_backward_kernel", "nerfcamopt_sum_rows_kernel",
            "nerfcamopt_finish_kernel", "nerfrender_trunk_kernel", "Memcpy")
-
-
-def kernel_times(fn):
-    from torch.profiler import ProfilerActivity, profile
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        fn()
-        torch.cuda.synchronize()
-    out = {k: 0.0 for k in KERNELS}
-    for e in prof.key_averages():
-        for k in KERNELS:
-            if k in e.key:
-                out[k] += getattr(e, "device_time_total", getattr(e, "cuda_time_total", 0.0)) / 1e3
-    return out if out["nerfcamopt_head_kernel"] > 0 else None
 
 
 def main():
@@ -74,7 +62,7 @@ def main():
         rec.update(chunk_rays=st.chunk, chunks=st.chunks, cached_chunks=st.cached_chunks, g_bytes=st.g_bytes,
                    prepare_ms=round(t_prepare, 2), eval_cached_ms=round(t_cached, 2), device=torch.cuda.get_device_name(0))
         try:
-            km = kernel_times(lambda: ops.nerf_camopt_eval(st, cam))
+            km = kernel_times(lambda: ops.nerf_camopt_eval(st, cam), KERNELS)
         except Exception as e:      # the profiler is optional: the event times stand without it
             km, rec["note"] = None, f"torch.profiler failed: {type(e).__name__}"
         if km:

@@ -30,6 +30,7 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
         sys.path.insert(0, p)
 
 import nerf_eval_ref as E  # noqa: E402
+from nerf_profile import kernel_times  # noqa: E402
 
 FRAME = (468, 624)
 KERNELS = ("nerfmetrics_tile_kernel", "nerfmetrics_reduce_kernel", "nerfmetrics_to8b_kernel", "nerfmetrics_to16b_kernel")
@@ -46,19 +47,6 @@ def wall_ms(fn, repeats, warmup=5):
         torch.cuda.synchronize()
         times.append((time.perf_counter() - t0) * 1e3)
     return statistics.median(times), min(times)
-
-
-def kernel_times(fn):
-    from torch.profiler import ProfilerActivity, profile
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        fn()
-        torch.cuda.synchronize()
-    out = {k: 0.0 for k in KERNELS}
-    for e in prof.key_averages():
-        for k in KERNELS:
-            if k in e.key:
-                out[k] += getattr(e, "device_time_total", getattr(e, "cuda_time_total", 0.0)) / 1e3
-    return out if out[KERNELS[0]] > 0 else None
 
 
 def measured_errors(ops, lib):
@@ -132,7 +120,7 @@ def main():
         if render_ms:
             rec["metrics_share_of_render"] = round(med_c / render_ms, 5)
         try:
-            km = kernel_times(call)
+            km = kernel_times(call, KERNELS)
         except Exception as e:      # the profiler is optional: the times above stand without it
             km, rec["note"] = None, f"torch.profiler failed: {type(e).__name__}"
         if km:

@@ -23,26 +23,13 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
         sys.path.insert(0, p)
 
 import nerf_extract_ref as R  # noqa: E402
+from nerf_profile import timed  # noqa: E402
 
 RES = (256, 208, 96)
 POSES = 100
 PEAK_TFLOPS = 157.0
 TRUNK_FLOP_PER_POINT = 2 * (57 * 256 + 4 * 256 * 256 + 313 * 256 + 2 * 256 * 256 + 256 * 256 + 256 + 256 * 128)
 HEAD_FLOP_PER_POINT_POSE = 2 * 128 + 2 * 3 * 128
-
-
-def timed(fn, repeats):
-    fn()
-    torch.cuda.synchronize()
-    best = float("inf")
-    for _ in range(repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        best = min(best, a.elapsed_time(b))
-    return best
 
 
 @torch.no_grad()

@@ -21,6 +21,7 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
         sys.path.insert(0, p)
 
 import nerf_extract_ref as R  # noqa: E402
+from nerf_profile import kernel_times, timed  # noqa: E402
 
 FRAME = (468, 624)
 N_SAMPLES = 256
@@ -28,34 +29,6 @@ PEAK_TFLOPS = 157.0
 TRUNK_FLOP_PER_POINT = 2 * (57 * 256 + 4 * 256 * 256 + 313 * 256 + 2 * 256 * 256 + 256 * 256 + 256 + 256 * 128)
 KERNELS = ("nerfrender_trunk_kernel", "nerfrender_head_kernel", "nerfrender_sample_kernel", "nerfrender_composite_kernel",
            "nerfrender_rays_kernel")
-
-
-def timed(fn, repeats):
-    fn()
-    torch.cuda.synchronize()
-    best = float("inf")
-    for _ in range(repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        best = min(best, a.elapsed_time(b))
-    return best
-
-
-def kernel_times(fn):
-    """Device time in ms per kernel family of one call of fn, from torch.profiler; None if the profiler records no kernels."""
-    from torch.profiler import ProfilerActivity, profile
-    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-        fn()
-        torch.cuda.synchronize()
-    out = {k: 0.0 for k in KERNELS}
-    for e in prof.key_averages():
-        for k in KERNELS:
-            if k in e.key:
-                out[k] += getattr(e, "device_time_total", getattr(e, "cuda_time_total", 0.0)) / 1e3
-    return out if out["nerfrender_trunk_kernel"] > 0 else None
 
 
 def main():
@@ -82,7 +55,7 @@ def main():
         rec.update(chunk_rays=ops.NERF_RENDER_DEFAULT_CHUNK, two_pass_frame_ms=round(t_two, 2), plain_frame_ms=round(t_plain, 2),
                    device=torch.cuda.get_device_name(0))
         try:
-            km = kernel_times(lambda: ops.nerf_render(weights, R.DEFAULT_CFG, z_samples=z, **kw))
+            km = kernel_times(lambda: ops.nerf_render(weights, R.DEFAULT_CFG, z_samples=z, **kw), KERNELS)
         except Exception as e:      # the profiler is optional: the event times above stand without it
             km, rec["note"] = None, f"torch.profiler failed: {type(e).__name__}"
         if km:
