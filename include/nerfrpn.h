@@ -830,6 +830,38 @@ int nrpn_nerfcamopt_eval(const float *rays, int64_t num_rays, float center_x, fl
                          const float *g_cache, int64_t cached_chunks, void *work, int64_t work_bytes, double *loss_grad, float *rgb,
                          nrpn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The NeRF MLP query as a differentiable operation, ops.nerf_query.  [f9]  Replaces run_network (data/scannet/run_nerf.py:50-65) as
+ * network_query_fn (:376-379) calls it in training, and what loss.backward() (:848) computes below it, for the model and the packed
+ * weights of nrpn_nerfgrid_pack; DESIGN.md 3.20.  Points are processed chunk points at a time (rounded up to tiles of 64); no atomics.
+ * nrpn_nerfquery_work_bytes(what, num_rays, num_samples, chunk, multires, multires_views, input_ch_cam): what 0: bytes of forward's
+ *   scratch; 1: of backward's; 2: of the packed transposes; 3: floats of the gradient array; 4: backward's scratch bytes per point of
+ *   a chunk.  -1 for sizes outside the supported range.
+ * nrpn_nerfquery_pack_t: raw as for nrpn_nerfgrid_pack -> packed_t, the h columns of pts_linears.1 .. 7, feature_linear and W_f
+ *   transposed, in the B-fragment order of the forward weights.
+ * nrpn_nerfquery_forward (run_network :50-65): pts f32 [num_rays][num_samples][3] world points, normalised as (pts - center) *
+ *   bb_scale (:53); viewdirs f32 [num_rays][3], embedded as given (:57-61); embedded_cam f32 [input_ch_cam] (null if 0); w_view f32
+ *   [128][views_ch + input_ch_cam] and b_view f32 [128] of views_linears.0 -> raw f32 [num_rays][num_samples][4]: rgb before the
+ *   sigmoid, sigma before the relu.  The result does not depend on chunk; sigma is bit-equal to nrpn_nerfrender_rays' raw1 for pts =
+ *   o + d z formed with a separately rounded multiply and add.
+ * nrpn_nerfquery_backward (loss.backward() :848 below raw): draw f32 [num_rays][num_samples][4], the cotangent of raw -> grads f32
+ *   [work_bytes(3, ..)]: the gradients in torch's layouts back to back: pts_linears.0 .. 7 weights, feature_linear.weight,
+ *   alpha_linear.weight, views_linears.0.weight, rgb_linear.weight, then the biases in the same order, then embedded_cam.  The forward
+ *   is re-run per chunk; the sums over a chunk's points run in 64 slices of whole tiles on the MFMA, the slices and the chunks are
+ *   added in order in float64.  For a given chunk repeated calls are bit-equal; across chunk sizes the sums differ in rounding.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t nrpn_nerfquery_work_bytes(int what, int64_t num_rays, int num_samples, int64_t chunk, int multires, int multires_views,
+                                  int input_ch_cam);
+int nrpn_nerfquery_pack_t(const float *raw, int input_ch, float *packed_t, nrpn_stream_t stream);
+int nrpn_nerfquery_forward(const float *pts, const float *viewdirs, int64_t num_rays, int num_samples, float center_x, float center_y,
+                           float center_z, float bb_scale, int multires, int multires_views, int input_ch_cam, const float *packed,
+                           const float *w_view, const float *b_view, const float *embedded_cam, int64_t chunk, void *work,
+                           int64_t work_bytes, float *raw, nrpn_stream_t stream);
+int nrpn_nerfquery_backward(const float *pts, const float *viewdirs, int64_t num_rays, int num_samples, float center_x, float center_y,
+                            float center_z, float bb_scale, int multires, int multires_views, int input_ch_cam, const float *packed,
+                            const float *packed_t, const float *w_view, const float *b_view, const float *embedded_cam,
+                            const float *draw, int64_t chunk, void *work, int64_t work_bytes, float *grads, nrpn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

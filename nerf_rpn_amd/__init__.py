@@ -5,4 +5,11 @@ through the C ABI in ``include/nerfrpn.h`` (``libnerfrpn_hip.so``).  No CPU fall
 """
 from . import lib  # noqa: F401
 
-__all__ = ["lib"]
+__all__ = ["lib", "NeRF"]
+
+
+def __getattr__(name):
+    if name == "NeRF":          # the NeRF MLP module (nerf_model.py); imported on first use, with torch
+        from .nerf_model import NeRF
+        return NeRF
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -87,6 +87,18 @@ __device__ __forceinline__ void gemm_tile(const float *act, int k0, int K, const
   }
 }
 
+// A sink that declares ``static constexpr bool kKeeps = true`` also gets keep(layer, act) once the image holds a layer's output that
+// every wave may read: layer -1 the encoding in columns 0 .. 63, 0 .. 7 the post-relu h_i and 8 the feature f in columns 64 .. 319
+// (nerfquery.hip keeps them for the backward pass).  Every thread of the workgroup calls it; it may only read the image.
+template <class S, class = void>
+struct sink_keeps {
+  static constexpr bool value = false;
+};
+template <class S>
+struct sink_keeps<S, decltype(void(S::kKeeps))> {
+  static constexpr bool value = S::kKeeps;
+};
+
 // row of the 32 x 32 accumulator that register reg of this lane holds
 __device__ __forceinline__ int acc_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 
@@ -118,6 +130,7 @@ __device__ __forceinline__ void trunk_body(float *act, const float *__restrict__
     }
   }
   __syncthreads();
+  if constexpr (sink_keeps<Sink>::value) sink.keep(-1, act);
 
   const float4 *wp = reinterpret_cast<const float4 *>(packed);
   const float *bias = packed + kOffBias;
@@ -165,6 +178,7 @@ __device__ __forceinline__ void trunk_body(float *act, const float *__restrict__
         }
     }
     __syncthreads();
+    if constexpr (sink_keeps<Sink>::value) sink.keep(layer, act);
   }
 
   // g = W_f f: 128 columns, 32 per wave; stored [column][point] so a head reads it coalesced

@@ -1,0 +1,661 @@
+// The NeRF MLP query as a differentiable operation (ops.nerf_query; reference data/scannet/run_nerf.py: run_network :50-65 as
+// network_query_fn, and what loss.backward() of train_nerf :848-849 computes below it).  DESIGN.md 3.20.
+//
+// Forward, per chunk of points:
+//   rays     one workgroup per ray: embed_dirs(viewdir), c_r = W_d embed_dirs + W_c cam + b of views_linears.0
+//   trunk    the shared MFMA trunk (nerf_mlp.cuh) over (pts - centre) * scale -> raw sigma and g = W_f f
+//   head     one thread per point: v = relu(g + c_r), raw rgb = W_rgb v + b_rgb
+// Backward, per chunk of points, for the cotangent draw [points][4] (nothing is kept between forward and backward):
+//   trunk    again, with a sink that keeps the encoding e, h_0 .. h_7 and f of every point of the chunk
+//   headbwd  one thread per point: v and dv = (W_rgb^T draw_rgb) [g + c_r > 0], the head's cotangent rows (draw_rgb, dsigma) and
+//            the point's [embed_dirs | cam] row
+//   dgrad    dX = dY W on the MFMA with W^T packed like the forward weights (nrpn_nerfquery_pack_t), one layer per launch:
+//            df = W_f^T dv; dy_7 = (W_feat^T df + dsigma w_alpha) [h_7 > 0]; dy_{i-1} = (W_i[:, h part]^T dy_i) [h_{i-1} > 0].
+//            Each result replaces, element for element, the activation whose mask it took (df replaces f).
+//   wgrad    dW = dY^T X on the MFMA, the points of the chunk cut into kSlices slices of whole tiles; a wave owns a 64 x 64 block of
+//            dW for one slice and adds its points in order; the bias gradient is the column sum of dY, taken by the same waves
+//   reduce   adds the slices in slice order in float64 into the float64 gradient, chunk after chunk
+// and finish: dcam = W_c^T db_views, everything rounded to float32.  No atomics: for a given chunk size every sum has a fixed order.
+#include "nerf_mlp.cuh"
+
+namespace {
+
+using namespace nerfmlp;
+
+constexpr int kMaxViewsCh = 64;       // 3 + 6 multires_views <= 64
+constexpr int kSlices = 64;           // of a chunk's points in wgrad
+constexpr int kHeadCols = 64;         // the head's cotangent rows: draw_rgb, dsigma, zeros (one 64-column block of wgrad)
+constexpr int kLdT = kHalf + 1;       // bank skew of headbwd's transposing tile
+
+// packed transposes, in floats: 0 .. 6 pts_linears.1 .. 7 (h part), 7 feature_linear, 8 W_f
+constexpr int64_t kSzT = (int64_t)kW * kW;
+constexpr int64_t kOffTf = 8 * kSzT;
+constexpr int64_t kPackedTFloats = kOffTf + (int64_t)kHalf * kW;
+
+int64_t align16(int64_t b) { return (b + 15) / 16 * 16; }
+
+struct Model {
+  int multires, multires_views, cam_ch;
+  int input_ch() const { return 3 + 6 * multires; }
+  int views_ch() const { return 3 + 6 * multires_views; }
+  int ldv() const { return views_ch() + cam_ch; }                          // view and camera columns of views_linears.0
+  int kv() const { return ldv() ? (ldv() + 63) / 64 * 64 : 64; }          // ... padded to 64-column blocks, at least one
+};
+
+// the gradient as one array, in floats: every tensor in torch's layout
+struct GradLayout {
+  int64_t w_pts[kLayers], w_feat, w_alpha, w_views, w_rgb, b_pts[kLayers], b_feat, b_alpha, b_views, b_rgb, cam, total;
+};
+GradLayout grad_layout(const Model &m) {
+  GradLayout g{};
+  int64_t at = 0;
+  for (int i = 0; i < kLayers; ++i) {
+    g.w_pts[i] = at;
+    at += (int64_t)kW * (i == 0 ? m.input_ch() : i == kSkipLayer ? m.input_ch() + kW : kW);
+  }
+  g.w_feat = at, at += kSzT;
+  g.w_alpha = at, at += kW;
+  g.w_views = at, at += (int64_t)kHalf * (kW + m.ldv());
+  g.w_rgb = at, at += 3 * kHalf;
+  for (int i = 0; i < kLayers; ++i) g.b_pts[i] = at, at += kW;
+  g.b_feat = at, at += kW;
+  g.b_alpha = at, at += 1;
+  g.b_views = at, at += kHalf;
+  g.b_rgb = at, at += 3;
+  g.cam = at, at += m.cam_ch;
+  g.total = at;
+  return g;
+}
+
+// ---- rays ------------------------------------------------------------------------------------------------------------------------
+// One workgroup of 128 threads per ray: ctab [ray][128] = b + W_c cam + W_d embed_dirs(viewdir) in the order of nerfrender's head;
+// xv [ray][kv] = [embed_dirs | cam | 0]
+__global__ __launch_bounds__(kHalf) void nerfquery_rays_kernel(const float *__restrict__ viewdirs, const float *__restrict__ w_view,
+                                                               const float *__restrict__ b_view, const float *__restrict__ cam,
+                                                               int multires_views, int cam_ch, int kv, float *__restrict__ ctab,
+                                                               float *__restrict__ xv) {
+  __shared__ float emb[kMaxViewsCh];
+  const int j = threadIdx.x;
+  const int64_t ray = blockIdx.x;
+  const int views_ch = 3 + 6 * multires_views, ldv = views_ch + cam_ch;
+  if (j < 3) {
+    const float d = viewdirs[ray * 3 + j];
+    emb[j] = d;
+    for (int l = 0; l < multires_views; ++l) {
+      const float arg = d * ldexpf(1.0f, l);
+      emb[3 + 6 * l + j] = sinf(arg);
+      emb[3 + 6 * l + 3 + j] = cosf(arg);
+    }
+  }
+  __syncthreads();
+  float c = b_view[j];
+  for (int k = 0; k < cam_ch; ++k) c = fmaf(w_view[j * ldv + views_ch + k], cam[k], c);
+  for (int k = 0; k < views_ch; ++k) c = fmaf(w_view[j * ldv + k], emb[k], c);
+  ctab[ray * kHalf + j] = c;
+  if (xv)
+    for (int k = j; k < kv; k += kHalf) xv[ray * kv + k] = k < views_ch ? emb[k] : k < ldv ? cam[k - views_ch] : 0.f;
+}
+
+// ---- trunk (body: nerf_mlp.cuh) --------------------------------------------------------------------------------------------------
+struct Points {
+  const float *pts;       // [num_points][3], world
+  int64_t num_points;     // of the whole call
+  int S;                  // points per ray
+  float cx, cy, cz, scale;
+};
+
+struct PointSrc {
+  const Points &pp;
+  int64_t tile0;
+  __device__ __forceinline__ void point(int i, float (&p)[3]) const {
+    int64_t pi = tile0 + i;
+    if (pi > pp.num_points - 1) pi = pp.num_points - 1;       // a partial tile repeats the last point; nothing of it is stored
+    const float c[3] = {pp.cx, pp.cy, pp.cz};
+#pragma unroll
+    for (int a = 0; a < 3; ++a) p[a] = __fmul_rn(__fsub_rn(pp.pts[pi * 3 + a], c[a]), pp.scale);
+  }
+};
+
+struct RawSink {          // forward: sigma to raw [point][4]
+  int64_t tile0, num_points;
+  float *raw;
+  __device__ __forceinline__ void sigma(int i, float s) const {
+    const int64_t pi = tile0 + i;
+    if (pi < num_points) raw[pi * 4 + 3] = s;
+  }
+};
+
+// what the backward keeps of a chunk, row = point of the chunk (whole tiles; the rows past the last point hold a repeated point)
+struct Kept {
+  float *enc;             // [rows][64]
+  float *h;               // [8][rows][256]; then dy_i in place
+  float *f;               // [rows][256]; then df in place
+  int64_t rows;
+};
+
+struct KeepSink {
+  static constexpr bool kKeeps = true;
+  Kept k;
+  int64_t row0;           // of the tile in the chunk
+  __device__ __forceinline__ void sigma(int, float) const {}
+  __device__ __forceinline__ void keep(int layer, const float *act) const {
+    const int t = threadIdx.x;
+    if (layer < 0) {
+      for (int idx = t; idx < kTile * (kEnc / 4); idx += 256) {
+        const int row = idx >> 4, c4 = idx & 15;
+        *reinterpret_cast<float4 *>(k.enc + (row0 + row) * kEnc + 4 * c4) = *reinterpret_cast<const float4 *>(act + row * kLd + 4 * c4);
+      }
+      return;
+    }
+    float *dst = layer < kLayers ? k.h + (int64_t)layer * k.rows * kW : k.f;
+    for (int idx = t; idx < kTile * (kW / 4); idx += 256) {
+      const int row = idx >> 6, c4 = idx & 63;
+      *reinterpret_cast<float4 *>(dst + (row0 + row) * kW + 4 * c4) = *reinterpret_cast<const float4 *>(act + row * kLd + kEnc + 4 * c4);
+    }
+  }
+};
+
+__global__ __launch_bounds__(256) void nerfquery_trunk_kernel(Points pp, int multires, const float *__restrict__ packed, int64_t point0,
+                                                              float *__restrict__ gbuf, float *__restrict__ raw) {
+  extern __shared__ __align__(16) float act[];
+  const int64_t tile0 = point0 + (int64_t)blockIdx.x * kTile;
+  trunk_body(act, packed, multires, 3 + 6 * multires, PointSrc{pp, tile0}, RawSink{tile0, pp.num_points, raw},
+             gbuf + (int64_t)blockIdx.x * (kTile * kHalf));
+}
+
+__global__ __launch_bounds__(256) void nerfquery_trunk_keep_kernel(Points pp, int multires, const float *__restrict__ packed,
+                                                                   int64_t point0, float *__restrict__ gbuf, Kept kept) {
+  extern __shared__ __align__(16) float act[];
+  const int64_t tile0 = point0 + (int64_t)blockIdx.x * kTile;
+  trunk_body(act, packed, multires, 3 + 6 * multires, PointSrc{pp, tile0}, KeepSink{kept, (int64_t)blockIdx.x * kTile},
+             gbuf + (int64_t)blockIdx.x * (kTile * kHalf));
+}
+
+// ---- head ------------------------------------------------------------------------------------------------------------------------
+// One workgroup of 64 threads, one tile; rgb_linear over v = relu(g + c_ray) as 128-term fmaf chains in j order
+__global__ __launch_bounds__(kTile) void nerfquery_head_kernel(Points pp, const float *__restrict__ packed, const float *__restrict__ ctab,
+                                                               int64_t point0, const float *__restrict__ gbuf, float *__restrict__ raw) {
+  const int t = threadIdx.x;
+  const int64_t pi = point0 + (int64_t)blockIdx.x * kTile + t;
+  const int64_t pc = pi < pp.num_points ? pi : pp.num_points - 1;
+  const float *c = ctab + (pc / pp.S) * kHalf;
+  const float *gt = gbuf + (int64_t)blockIdx.x * (kTile * kHalf) + t;
+  const float *w = packed + kOffRgbW;
+  float r0 = 0.f, r1 = 0.f, r2 = 0.f;
+#pragma unroll 8
+  for (int j = 0; j < kHalf; ++j) {
+    const float v = fmaxf(gt[j * kTile] + c[j], 0.f);
+    r0 = fmaf(w[j], v, r0);
+    r1 = fmaf(w[kHalf + j], v, r1);
+    r2 = fmaf(w[2 * kHalf + j], v, r2);
+  }
+  if (pi < pp.num_points) {
+    float *o = raw + pi * 4;
+    o[0] = r0 + packed[kOffRgbB];
+    o[1] = r1 + packed[kOffRgbB + 1];
+    o[2] = r2 + packed[kOffRgbB + 2];
+  }
+}
+
+// what headbwd writes, row = point of the chunk; the rows past the last point are zero in dv and dyhead
+struct HeadOut {
+  float *v, *dv;          // [rows][128]
+  float *dyhead;          // [rows][64]: draw_rgb, dsigma, zeros
+  float *xvp;             // [rows][kv]: the ray's [embed_dirs | cam | 0]
+};
+
+// One workgroup of 64 threads, one tile.  The relu's derivative is 0 at exactly 0, as torch has it.
+__global__ __launch_bounds__(kTile) void nerfquery_headbwd_kernel(Points pp, const float *__restrict__ packed,
+                                                                  const float *__restrict__ ctab, const float *__restrict__ xv, int kv,
+                                                                  int64_t point0, const float *__restrict__ gbuf,
+                                                                  const float *__restrict__ draw, HeadOut o) {
+  __shared__ float tile[kTile * kLdT];
+  const int t = threadIdx.x;
+  const int64_t row0 = (int64_t)blockIdx.x * kTile;
+  const int64_t pi = point0 + row0 + t;
+  const bool in = pi < pp.num_points;
+  const int64_t pc = in ? pi : pp.num_points - 1;
+  const int64_t ray = pc / pp.S;
+  const float *c = ctab + ray * kHalf;
+  const float *gt = gbuf + (int64_t)blockIdx.x * (kTile * kHalf) + t;
+  const float *w = packed + kOffRgbW;
+  const float d0 = in ? draw[pi * 4] : 0.f, d1 = in ? draw[pi * 4 + 1] : 0.f, d2 = in ? draw[pi * 4 + 2] : 0.f;
+  const float ds = in ? draw[pi * 4 + 3] : 0.f;
+  // v, then dv, through the transposing tile: a thread computes a row, the workgroup stores rows coalesced
+  for (int pass = 0; pass < 2; ++pass) {
+#pragma unroll 8
+    for (int j = 0; j < kHalf; ++j) {
+      const float pre = gt[j * kTile] + c[j];
+      float val;
+      if (pass == 0) {
+        val = fmaxf(pre, 0.f);
+      } else {
+        const float s = fmaf(w[2 * kHalf + j], d2, fmaf(w[kHalf + j], d1, w[j] * d0));
+        val = pre > 0.f ? s : 0.f;
+      }
+      tile[t * kLdT + j] = val;
+    }
+    __syncthreads();
+    float *dst = (pass == 0 ? o.v : o.dv) + row0 * kHalf;
+    for (int idx = t; idx < kTile * kHalf; idx += kTile) dst[idx] = tile[(idx >> 7) * kLdT + (idx & (kHalf - 1))];
+    __syncthreads();
+  }
+  // the point's own rows of dyhead and xvp
+  float4 *dh = reinterpret_cast<float4 *>(o.dyhead + (row0 + t) * kHeadCols);
+  dh[0] = make_float4(d0, d1, d2, ds);
+  for (int k = 1; k < kHeadCols / 4; ++k) dh[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+  const float4 *xs = reinterpret_cast<const float4 *>(xv + ray * kv);
+  float4 *xd = reinterpret_cast<float4 *>(o.xvp + (row0 + t) * kv);
+  for (int k = 0; k < kv / 4; ++k) xd[k] = xs[k];
+}
+
+// ---- pack of the transposes ----------------------------------------------------------------------------------------------------
+// raw: nrpn_nerfgrid_pack's.  Segment blockIdx.y: B fragments (nerfgrid.hip) of W^T, i.e. k runs over W's rows and the output column o
+// over W's columns from col_off: the float4 of (kg, o, h) holds W[8 kg + 4 h + j][col_off + o], j = 0 .. 3
+struct PackTSeg {
+  int64_t dst, src;
+  int ld, col_off, K;     // row stride of W, first column, rows of W
+};
+struct PackTPlan {
+  PackTSeg seg[9];
+};
+
+__global__ void nerfquery_pack_t_kernel(const float *__restrict__ raw, float *__restrict__ packed_t, PackTPlan plan) {
+  const PackTSeg s = plan.seg[blockIdx.y];
+  const int64_t total = (int64_t)s.K * kW;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int j = (int)(i & 3), h = (int)((i >> 2) & 1);
+    const int64_t q = i >> 3;
+    const int o = (int)(q % kW), kg = (int)(q / kW);
+    packed_t[s.dst + i] = raw[s.src + (int64_t)(8 * kg + 4 * h + j) * s.ld + s.col_off + o];
+  }
+}
+
+// ---- dgrad -----------------------------------------------------------------------------------------------------------------------
+// One workgroup of 256 threads, one tile: out[p][0 .. 255] = (sum_n dy[p][n] W[n][.] + dsig[p] * alpha_w[.]) [mask[p][.] > 0].  dy
+// [rows][K], K = 128 or 256; wt: the packed W^T; dsig: column 3 of dyhead, or null; mask [rows][256] or null; out may be mask.
+__global__ __launch_bounds__(256) void nerfquery_dgrad_kernel(const float *__restrict__ dy, int K, const float *__restrict__ wt,
+                                                              const float *__restrict__ dyhead, const float *__restrict__ alpha_w,
+                                                              const float *mask, float *out) {
+  extern __shared__ __align__(16) float act[];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
+  const int64_t row0 = (int64_t)blockIdx.x * kTile;
+  const int k4 = K >> 2;
+  for (int idx = t; idx < kTile * k4; idx += 256) {
+    const int row = idx / k4, c4 = idx - row * k4;
+    *reinterpret_cast<float4 *>(act + row * kLd + kEnc + 4 * c4) = *reinterpret_cast<const float4 *>(dy + (row0 + row) * K + 4 * c4);
+  }
+  __syncthreads();
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[m][c][e] = 0.f;
+  const int col0 = wave * 64;
+  gemm_tile<2>(act, kEnc, K, reinterpret_cast<const float4 *>(wt), kW, col0, acc);
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const int col = col0 + 32 * c + r;
+    const float aw = dyhead ? alpha_w[col] : 0.f;
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int64_t row = row0 + 32 * m + acc_row(e, h);
+        float v = acc[m][c][e];
+        if (dyhead) v = fmaf(dyhead[row * kHeadCols + 3], aw, v);
+        if (mask) v = mask[row * kW + col] > 0.f ? v : 0.f;
+        out[row * kW + col] = v;
+      }
+  }
+}
+
+// ---- wgrad -----------------------------------------------------------------------------------------------------------------------
+constexpr int kWgSteps = 8;           // point pairs per register set
+struct WgFrag {
+  float a0[kWgSteps], a1[kWgSteps], b0[kWgSteps], b1[kWgSteps];
+};
+__device__ __forceinline__ void wg_load(WgFrag &f, const float *__restrict__ ap, const float *__restrict__ bp, int ldy, int ldx) {
+#pragma unroll
+  for (int s = 0; s < kWgSteps; ++s) {
+    f.a0[s] = ap[(int64_t)2 * s * ldy];
+    f.a1[s] = ap[(int64_t)2 * s * ldy + 32];
+    f.b0[s] = bp[(int64_t)2 * s * ldx];
+    f.b1[s] = bp[(int64_t)2 * s * ldx + 32];
+  }
+}
+__device__ __forceinline__ void wg_mma(const WgFrag &f, f32x16 (&acc)[2][2], bool sums, double &bs0, double &bs1) {
+#pragma unroll
+  for (int s = 0; s < kWgSteps; ++s) {
+    if (sums) {
+      bs0 += (double)f.a0[s];
+      bs1 += (double)f.a1[s];
+    }
+    acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a0[s], f.b0[s], acc[0][0], 0, 0, 0);
+    acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a0[s], f.b1[s], acc[0][1], 0, 0, 0);
+    acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a1[s], f.b0[s], acc[1][0], 0, 0, 0);
+    acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a1[s], f.b1[s], acc[1][1], 0, 0, 0);
+  }
+}
+
+// dW = dY^T X over the rows of one slice.  dy [rows][ldy], n columns used; x [rows][ldx], kpad columns used (n, kpad multiples of 64).
+// A wave owns the 64 x 64 block (nb, kb) of dW for slice blockIdx.y: per pair of points one A and one B value per lane and accumulator
+// row / column block, four MFMAs.  partial [slice][n][kpad]; bias (or null) f64 [slice][2][n]: the column sums of dY over the even and
+// the odd rows of the slice, added in float64 by the waves with kb = 0 (a bias gradient has no product to hide a float32 sum's
+// rounding behind, and the checker's bound on it is a few ulp).
+__global__ __launch_bounds__(256) void nerfquery_wgrad_kernel(const float *__restrict__ dy, int ldy, int n, const float *__restrict__ x,
+                                                              int ldx, int kpad, int64_t rows, int64_t rows_per_slice,
+                                                              float *__restrict__ partial, double *__restrict__ bias) {
+  const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+  const int kblocks = kpad >> 6;
+  const int blk = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (blk >= (n >> 6) * kblocks) return;
+  const int nb = blk / kblocks, kb = blk - nb * kblocks;
+  const int64_t slice = blockIdx.y;
+  int64_t p0 = slice * rows_per_slice, p1 = p0 + rows_per_slice;
+  if (p0 > rows) p0 = rows;
+  if (p1 > rows) p1 = rows;
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[m][c][e] = 0.f;
+  double bs0 = 0.0, bs1 = 0.0;
+  const bool sums = bias && kb == 0;
+  const float *ap = dy + (p0 + h) * ldy + nb * 64 + r;
+  const float *bp = x + (p0 + h) * ldx + kb * 64 + r;
+  // blocks of kWgSteps point pairs; two register sets alternate as in gemm_tile, so the loads of block n + 1 are in flight during the
+  // MFMAs of block n.  Rows come in whole tiles: the block count is a multiple of 4, or 0 for an empty slice
+  const int blocks = (int)((p1 - p0) / (2 * kWgSteps));
+  WgFrag f0, f1;
+  if (blocks > 0) wg_load(f0, ap, bp, ldy, ldx);
+  for (int blk = 0; blk < blocks; blk += 2) {
+    wg_load(f1, ap + (int64_t)(blk + 1) * 2 * kWgSteps * ldy, bp + (int64_t)(blk + 1) * 2 * kWgSteps * ldx, ldy, ldx);
+    __builtin_amdgcn_sched_barrier(0);
+    wg_mma(f0, acc, sums, bs0, bs1);
+    __builtin_amdgcn_sched_barrier(0);
+    const int nx = blk + 2 < blocks ? blk + 2 : blk;            // the last iteration reloads its own block: in bounds, unused
+    wg_load(f0, ap + (int64_t)nx * 2 * kWgSteps * ldy, bp + (int64_t)nx * 2 * kWgSteps * ldx, ldy, ldx);
+    __builtin_amdgcn_sched_barrier(0);
+    wg_mma(f1, acc, sums, bs0, bs1);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  float *out = partial + slice * n * kpad;
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int e = 0; e < 16; ++e)
+        out[(int64_t)(nb * 64 + 32 * m + acc_row(e, h)) * kpad + kb * 64 + 32 * c + r] = acc[m][c][e];
+  if (sums) {
+    double *b = bias + (slice * 2 + h) * n + nb * 64 + r;
+    b[0] = bs0;
+    b[32] = bs1;
+  }
+}
+
+// gacc[dst + i * ld + j] += sum over the parts, in order, of partial[part][row_lo + i][col_lo + j], i < nr, j < nc; float64
+template <class T>
+__global__ void nerfquery_reduce_kernel(const T *__restrict__ partial, int parts, int n, int kpad, int row_lo, int nr, int col_lo,
+                                        int nc, double *__restrict__ gacc, int64_t dst, int ld) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= nr * nc) return;
+  const int i = idx / nc, j = idx - i * nc;
+  const T *p = partial + (int64_t)(row_lo + i) * kpad + col_lo + j;
+  double s = 0.0;
+#pragma unroll 16
+  for (int q = 0; q < parts; ++q) s += (double)p[(int64_t)q * n * kpad];
+  gacc[dst + (int64_t)i * ld + j] += s;
+}
+
+// grads[i] = (float)gacc[i]; before that dcam[k] = sum_j W_c[j][k] db_views[j] in j order
+__global__ void nerfquery_finish_kernel(double *__restrict__ gacc, int64_t total, int64_t cam_at, int64_t b_views_at,
+                                        const float *__restrict__ w_view, int views_ch, int cam_ch, float *__restrict__ grads) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  double v = gacc[i];
+  if (i >= cam_at && i < cam_at + cam_ch) {
+    const int k = (int)(i - cam_at);
+    v = 0.0;
+    for (int j = 0; j < kHalf; ++j) v += (double)w_view[j * (views_ch + cam_ch) + views_ch + k] * gacc[b_views_at + j];
+  }
+  grads[i] = (float)v;
+}
+
+// ---- host ------------------------------------------------------------------------------------------------------------------------
+struct QueryCall {
+  Points pp;
+  Model m;
+  const float *viewdirs, *packed, *w_view, *b_view, *cam;
+  int64_t num_rays, chunk;
+  void *work;
+  int64_t work_bytes;
+  hipStream_t stream;
+  int64_t chunk_tiles() const { return cdiv64(chunk < pp.num_points ? chunk : pp.num_points, kTile); }
+};
+
+bool sizes_ok(int64_t num_rays, int samples, int64_t chunk) {
+  return num_rays >= 1 && samples >= 1 && samples <= 65536 && num_rays < ((int64_t)1 << 31) && chunk >= 1 &&
+         num_rays * samples < ((int64_t)1 << 40);
+}
+bool model_ok(const Model &m) {
+  return m.multires >= 0 && m.input_ch() <= kEnc && m.multires_views >= 0 && m.views_ch() <= kMaxViewsCh && m.cam_ch >= 0 &&
+         m.cam_ch <= 65536;
+}
+
+struct Layout {           // of the work buffer, in bytes; every part 16-byte aligned
+  int64_t ctab, xv, gbuf, fwd_end;                                             // forward
+  int64_t enc, h, f, v, dv, dyhead, xvp, partial, bias, gacc, total;           // backward
+  int64_t rows;
+};
+Layout layout(const Model &m, int64_t num_rays, int64_t chunk_tiles) {
+  Layout l{};
+  l.rows = chunk_tiles * kTile;
+  l.ctab = 0;
+  l.xv = l.ctab + num_rays * kHalf * 4;
+  l.gbuf = l.xv + align16(num_rays * m.kv() * 4);
+  l.fwd_end = l.gbuf + l.rows * kHalf * 4;
+  l.enc = l.fwd_end;
+  l.h = l.enc + l.rows * kEnc * 4;
+  l.f = l.h + l.rows * kLayers * kW * 4;
+  l.v = l.f + l.rows * kW * 4;
+  l.dv = l.v + l.rows * kHalf * 4;
+  l.dyhead = l.dv + l.rows * kHalf * 4;
+  l.xvp = l.dyhead + l.rows * kHeadCols * 4;
+  l.partial = l.xvp + l.rows * m.kv() * 4;
+  l.bias = l.partial + (int64_t)kSlices * (kW > m.kv() / 2 ? kW * kW : kHalf * m.kv()) * 4;
+  l.gacc = l.bias + (int64_t)kSlices * 2 * kW * 8;
+  l.total = l.gacc + align16(grad_layout(m).total * 8);
+  return l;
+}
+
+int check(const char *who, const QueryCall &c, bool backward) {
+  NRPN_REQUIRE(c.pp.pts && c.viewdirs && c.packed && c.w_view && c.b_view && c.work, "%s: null pointer", who);
+  NRPN_REQUIRE(model_ok(c.m), "%s: multires %d / multires_views %d / input_ch_cam %d", who, c.m.multires, c.m.multires_views, c.m.cam_ch);
+  NRPN_REQUIRE(c.m.cam_ch == 0 || c.cam, "%s: input_ch_cam %d without an embedded_cam", who, c.m.cam_ch);
+  NRPN_REQUIRE(sizes_ok(c.num_rays, c.pp.S, c.chunk), "%s: %lld rays of %d points in chunks of %lld", who, (long long)c.num_rays, c.pp.S,
+               (long long)c.chunk);
+  NRPN_REQUIRE(c.chunk_tiles() <= 0x7fffff, "%s: chunk too large", who);
+  const Layout l = layout(c.m, c.num_rays, c.chunk_tiles());
+  NRPN_REQUIRE(c.work_bytes >= (backward ? l.total : l.fwd_end), "%s: work buffer of %lld bytes is too small", who,
+               (long long)c.work_bytes);
+  return NRPN_OK;
+}
+
+int launch_rays(const QueryCall &c, const Layout &l, bool with_xv) {
+  char *wk = static_cast<char *>(c.work);
+  nerfquery_rays_kernel<<<(unsigned)c.num_rays, kHalf, 0, c.stream>>>(c.viewdirs, c.w_view, c.b_view, c.cam, c.m.multires_views, c.m.cam_ch,
+                                                                      c.m.kv(), reinterpret_cast<float *>(wk + l.ctab),
+                                                                      with_xv ? reinterpret_cast<float *>(wk + l.xv) : nullptr);
+  NRPN_LAUNCH_CHECK("nerfquery_rays_kernel");
+  return NRPN_OK;
+}
+
+int forward(const QueryCall &c, float *raw) {
+  if (int rc = check("nerfquery_forward", c, false)) return rc;
+  NRPN_REQUIRE(raw, "nerfquery_forward: null output");
+  NRPN_LDS(nerfquery_trunk_kernel, kLdsBytes);
+  const Layout l = layout(c.m, c.num_rays, c.chunk_tiles());
+  char *wk = static_cast<char *>(c.work);
+  const float *ctab = reinterpret_cast<float *>(wk + l.ctab);
+  float *gbuf = reinterpret_cast<float *>(wk + l.gbuf);
+  if (int rc = launch_rays(c, l, false)) return rc;
+  for (int64_t p0 = 0; p0 < c.pp.num_points; p0 += l.rows) {
+    const int64_t left = c.pp.num_points - p0;
+    const int tiles = (int)cdiv64(left < l.rows ? left : l.rows, kTile);
+    nerfquery_trunk_kernel<<<tiles, 256, kLdsBytes, c.stream>>>(c.pp, c.m.multires, c.packed, p0, gbuf, raw);
+    NRPN_LAUNCH_CHECK("nerfquery_trunk_kernel");
+    nerfquery_head_kernel<<<tiles, kTile, 0, c.stream>>>(c.pp, c.packed, ctab, p0, gbuf, raw);
+    NRPN_LAUNCH_CHECK("nerfquery_head_kernel");
+  }
+  return NRPN_OK;
+}
+
+struct Wgrad {            // one product of the backward and where its rows and columns go
+  const float *dy;
+  int ldy, n;
+  const float *x;
+  int ldx, kpad;
+  int row_lo, nr, nc;     // rows row_lo .. row_lo + nr of dW, columns 0 .. nc
+  int64_t dst;            // of the first of them in the gradient
+  int ld;
+  int64_t bias_dst;       // of column sum row_lo, or -1
+};
+
+int backward(const QueryCall &c, const float *packed_t, const float *draw, float *grads) {
+  if (int rc = check("nerfquery_backward", c, true)) return rc;
+  NRPN_REQUIRE(packed_t && draw && grads, "nerfquery_backward: null pointer");
+  NRPN_LDS(nerfquery_trunk_keep_kernel, kLdsBytes);
+  NRPN_LDS(nerfquery_dgrad_kernel, kLdsBytes);
+  const Model &m = c.m;
+  const Layout l = layout(m, c.num_rays, c.chunk_tiles());
+  const GradLayout gl = grad_layout(m);
+  char *wk = static_cast<char *>(c.work);
+  auto F = [&](int64_t at) { return reinterpret_cast<float *>(wk + at); };
+  const float *ctab = F(l.ctab), *xv = F(l.xv);
+  float *gbuf = F(l.gbuf), *partial = F(l.partial);
+  double *bias = reinterpret_cast<double *>(wk + l.bias);
+  double *gacc = reinterpret_cast<double *>(wk + l.gacc);
+  const Kept kept{F(l.enc), F(l.h), F(l.f), l.rows};
+  const HeadOut ho{F(l.v), F(l.dv), F(l.dyhead), F(l.xvp)};
+  const int kv = m.kv(), in_ch = m.input_ch();
+  if (int rc = launch_rays(c, l, true)) return rc;
+  NRPN_HIP(hipMemsetAsync(gacc, 0, gl.total * 8, c.stream));
+
+  for (int64_t p0 = 0; p0 < c.pp.num_points; p0 += l.rows) {
+    const int64_t left = c.pp.num_points - p0;
+    const int tiles = (int)cdiv64(left < l.rows ? left : l.rows, kTile);
+    const int64_t rows = (int64_t)tiles * kTile, rps = cdiv64(tiles, kSlices) * kTile;
+    // h and f of this chunk are laid out for l.rows rows whatever the chunk's own count: Kept::rows is the stride of h's layers
+    auto wgrad = [&](const Wgrad &w) -> int {
+      const int blocks = (w.n >> 6) * (w.kpad >> 6);
+      nerfquery_wgrad_kernel<<<dim3((blocks + 3) / 4, kSlices), 256, 0, c.stream>>>(w.dy, w.ldy, w.n, w.x, w.ldx, w.kpad, rows, rps, partial,
+                                                                                   w.bias_dst >= 0 ? bias : nullptr);
+      NRPN_LAUNCH_CHECK("nerfquery_wgrad_kernel");
+      if (w.nc > 0) {
+        nerfquery_reduce_kernel<float><<<(w.nr * w.nc + 255) / 256, 256, 0, c.stream>>>(partial, kSlices, w.n, w.kpad, w.row_lo, w.nr, 0, w.nc, gacc,
+                                                                               w.dst, w.ld);
+        NRPN_LAUNCH_CHECK("nerfquery_reduce_kernel");
+      }
+      if (w.bias_dst >= 0) {
+        nerfquery_reduce_kernel<double><<<(w.nr + 255) / 256, 256, 0, c.stream>>>(bias, 2 * kSlices, 1, w.n, 0, 1, w.row_lo, w.nr, gacc, w.bias_dst,
+                                                                         w.nr);
+        NRPN_LAUNCH_CHECK("nerfquery_reduce_kernel");
+      }
+      return NRPN_OK;
+    };
+    auto dgrad = [&](const float *dy, int K, int64_t wt_at, bool alpha, const float *mask, float *out) -> int {
+      nerfquery_dgrad_kernel<<<tiles, 256, kLdsBytes, c.stream>>>(dy, K, packed_t + wt_at, alpha ? ho.dyhead : nullptr,
+                                                                  c.packed + kOffAlphaW, mask, out);
+      NRPN_LAUNCH_CHECK("nerfquery_dgrad_kernel");
+      return NRPN_OK;
+    };
+    auto hl = [&](int i) { return kept.h + (int64_t)i * l.rows * kW; };
+
+    nerfquery_trunk_keep_kernel<<<tiles, 256, kLdsBytes, c.stream>>>(c.pp, m.multires, c.packed, p0, gbuf, kept);
+    NRPN_LAUNCH_CHECK("nerfquery_trunk_keep_kernel");
+    nerfquery_headbwd_kernel<<<tiles, kTile, 0, c.stream>>>(c.pp, c.packed, ctab, xv, kv, p0, gbuf, draw, ho);
+    NRPN_LAUNCH_CHECK("nerfquery_headbwd_kernel");
+    // rgb_linear and alpha_linear: rows 0 .. 2 and row 3 of the head's cotangent
+    if (int rc = wgrad({ho.dyhead, kHeadCols, kHeadCols, ho.v, kHalf, kHalf, 0, 3, kHalf, gl.w_rgb, kHalf, gl.b_rgb})) return rc;
+    if (int rc = wgrad({ho.dyhead, kHeadCols, kHeadCols, hl(7), kW, kW, 3, 1, kW, gl.w_alpha, kW, gl.b_alpha})) return rc;
+    // views_linears.0: the feature columns, then the view and camera columns
+    const int ldw = kW + m.ldv();
+    if (int rc = wgrad({ho.dv, kHalf, kHalf, kept.f, kW, kW, 0, kHalf, kW, gl.w_views, ldw, gl.b_views})) return rc;
+    if (m.ldv() > 0)
+      if (int rc = wgrad({ho.dv, kHalf, kHalf, ho.xvp, kv, kv, 0, kHalf, m.ldv(), gl.w_views + kW, ldw, -1})) return rc;
+    if (int rc = dgrad(ho.dv, kHalf, kOffTf, false, nullptr, kept.f)) return rc;                          // df
+    if (int rc = wgrad({kept.f, kW, kW, hl(7), kW, kW, 0, kW, kW, gl.w_feat, kW, gl.b_feat})) return rc;
+    if (int rc = dgrad(kept.f, kW, 7 * kSzT, true, hl(7), hl(7))) return rc;                              // dy_7
+    for (int i = kLayers - 1; i >= 1; --i) {
+      const int ldi = i == kSkipLayer ? in_ch + kW : kW, hoff = i == kSkipLayer ? in_ch : 0;
+      if (int rc = wgrad({hl(i), kW, kW, hl(i - 1), kW, kW, 0, kW, kW, gl.w_pts[i] + hoff, ldi, gl.b_pts[i]})) return rc;
+      if (i == kSkipLayer)
+        if (int rc = wgrad({hl(i), kW, kW, kept.enc, kEnc, kEnc, 0, kW, in_ch, gl.w_pts[i], ldi, -1})) return rc;
+      if (int rc = dgrad(hl(i), kW, (int64_t)(i - 1) * kSzT, false, hl(i - 1), hl(i - 1))) return rc;   // dy_{i-1}
+    }
+    if (int rc = wgrad({hl(0), kW, kW, kept.enc, kEnc, kEnc, 0, kW, in_ch, gl.w_pts[0], in_ch, gl.b_pts[0]})) return rc;
+  }
+  nerfquery_finish_kernel<<<(unsigned)cdiv64(gl.total, 256), 256, 0, c.stream>>>(gacc, gl.total, gl.cam, gl.b_views, c.w_view, m.views_ch(),
+                                                                                 m.cam_ch, grads);
+  NRPN_LAUNCH_CHECK("nerfquery_finish_kernel");
+  return NRPN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t nrpn_nerfquery_work_bytes(int what, int64_t num_rays, int num_samples, int64_t chunk, int multires, int multires_views,
+                                  int input_ch_cam) {
+  const Model m{multires, multires_views, input_ch_cam};
+  if (what == 2) return kPackedTFloats * 4;
+  if (what == 4) return 4 * (int64_t)(kEnc + kLayers * kW + kW + 3 * kHalf + kHeadCols + (model_ok(m) ? m.kv() : 0));
+  if (!model_ok(m) || !sizes_ok(num_rays, num_samples, chunk)) return -1;
+  if (what == 3) return grad_layout(m).total;
+  const int64_t n = num_rays * num_samples;
+  const Layout l = layout(m, num_rays, cdiv64(chunk < n ? chunk : n, kTile));
+  return what == 0 ? l.fwd_end : what == 1 ? l.total : -1;
+}
+
+int nrpn_nerfquery_pack_t(const float *raw, int input_ch, float *packed_t, nrpn_stream_t stream) {
+  NRPN_REQUIRE(raw && packed_t, "nerfquery_pack_t: null pointer");
+  NRPN_REQUIRE(input_ch >= 3 && input_ch <= kEnc, "nerfquery_pack_t: input_ch %d outside 3 .. %d", input_ch, kEnc);
+  PackTPlan plan{};
+  int64_t src = (int64_t)kW * input_ch;                       // after pts_linears.0
+  for (int i = 1; i <= 9; ++i) {                              // raw order: pts_linears 1 .. 7, feature_linear, W_f
+    const int ld = i == kSkipLayer ? input_ch + kW : kW, K = i == 9 ? kHalf : kW;
+    plan.seg[i - 1] = PackTSeg{(int64_t)(i - 1) * kSzT, src, ld, i == kSkipLayer ? input_ch : 0, K};
+    src += (int64_t)K * ld;
+  }
+  nerfquery_pack_t_kernel<<<dim3(64, 9), 256, 0, as_stream(stream)>>>(raw, packed_t, plan);
+  NRPN_LAUNCH_CHECK("nerfquery_pack_t_kernel");
+  return NRPN_OK;
+}
+
+int nrpn_nerfquery_forward(const float *pts, const float *viewdirs, int64_t num_rays, int num_samples, float center_x, float center_y,
+                           float center_z, float bb_scale, int multires, int multires_views, int input_ch_cam, const float *packed,
+                           const float *w_view, const float *b_view, const float *embedded_cam, int64_t chunk, void *work,
+                           int64_t work_bytes, float *raw, nrpn_stream_t stream) {
+  QueryCall c{Points{pts, num_rays * num_samples, num_samples, center_x, center_y, center_z, bb_scale},
+              Model{multires, multires_views, input_ch_cam}, viewdirs, packed, w_view, b_view, embedded_cam, num_rays, chunk, work,
+              work_bytes, as_stream(stream)};
+  return forward(c, raw);
+}
+
+int nrpn_nerfquery_backward(const float *pts, const float *viewdirs, int64_t num_rays, int num_samples, float center_x, float center_y,
+                            float center_z, float bb_scale, int multires, int multires_views, int input_ch_cam, const float *packed,
+                            const float *packed_t, const float *w_view, const float *b_view, const float *embedded_cam,
+                            const float *draw, int64_t chunk, void *work, int64_t work_bytes, float *grads, nrpn_stream_t stream) {
+  QueryCall c{Points{pts, num_rays * num_samples, num_samples, center_x, center_y, center_z, bb_scale},
+              Model{multires, multires_views, input_ch_cam}, viewdirs, packed, w_view, b_view, embedded_cam, num_rays, chunk, work,
+              work_bytes, as_stream(stream)};
+  return backward(c, packed_t, draw, grads);
+}
+
+}  // extern "C"

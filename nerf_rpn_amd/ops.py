@@ -2539,9 +2539,19 @@ def nerf_grid_config(cfg):
 class NerfGridWeights:
     """The device-side weights of one NeRF MLP for nerf_grid_query: the packed trunk and rgb_linear (nrpn_nerfgrid_pack), the view
     columns W_d and the bias of views_linears.0 for the c_p table, and the options they were built for."""
-    def __init__(self, packed, w_dirs, b_views, config, w_view=None):
+    def __init__(self, packed, w_dirs, b_views, config, w_view=None, raw=None):
         self.packed, self.w_dirs, self.b_views, self.config = packed, w_dirs, b_views, config
         self.w_view = w_view        # the view and camera columns together, [128][views_ch + input_ch_cam]: nerf_render's head
+        self.raw = raw              # what nrpn_nerfgrid_pack read: nerf_query's backward packs the transposes from it
+
+
+def _nerf_raw(t):
+    """The float32 device tensors of a network, keyed without ``module.`` -> the one array nrpn_nerfgrid_pack reads."""
+    return torch.cat([t[f"pts_linears.{i}.weight"].reshape(-1) for i in range(8)]
+                     + [t["feature_linear.weight"].reshape(-1), t["views_linears.0.weight"][:, :256].reshape(-1)]
+                     + [t[f"pts_linears.{i}.bias"] for i in range(8)]
+                     + [t["feature_linear.bias"], t["alpha_linear.weight"].reshape(-1), t["alpha_linear.bias"],
+                        t["rgb_linear.weight"].reshape(-1), t["rgb_linear.bias"]]).contiguous()
 
 
 def nerf_grid_pack(state_dict, cfg):
@@ -2565,14 +2575,10 @@ def nerf_grid_pack(state_dict, cfg):
             raise lib.NrpnError(f"nerf_grid_query: {k} has shape {tuple(sd[k].shape)}, the configuration implies {shape}")
     t = {k: sd[k].detach().to(device=dev, dtype=torch.float32) for k in want}
     wv = t["views_linears.0.weight"]
-    raw = torch.cat([t[f"pts_linears.{i}.weight"].reshape(-1) for i in range(8)]
-                    + [t["feature_linear.weight"].reshape(-1), wv[:, :W].reshape(-1)]
-                    + [t[f"pts_linears.{i}.bias"] for i in range(8)]
-                    + [t["feature_linear.bias"], t["alpha_linear.weight"].reshape(-1), t["alpha_linear.bias"],
-                       t["rgb_linear.weight"].reshape(-1), t["rgb_linear.bias"]]).contiguous()
+    raw = _nerf_raw(t)
     packed = torch.empty(lib.query("nerfgrid_work_bytes", 0, 0) // 4, dtype=torch.float32, device=dev)
     call("nerfgrid_pack", _p(raw), input_ch, _p(packed), _s())
-    return NerfGridWeights(packed, wv[:, W:W + views_ch].contiguous(), t["views_linears.0.bias"], c, wv[:, W:].contiguous())
+    return NerfGridWeights(packed, wv[:, W:W + views_ch].contiguous(), t["views_linears.0.bias"], c, wv[:, W:].contiguous(), raw)
 
 
 def _nerf_weights(who, weights_or_state, cfg):
@@ -2921,3 +2927,110 @@ def nerf_view_metrics(rgb, target_rgb, depth=None, target_depth=None, valid_dept
                ssim=(s[1] / windows + s[2] / windows + s[3] / windows) / 3.,
                depth_rmse=math.sqrt(s[4] / n_valid) if n_valid > 0 else None, n_valid=n_valid)
     return out
+
+
+# ======================================================================================================================
+# the NeRF MLP query as a differentiable operation  [f9]
+# ======================================================================================================================
+NERF_QUERY_DEFAULT_CHUNK = 1 << 16     # points per launch group: 720 MiB of backward scratch (11520 bytes per point)
+NERF_QUERY_PARAMS = tuple([f"pts_linears.{i}.weight" for i in range(8)]
+                          + ["feature_linear.weight", "alpha_linear.weight", "views_linears.0.weight", "rgb_linear.weight"]
+                          + [f"pts_linears.{i}.bias" for i in range(8)]
+                          + ["feature_linear.bias", "alpha_linear.bias", "views_linears.0.bias", "rgb_linear.bias"])
+
+
+class NerfQueryFn(torch.autograd.Function):
+    """run_network (run_nerf.py:50-65) and its backward on the GPU (csrc/nerfquery.hip).  forward(pts [R, S, 3], viewdirs [R, 3], cam
+    [input_ch_cam], cfg, bounds, chunk, *params): params are the 24 tensors in NERF_QUERY_PARAMS order -> raw [R, S, 4].  Nothing but
+    the inputs is kept for the backward: it runs the forward again, chunk by chunk, into the scratch."""
+
+    @staticmethod
+    def forward(ctx, pts, viewdirs, cam, cfg, bounds, chunk, *params):
+        c = nerf_grid_config(cfg)
+        weights = nerf_grid_pack(dict(zip(NERF_QUERY_PARAMS, params)), cfg)
+        R, S = int(pts.shape[0]), int(pts.shape[1])
+        size = (R, S, chunk, c["multires"], c["multires_views"], c["input_ch_cam"])
+        nbytes = lib.query("nerfquery_work_bytes", 0, *size)
+        if nbytes < 0:
+            raise lib.NrpnError(f"nerf_query: {R} rays of {S} points in chunks of {chunk} are outside the supported range")
+        work = torch.empty(nbytes, dtype=torch.uint8, device=pts.device)
+        raw = torch.empty((R, S, 4), dtype=torch.float32, device=pts.device)
+        call("nerfquery_forward", _p(pts), _p(viewdirs), R, S, *bounds, c["multires"], c["multires_views"], c["input_ch_cam"],
+             _p(weights.packed), _p(weights.w_view), _p(weights.b_views), _p(cam) if c["input_ch_cam"] else None, chunk, _p(work), nbytes,
+             _p(raw), _s())
+        ctx.save_for_backward(pts, viewdirs, cam)
+        ctx.weights, ctx.size, ctx.bounds, ctx.shapes = weights, size, bounds, [tuple(p.shape) for p in params]
+        return raw
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, draw):
+        pts, viewdirs, cam = ctx.saved_tensors
+        weights, size = ctx.weights, ctx.size
+        R, S, chunk, multires, multires_views, cam_ch = size
+        dev = pts.device
+        packed_t = torch.empty(lib.query("nerfquery_work_bytes", 2, *size) // 4, dtype=torch.float32, device=dev)
+        call("nerfquery_pack_t", _p(weights.raw), 3 + 6 * multires, _p(packed_t), _s())
+        nbytes = lib.query("nerfquery_work_bytes", 1, *size)
+        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        grads = torch.empty(lib.query("nerfquery_work_bytes", 3, *size), dtype=torch.float32, device=dev)
+        draw = draw.to(torch.float32).contiguous()
+        call("nerfquery_backward", _p(pts), _p(viewdirs), R, S, *ctx.bounds, multires, multires_views, cam_ch, _p(weights.packed),
+             _p(packed_t), _p(weights.w_view), _p(weights.b_views), _p(cam) if cam_ch else None, _p(draw), chunk, _p(work), nbytes,
+             _p(grads), _s())
+        out, at = [], 0
+        for shape in ctx.shapes:
+            n = math.prod(shape)
+            out.append(grads[at:at + n].view(shape))
+            at += n
+        dcam = grads[at:at + cam_ch]
+        return (None, None, dcam, None, None, None, *out)
+
+
+def nerf_query(params, cfg, pts, viewdirs, embedded_cam=None, bb_center=(0., 0., 0.), bb_scale=1., chunk=None):
+    """network_query_fn(pts, viewdirs, embedded_cam, network_fn) of the reference (run_network, run_nerf.py:50-65) for the NeRF MLP of
+    DESIGN.md 3.16, differentiable with respect to the network's 24 parameter tensors and to embedded_cam.
+
+    params: a mapping from the checkpoint's key names (with or without ``module.``) to float32 device tensors; cfg: the run's
+    args.json, through nerf_grid_config.  pts [R, S, 3] float32 world points; viewdirs [R, 3] float32, used as given (render has
+    normalised them; nothing is normalised here); embedded_cam [input_ch_cam] (default zeros); bb_center [3], bb_scale: the scene
+    normalisation.  Returns raw [R, S, 4] float32 on the device: rgb before the sigmoid, sigma before the relu.  pts or viewdirs that
+    require grad raise NotImplementedError (no entry point of the reference differentiates them).
+
+    chunk (points, default 2^16, rounded up to tiles of 64) bounds the scratch: the forward keeps 512 bytes per point of a chunk and
+    nothing for the backward, which re-runs the forward chunk by chunk and keeps 11264 + 4 * ceil64(views_ch + input_ch_cam) bytes
+    per point (11520 for the default options), plus 512 + 4 * ceil64(views_ch + input_ch_cam) bytes per ray, 16 MiB of slice partials
+    and the float64 gradient (lib.query("nerfquery_work_bytes", ...) has the figures).  raw does not depend on chunk, bit for bit.
+    The gradients are sums over points: for a given chunk and given inputs they are bit-equal from call to call (no atomics,
+    fixed-order sums); for different chunks they differ in rounding only."""
+    c = nerf_grid_config(cfg)
+    if not torch.cuda.is_available():
+        raise lib.NrpnError("nerf_query needs a gfx950 device (the product path has no CPU fallback)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    for name, x in (("pts", pts), ("viewdirs", viewdirs)):
+        if isinstance(x, torch.Tensor) and x.requires_grad:
+            raise NotImplementedError(f"nerf_query: {name} requires grad; the query is differentiable in the parameters and embedded_cam only")
+    sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in params.items()}
+    for k in NERF_QUERY_PARAMS:
+        if k not in sd:
+            raise lib.NrpnError(f"nerf_query: the parameters have no {k}")
+        if not isinstance(sd[k], torch.Tensor) or sd[k].dtype != torch.float32 or not sd[k].is_cuda:
+            raise lib.NrpnError(f"nerf_query: {k} must be a float32 device tensor")
+    pts = torch.as_tensor(pts, dtype=torch.float32).to(dev).contiguous()
+    viewdirs = torch.as_tensor(viewdirs, dtype=torch.float32).to(dev).contiguous()
+    if pts.dim() != 3 or pts.shape[2] != 3 or pts.shape[0] < 1 or pts.shape[1] < 1:
+        raise lib.NrpnError(f"nerf_query expects pts [R, S, 3], got {tuple(pts.shape)}")
+    if tuple(viewdirs.shape) != (pts.shape[0], 3):
+        raise lib.NrpnError(f"nerf_query expects viewdirs [{pts.shape[0]}, 3], got {tuple(viewdirs.shape)}")
+    cam_ch = c["input_ch_cam"]
+    if embedded_cam is None:
+        cam = torch.zeros(cam_ch, dtype=torch.float32, device=dev)
+    else:
+        cam = embedded_cam if isinstance(embedded_cam, torch.Tensor) else torch.as_tensor(embedded_cam, dtype=torch.float32)
+        cam = cam.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+    if cam.numel() != cam_ch:
+        raise lib.NrpnError(f"nerf_query: embedded_cam has {cam.numel()} values, input_ch_cam is {cam_ch}")
+    chunk = NERF_QUERY_DEFAULT_CHUNK if chunk is None else int(chunk)
+    if chunk < 1:
+        raise lib.NrpnError(f"nerf_query: chunk {chunk}")
+    return NerfQueryFn.apply(pts, viewdirs, cam, cfg, _nerf_bounds(bb_center, bb_scale), chunk, *(sd[k] for k in NERF_QUERY_PARAMS))
