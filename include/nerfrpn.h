@@ -862,6 +862,48 @@ int nrpn_nerfquery_backward(const float *pts, const float *viewdirs, int64_t num
                             const float *packed_t, const float *w_view, const float *b_view, const float *embedded_cam,
                             const float *draw, int64_t chunk, void *work, int64_t work_bytes, float *grads, nrpn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The ray stage of NeRF training as differentiable operations, ops.nerf_composite and ops.nerf_ray_losses.  [f10]  Replaces
+ * compute_weights and raw2outputs (data/scannet/run_nerf.py:419-469) on the merged samples of forward_with_additonal_samples
+ * (:504-512), the losses of train (:837-847) and what loss.backward() computes between them and raw; DESIGN.md 3.21.  One thread per
+ * ray; everything after the float32 inputs is float64; no atomics, sums in a fixed order, repeated calls are bit-equal.
+ * nrpn_nerfcomposite_work_bytes(num_rays, s1, s2): bytes of nrpn_nerfraylosses_forward's scratch (the composite needs none); -1 for
+ *   sizes outside the range nrpn_nerfrender_work_bytes supports (num_rays < 2^31).
+ * nrpn_nerfcomposite_forward: raw1 f32 [num_rays][s1][4] at z1 f32 [s1] (z1_stride 0: every ray's) or [num_rays][s1] (z1_stride s1);
+ *   raw2 f32 [num_rays][s2][4] at z2 f32 [num_rays][s2] (s2 may be 0, both null).  Both lists are non-decreasing per ray (not checked);
+ *   they are merged, list 1 first on a tie.  noise1 f32 [num_rays][s1], noise2 f32 [num_rays][s2] (both null for none): added to a
+ *   sample's sigma before the relu (:426).  rays_d f32 [num_rays][3].  -> rgb_map f32 [num_rays][3], depth_map, acc_map, disp_map f32
+ *   [num_rays], weights and z_vals f32 [num_rays][s1 + s2] in merged order.  Without noise, the bits of nrpn_nerfrender_rays' rgb,
+ *   depth, acc, disp, weights and z_vals for the same raw.
+ * nrpn_nerfcomposite_backward: the same inputs and the cotangents g_rgb f32 [num_rays][3], g_depth, g_acc f32 [num_rays], g_w f32
+ *   [num_rays][s1 + s2] (merged order), each may be null (zero) -> draw1 f32 [num_rays][s1][4], draw2 f32 [num_rays][s2][4] (null
+ *   if s2 = 0), every entry written.  disp_map and z_vals are not differentiated.  The ray is walked twice and nothing of the
+ *   forward is kept: total = sum G_j w_j, then d alpha_i = G_i T_i - (total - sum_{j <= i} G_j w_j) / (1 - alpha_i + 1e-10).
+ * nrpn_nerfraylosses_forward: rgb_map, target_s f32 [num_rays][3] -> losses[0] = mean((rgb_map - target_s)^2) (img2mse, :837).
+ *   depth_map f32 [num_rays], z_vals and weights f32 [num_rays][num_samples], target_d f32 [num_rays][2] (mean, std), target_vd u8
+ *   [num_rays] (non-zero: the ray has a depth target) go together or target_d is null -> losses[1] = compute_depth_loss (:841; the
+ *   fork's): over the valid rays with |m - t| - s > 0 or s^2 < v, v = sum (z - m)^2 w + 1e-5, the sum of
+ *   (log v_c + (m - t)^2 / v_c) / 2, v_c = max(v, 1e-3), divided by num_rays; 0 without target_d.  losses f32 [2]; work:
+ *   nrpn_nerfcomposite_work_bytes bytes, 8-byte aligned.
+ * nrpn_nerfraylosses_backward: g_losses f32 [2] on the device, the cotangents of the two losses -> g_rgb f32 [num_rays][3] and, with
+ *   target_d, g_depth f32 [num_rays] and g_w f32 [num_rays][num_samples], every entry written.  The clamp of v passes its gradient
+ *   through unchanged, as torch's GaussianNLLLoss does; m inside v is differentiated.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t nrpn_nerfcomposite_work_bytes(int64_t num_rays, int s1, int s2);
+int nrpn_nerfcomposite_forward(const float *raw1, const float *z1, int z1_stride, int s1, const float *raw2, const float *z2, int s2,
+                               const float *noise1, const float *noise2, const float *rays_d, int64_t num_rays, float *rgb_map,
+                               float *depth_map, float *acc_map, float *disp_map, float *weights, float *z_vals, nrpn_stream_t stream);
+int nrpn_nerfcomposite_backward(const float *raw1, const float *z1, int z1_stride, int s1, const float *raw2, const float *z2, int s2,
+                                const float *noise1, const float *noise2, const float *rays_d, int64_t num_rays, const float *g_rgb,
+                                const float *g_depth, const float *g_acc, const float *g_w, float *draw1, float *draw2,
+                                nrpn_stream_t stream);
+int nrpn_nerfraylosses_forward(const float *rgb_map, const float *target_s, const float *depth_map, const float *z_vals,
+                               const float *weights, const float *target_d, const uint8_t *target_vd, int64_t num_rays, int num_samples,
+                               void *work, int64_t work_bytes, float *losses, nrpn_stream_t stream);
+int nrpn_nerfraylosses_backward(const float *rgb_map, const float *target_s, const float *depth_map, const float *z_vals,
+                                const float *weights, const float *target_d, const uint8_t *target_vd, int64_t num_rays,
+                                int num_samples, const float *g_losses, float *g_rgb, float *g_depth, float *g_w, nrpn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

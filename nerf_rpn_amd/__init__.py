@@ -5,11 +5,14 @@ through the C ABI in ``include/nerfrpn.h`` (``libnerfrpn_hip.so``).  No CPU fall
 """
 from . import lib  # noqa: F401
 
-__all__ = ["lib", "NeRF"]
+__all__ = ["lib", "NeRF", "render_rays_train", "training_loss"]
 
 
 def __getattr__(name):
     if name == "NeRF":          # the NeRF MLP module (nerf_model.py); imported on first use, with torch
         from .nerf_model import NeRF
         return NeRF
+    if name in ("render_rays_train", "training_loss"):        # one training step's ray stage (nerf_train.py)
+        from . import nerf_train
+        return getattr(nerf_train, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

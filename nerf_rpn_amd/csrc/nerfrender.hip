@@ -14,10 +14,13 @@
 // float32 with the reference's operation order and no contraction (they feed sinf(2^8 p)).  No atomics; a ray's result does not
 // depend on its chunk or on the tiles its samples fall into.
 #include "nerf_mlp.cuh"
+#include "nerf_ray.cuh"
 
 namespace {
 
 using namespace nerfmlp;
+using namespace nerfray;      // ray_norm, sample_weight, MergeCursor, merged_walk, RaySums, sizes_ok
+static_assert(kRayTile == kTile, "the size limits count the trunk's tiles");
 
 constexpr int kMaxViewsCh = 64;       // 3 + 6 multires_views <= 64 (multires_views <= 10)
 constexpr int kCtileLd = kHalf + 1;   // bank skew between the rays of a head tile
@@ -169,56 +172,6 @@ __global__ __launch_bounds__(kTile) void nerfrender_head_kernel(RayPoints rp, co
 }
 
 // ---- per-ray reductions, float64 ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ double ray_norm(const float *d) {
-  const double x = d[0], y = d[1], z = d[2];
-  return sqrt(x * x + y * y + z * z);
-}
-
-// compute_weights (:419-429) for one sample: alpha from relu(sigma) and dist; T is the transmittance before it and is advanced
-__device__ __forceinline__ double sample_weight(float sigma, double dist, double &T) {
-  const double alpha = 1.0 - exp(-fmax((double)sigma, 0.0) * dist);
-  const double w = alpha * T;
-  T *= 1.0 - alpha + 1e-10;
-  return w;
-}
-
-struct MergeCursor {      // the order of a ray's two non-decreasing sample lists: the smaller head first, list 1 on a tie
-  const float *za, *zb;
-  int S1, S2, ia, ib;
-  __device__ __forceinline__ bool next(int &i) {
-    const bool a = ib >= S2 || (ia < S1 && za[ia] <= zb[ib]);
-    i = a ? ia++ : ib++;
-    return a;
-  }
-};
-
-// One ray's samples in merged order: visit(from list 1?, index in that list, z, weight).  The weight is compute_weights' of the sample
-// in the merged list: dist to the next sample times |d| = nd, 1e10 after the last.  sa / sb: the lists' sigma, 4 floats apart; it is
-// loaded with its z, one sample ahead of its use: a thread's loop waits on these loads and on little else
-template <class Visit>
-__device__ __forceinline__ void merged_walk(const float *za, const float *sa, int S1, const float *zb, const float *sb, int S2,
-                                            double nd, Visit &&visit) {
-  MergeCursor m{za, zb, S1, S2, 0, 0};
-  const int S = S1 + S2;
-  int i;
-  bool a = m.next(i);
-  float zc = a ? za[i] : zb[i], sg = a ? sa[4 * i] : sb[4 * i];
-  double T = 1.0;
-  for (int s = 0; s < S; ++s) {
-    int in = i;
-    bool an = a;
-    float zn = zc, sn = sg;
-    if (s + 1 < S) {
-      an = m.next(in);
-      zn = an ? za[in] : zb[in];
-      sn = an ? sa[4 * in] : sb[4 * in];
-    }
-    const double dist = (s + 1 < S ? (double)zn - (double)zc : 1e10) * nd;
-    visit(a, i, zc, sample_weight(sg, dist, T));
-    a = an, i = in, zc = zn, sg = sn;
-  }
-}
-
 struct Bins {           // sample_3sigma (:471-478): edges and weights of the N - 1 bins between depth -+ 3 std, clamped to [near, far]
   double lo, hi, step, near, far;
   int N;
@@ -291,46 +244,25 @@ __global__ void nerfrender_composite_kernel(const float *__restrict__ raw1, cons
   const float *ra = raw1 + (int64_t)r * S1 * 4, *rb = raw2 + (int64_t)r * S2 * 4;
   const int S = S1 + S2;
   const int64_t gr = ray0 + r;
-  int s = 0;
-  double shift = 0.0, acc = 0.0, m1 = 0.0, m2 = 0.0, c0 = 0.0, c1 = 0.0, c2 = 0.0;
+  RaySums sums;
   merged_walk(za, ra + 3, S1, zb, rb + 3, S2, nd, [&](bool a, int i, float zc, double w) {
-    const float *rw = a ? ra + 4 * i : rb + 4 * i;
-    if (s == 0) shift = zc;
-    const double dz = (double)zc - shift;
-    acc += w;
-    m1 += w * dz;
-    m2 += w * dz * dz;
-    c0 += w / (1.0 + exp(-(double)rw[0]));
-    c1 += w / (1.0 + exp(-(double)rw[1]));
-    c2 += w / (1.0 + exp(-(double)rw[2]));
+    const int s = sums.s;
+    sums.add(a ? ra + 4 * i : rb + 4 * i, zc, w);
     if (o.z_vals) o.z_vals[gr * S + s] = zc;
     if (o.weights) o.weights[gr * S + s] = (float)w;
-    ++s;
   });
-  const double depth = shift * acc + m1;
-  // sum w (z - depth)^2 with z - depth = dz - e, e = depth - shift
-  const double e = depth - shift;
-  const double var = m2 - 2.0 * e * m1 + e * e * acc;
-  const double q = depth / acc;
-  o.rgb[gr * 3] = (float)c0;
-  o.rgb[gr * 3 + 1] = (float)c1;
-  o.rgb[gr * 3 + 2] = (float)c2;
+  const double depth = sums.depth();
+  o.rgb[gr * 3] = (float)sums.c0;
+  o.rgb[gr * 3 + 1] = (float)sums.c1;
+  o.rgb[gr * 3 + 2] = (float)sums.c2;
   o.depth[gr] = (float)depth;
-  o.acc[gr] = (float)acc;
-  o.disp[gr] = (float)(1.0 / (q < 1e-10 ? 1e-10 : q));          // a NaN quotient (acc 0) stays NaN, as torch.max keeps it
-  o.depth_std[gr] = (float)sqrt(fmin(fmax(var, 0.0), 1.0));
+  o.acc[gr] = (float)sums.acc;
+  o.disp[gr] = (float)sums.disp();
+  o.depth_std[gr] = (float)sqrt(fmin(fmax(sums.var(), 0.0), 1.0));
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
 constexpr int64_t kMaxRenderRays = (int64_t)1 << 40, kMaxCamoptRays = (int64_t)1 << 31;
-
-// The limits every size query and entry point shares: num_rays rays (below max_rays) in chunks of ``chunk`` with s1 + s2 samples per
-// ray; the points of a chunk's pass, rounded up to tiles, are counted in an int
-bool sizes_ok(int64_t num_rays, int64_t max_rays, int64_t chunk, int s1, int s2) {
-  if (num_rays < 1 || num_rays >= max_rays || chunk < 1 || s1 < 1 || s2 < 0 || s1 > 65536 || s2 > 65536) return false;
-  const int64_t n = chunk < num_rays ? chunk : num_rays;
-  return n < ((int64_t)1 << 31) && n * (s1 > s2 ? s1 : s2) < ((int64_t)1 << 31) - kTile;
-}
 
 int check_model(const char *who, int multires, int multires_views, int cam_ch) {
   NRPN_REQUIRE(multires >= 0 && 3 + 6 * multires <= kEnc, "%s: multires %d does not fit %d encoding columns", who, multires, kEnc);

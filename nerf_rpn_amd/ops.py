@@ -3034,3 +3034,175 @@ def nerf_query(params, cfg, pts, viewdirs, embedded_cam=None, bb_center=(0., 0.,
     if chunk < 1:
         raise lib.NrpnError(f"nerf_query: chunk {chunk}")
     return NerfQueryFn.apply(pts, viewdirs, cam, cfg, _nerf_bounds(bb_center, bb_scale), chunk, *(sd[k] for k in NERF_QUERY_PARAMS))
+
+
+# ======================================================================================================================
+# the ray stage of NeRF training as differentiable operations  [f10]
+# ======================================================================================================================
+class NerfCompositeFn(torch.autograd.Function):
+    """forward_with_additonal_samples' merge (run_nerf.py:504-512) and raw2outputs (:437-469) with their backward on the GPU
+    (csrc/nerfcomposite.hip).  Nothing but the inputs is kept for the backward: it walks every ray again."""
+
+    @staticmethod
+    def forward(ctx, raw1, raw2, z1, z2, rays_d, noise1, noise2):
+        R, S1 = int(raw1.shape[0]), int(raw1.shape[1])
+        S2 = 0 if raw2 is None else int(raw2.shape[1])
+        dev = raw1.device
+
+        def new(*shape):
+            return torch.empty(shape, dtype=torch.float32, device=dev)
+        rgb, depth, acc, disp, weights, z_vals = new(R, 3), new(R), new(R), new(R), new(R, S1 + S2), new(R, S1 + S2)
+        ctx.lists = (_p(raw1), _p(z1), 0 if z1.dim() == 1 else S1, S1, _p(raw2) if S2 else None, _p(z2) if S2 else None, S2,
+                     None if noise1 is None else _p(noise1), None if noise2 is None or not S2 else _p(noise2), _p(rays_d), R)
+        call("nerfcomposite_forward", *ctx.lists, _p(rgb), _p(depth), _p(acc), _p(disp), _p(weights), _p(z_vals), _s())
+        ctx.keep = (raw1, raw2, z1, z2, rays_d, noise1, noise2)       # the pointers of ctx.lists stay valid with them
+        ctx.set_materialize_grads(False)      # an output nobody differentiates sends None: a null cotangent
+        ctx.mark_non_differentiable(disp, z_vals)
+        return rgb, disp, acc, weights, depth, z_vals
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_rgb, g_disp, g_acc, g_w, g_depth, g_z):
+        raw1, raw2 = ctx.keep[:2]
+        cot = [None if g is None else g.to(torch.float32).contiguous() for g in (g_rgb, g_depth, g_acc, g_w)]
+        draw1 = torch.empty_like(raw1)
+        draw2 = None if raw2 is None else torch.empty_like(raw2)
+        call("nerfcomposite_backward", *ctx.lists, *(None if g is None else _p(g) for g in cot), _p(draw1),
+             None if draw2 is None else _p(draw2), _s())
+        return draw1, draw2, None, None, None, None, None
+
+
+def _f32_device(who, name, x, dev, shape):
+    """x as a contiguous float32 tensor on dev (a tensor that requires grad stays in the graph); shape: its expected shape."""
+    t = x if isinstance(x, torch.Tensor) else torch.as_tensor(x, dtype=torch.float32)
+    t = t.to(device=dev, dtype=torch.float32).contiguous()
+    if tuple(t.shape) != tuple(shape):
+        raise lib.NrpnError(f"{who} expects {name} {list(shape)}, got {list(t.shape)}")
+    return t
+
+
+def nerf_composite(raw1, z1, rays_d, raw2=None, z2=None, noise=None, check=False):
+    """raw2outputs (run_nerf.py:437-469) on the merged samples of forward_with_additonal_samples (:504-512), differentiable with
+    respect to raw1 and raw2.
+
+    raw1 [R, S1, 4] float32 at z1 [S1] (every ray's) or [R, S1]; raw2 [R, S2, 4] at z2 [R, S2], both or neither; rays_d [R, 3].  Each
+    list is non-decreasing along a ray; the lists are merged, list 1 first on a tie (where the lists share no value this is the
+    reference's sort of the concatenation).  check=True verifies the order and raises NrpnError on an unsorted list; it
+    synchronises, so it is off by default.  noise [R, S1 + S2]: added to sigma before the relu (raw_noise_std's, :426), columns
+    [:S1] for list 1 and [S1:] for list 2 in each list's own order.
+
+    Returns (rgb_map [R, 3], disp_map [R], acc_map [R], weights [R, S1 + S2], depth_map [R], z_vals [R, S1 + S2]): raw2outputs'
+    tuple with the merged z_vals appended, float32 on the device.  disp_map and z_vals are not differentiable, and z1, z2, rays_d
+    or noise that require grad raise NotImplementedError (no entry point of the reference differentiates them).  Without noise the
+    outputs are nerf_render's for the same raw, bit for bit.  Two calls are bit-equal, forward and backward."""
+    who = "nerf_composite"
+    if not torch.cuda.is_available():
+        raise lib.NrpnError(f"{who} needs a gfx950 device (the product path has no CPU fallback)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    for name, x in (("z1", z1), ("z2", z2), ("rays_d", rays_d), ("noise", noise)):
+        if isinstance(x, torch.Tensor) and x.requires_grad:
+            raise NotImplementedError(f"{who}: {name} requires grad; the composite is differentiable in raw1 and raw2 only")
+    if (raw2 is None) != (z2 is None):
+        raise lib.NrpnError(f"{who}: raw2 and z2 go together")
+    if not isinstance(raw1, torch.Tensor) or raw1.dim() != 3 or raw1.shape[2] != 4 or raw1.shape[0] < 1 or raw1.shape[1] < 1:
+        raise lib.NrpnError(f"{who} expects raw1 [R, S1, 4], got {tuple(getattr(raw1, 'shape', ()))}")
+    R, S1 = int(raw1.shape[0]), int(raw1.shape[1])
+    raw1 = _f32_device(who, "raw1", raw1, dev, (R, S1, 4))
+    z1 = torch.as_tensor(z1, dtype=torch.float32)
+    z1 = _f32_device(who, "z1", z1, dev, (S1,) if z1.dim() == 1 else (R, S1))
+    rays_d = _f32_device(who, "rays_d", rays_d, dev, (R, 3))
+    S2 = 0
+    if raw2 is not None:
+        if not isinstance(raw2, torch.Tensor) or raw2.dim() != 3 or raw2.shape[1] < 1:
+            raise lib.NrpnError(f"{who} expects raw2 [R, S2, 4], got {tuple(getattr(raw2, 'shape', ()))}")
+        S2 = int(raw2.shape[1])
+        raw2 = _f32_device(who, "raw2", raw2, dev, (R, S2, 4))
+        z2 = _f32_device(who, "z2", z2, dev, (R, S2))
+    if lib.query("nerfcomposite_work_bytes", R, S1, S2) < 0:
+        raise lib.NrpnError(f"{who}: {R} rays with {S1} + {S2} samples are outside the supported range")
+    noise1 = noise2 = None
+    if noise is not None:
+        noise = _f32_device(who, "noise", noise, dev, (R, S1 + S2))
+        noise1, noise2 = noise[:, :S1].contiguous(), noise[:, S1:].contiguous()
+    if check:
+        for name, z in (("z1", z1), ("z2", z2)):
+            if z is not None and z.shape[-1] > 1 and not bool((z[..., 1:] >= z[..., :-1]).all()):
+                raise lib.NrpnError(f"{who}: {name} is not non-decreasing along every ray")
+    return NerfCompositeFn.apply(raw1, raw2, z1, z2, rays_d, noise1, noise2)
+
+
+class NerfRayLossesFn(torch.autograd.Function):
+    """img2mse (run_nerf.py:837) and compute_depth_loss (:841) with their backward on the GPU (csrc/nerfcomposite.hip)."""
+
+    @staticmethod
+    def forward(ctx, rgb_map, depth_map, weights, target_s, z_vals, target_d, target_vd):
+        R = int(rgb_map.shape[0])
+        S = 1 if target_d is None else int(weights.shape[1])
+        dev = rgb_map.device
+        nbytes = lib.query("nerfcomposite_work_bytes", R, S - S // 2, S // 2)      # S = S1 + S2 of a composite: two lists of up to 65536
+        if nbytes < 0:
+            raise lib.NrpnError(f"nerf_ray_losses: {R} rays with {S} samples are outside the supported range")
+        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        losses = torch.empty(2, dtype=torch.float32, device=dev)
+        if target_d is None:
+            ctx.args = (_p(rgb_map), _p(target_s), None, None, None, None, None, R, S)
+        else:
+            ctx.args = (_p(rgb_map), _p(target_s), _p(depth_map), _p(z_vals), _p(weights), _p(target_d), _p(target_vd), R, S)
+        call("nerfraylosses_forward", *ctx.args, _p(work), nbytes, _p(losses), _s())
+        ctx.keep = (rgb_map, target_s, depth_map, z_vals, weights, target_d, target_vd)      # the pointers of ctx.args stay valid with them
+        ctx.set_materialize_grads(False)
+        return losses[0], losses[1]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_img, g_depth_loss):
+        rgb_map, _, depth_map, _, weights, target_d, _ = ctx.keep
+        zero = torch.zeros((), dtype=torch.float32, device=rgb_map.device)
+        g = torch.stack([zero if x is None else x.to(torch.float32).reshape(()) for x in (g_img, g_depth_loss)])
+        g_rgb = torch.empty_like(rgb_map)
+        if target_d is None:
+            call("nerfraylosses_backward", *ctx.args, _p(g), _p(g_rgb), None, None, _s())
+            return g_rgb, None, None, None, None, None, None
+        g_depth, g_w = torch.empty_like(depth_map), torch.empty_like(weights)
+        call("nerfraylosses_backward", *ctx.args, _p(g), _p(g_rgb), _p(g_depth), _p(g_w), _s())
+        return g_rgb, g_depth, g_w, None, None, None, None
+
+
+def nerf_ray_losses(rgb_map, target_s, depth_map=None, z_vals=None, weights=None, target_d=None, target_vd=None):
+    """The losses of a training step (run_nerf.py:837-842) on the GPU, differentiable with respect to rgb_map, depth_map and weights
+     -> (img_loss, depth_loss), float32 scalars on the device.
+
+    img_loss = mean((rgb_map - target_s)^2) over the 3 R values (img2mse).  depth_loss = compute_depth_loss(depth_map, z_vals,
+    weights, target_d, target_vd): target_d [R, 2] holds the target depth and its standard deviation, target_vd [R] (bool) the rays
+    that have one; over those rays with |m - t| - s > 0 or s^2 < v, where m = depth_map and v = sum (z - m)^2 w + 1e-5, the Gaussian
+    negative log-likelihood (log v_c + (m - t)^2 / v_c) / 2 with v_c = max(v, 1e-3), summed and divided by R.  With no valid or no
+    applied ray it is exactly 0 and so is every gradient.  target_d=None gives img_loss alone (depth_loss 0, detached from the depth
+    inputs).  The caller applies depth_loss_weight (:842).  z_vals, the targets and target_vd are not differentiated."""
+    who = "nerf_ray_losses"
+    if not torch.cuda.is_available():
+        raise lib.NrpnError(f"{who} needs a gfx950 device (the product path has no CPU fallback)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    for name, x in (("target_s", target_s), ("z_vals", z_vals), ("target_d", target_d)):
+        if isinstance(x, torch.Tensor) and x.requires_grad:
+            raise NotImplementedError(f"{who}: {name} requires grad; the losses are differentiable in rgb_map, depth_map and weights only")
+    if not isinstance(rgb_map, torch.Tensor) or rgb_map.dim() != 2 or rgb_map.shape[1] != 3 or rgb_map.shape[0] < 1:
+        raise lib.NrpnError(f"{who} expects rgb_map [R, 3], got {tuple(getattr(rgb_map, 'shape', ()))}")
+    R = int(rgb_map.shape[0])
+    rgb_map = _f32_device(who, "rgb_map", rgb_map, dev, (R, 3))
+    target_s = _f32_device(who, "target_s", target_s, dev, (R, 3))
+    if target_d is None:
+        return NerfRayLossesFn.apply(rgb_map, None, None, target_s, None, None, None)
+    if depth_map is None or z_vals is None or weights is None or target_vd is None:
+        raise lib.NrpnError(f"{who}: target_d goes with depth_map, z_vals, weights and target_vd")
+    if not isinstance(weights, torch.Tensor) or weights.dim() != 2 or weights.shape[0] != R or weights.shape[1] < 1:
+        raise lib.NrpnError(f"{who} expects weights [{R}, S], got {tuple(getattr(weights, 'shape', ()))}")
+    S = int(weights.shape[1])
+    weights = _f32_device(who, "weights", weights, dev, (R, S))
+    depth_map = _f32_device(who, "depth_map", depth_map, dev, (R,))
+    z_vals = _f32_device(who, "z_vals", z_vals, dev, (R, S))
+    target_d = _f32_device(who, "target_d", target_d, dev, (R, 2))
+    target_vd = torch.as_tensor(target_vd).to(dev)
+    if tuple(target_vd.shape) != (R,):
+        raise lib.NrpnError(f"{who} expects target_vd [{R}], got {list(target_vd.shape)}")
+    target_vd = (target_vd != 0).to(torch.uint8).contiguous()
+    return NerfRayLossesFn.apply(rgb_map, depth_map, weights, target_s, z_vals, target_d, target_vd)
