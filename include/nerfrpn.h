@@ -532,7 +532,9 @@ int nrpn_fcos_decode_f32(const int32_t *idx, const float *score, int64_t count, 
  *   rois rows = (batch index, cx, cy, cz, w, l, h, theta in DEGREES); sampling_ratio <= 0: ceil(roi extent / pooled extent) samples.
  * Here: channels-last feature map feat [N][X][Y][Z][C] (dtype), out / grad_out [R][pw][pl][ph][C] (dtype), C % 4 == 0.
  * The backward accumulates through 64-bit fixed-point integer atomics in `workspace` (nrpn_roi_align_rotated_3d_bwd_workspace_bytes,
- * zeroed by the call) and converts once: deterministic, unlike the reference's fp32 atomicAdd.
+ * zeroed by the call) and converts once: deterministic, unlike the reference's fp32 atomicAdd.  A finite contribution is clamped to
+ * +-2^18; a contribution that is not finite (NaN / +-Inf in grad_out) raises the flag word at the end of the workspace and the WHOLE
+ * grad_in comes out NaN (nrpn_roipool_*_bwd likewise).
  * ---------------------------------------------------------------------------------------------- */
 int nrpn_roi_align_rotated_3d_fwd(const void *feat, const float *rois, int num_rois, int n, int x, int y, int z, int c,
                                   float spatial_scale, int pw, int pl, int ph, int sampling_ratio, void *out, int dtype,

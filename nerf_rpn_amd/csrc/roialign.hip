@@ -95,17 +95,21 @@ __device__ __forceinline__ void sample_xyz(const Roi &o, int pw, int pl, int ph,
 }
 
 // 2^44 fixed point in a signed 64-bit accumulator: contributions of 1e-9 (a mean loss over ~1000 RoIs spread over 8..64 samples) keep
-// 4+ significant digits, values down to 6e-14 survive, and the sum may reach +-2^19 before it would wrap; a single contribution is
-// clamped to +-2^18 so that one outlier cannot wrap the accumulator on its own.
+// 4+ significant digits, values down to 6e-14 survive, and the sum may reach +-2^19 before it would wrap; a single FINITE contribution
+// is clamped to +-2^18 so that one outlier cannot wrap the accumulator on its own.  A contribution that is not finite (NaN or +-Inf in
+// grad_out, inf * 0 at a zero-weight tap) has no fixed-point value -- fmaxf(NaN, a) is a, so the clamp alone would turn it into -2^18:
+// it is not added but raises the flag word that follows the accumulators in the workspace, and the conversion then writes NaN to the
+// WHOLE gradient (what autograd would have left non-finite never comes out as a finite number; still bit-identical from run to run).
 constexpr double kFix = 17592186044416.0;     // 2^44
 constexpr float kFixClamp = 262144.f;         // 2^18
+__device__ __forceinline__ bool fix_finite(float g) { return fabsf(g) <= 3.402823466e38f; }      // false for NaN and +-Inf
 
 // MODE 0: forward  out[bin][c] = mean of samples;  MODE 1: backward scatter of grad_out[bin][c] * w / count (fixed point)
 template <typename T, int MODE>
 __global__ void __launch_bounds__(64) roi_align_kernel(const T *__restrict__ feat, const float *__restrict__ rois, int width, int length, int height,
                                                        int channels, float scale, int pw_n, int pl_n, int ph_n, int sampling_ratio,
                                                        T *__restrict__ out, const T *__restrict__ grad_out, long long *__restrict__ ws,
-                                                       int nbatch) {
+                                                       int nbatch, unsigned long long *__restrict__ flag) {
   const int bins = pw_n * pl_n * ph_n;
   const int bin = blockIdx.x % bins;
   const long long n = blockIdx.x / bins;
@@ -146,7 +150,9 @@ __global__ void __launch_bounds__(64) roi_align_kernel(const T *__restrict__ fea
               long long *dst = ws + (base + tap_voxel(t, k, length, height)) * channels + cg;
 #pragma unroll
               for (int q = 0; q < 4; ++q) {
-                const float g = fminf(fmaxf(top[q] * t.w[k] / o.count, -kFixClamp), kFixClamp);
+                float g = top[q] * t.w[k] / o.count;
+                if (!fix_finite(g)) { atomicOr(flag, 1ull); continue; }
+                g = fminf(fmaxf(g, -kFixClamp), kFixClamp);
                 if (g != 0.f) atomicAdd(reinterpret_cast<unsigned long long *>(dst + q), (unsigned long long)__double2ll_rn((double)g * kFix));
               }
             }
@@ -162,8 +168,9 @@ __global__ void __launch_bounds__(64) roi_align_kernel(const T *__restrict__ fea
 
 template <typename T>
 __global__ void fixed_to_float_kernel(const long long *__restrict__ ws, T *__restrict__ dst, long long count) {
+  const bool poisoned = ws[count] != 0;         // the flag word: some contribution was not finite
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (long long)gridDim.x * blockDim.x)
-    elem<T>::st(dst + i, (float)((double)ws[i] * (1.0 / kFix)));
+    elem<T>::st(dst + i, poisoned ? __builtin_nanf("") : (float)((double)ws[i] * (1.0 / kFix)));
 }
 
 int check(int num_rois, int n, int x, int y, int z, int c, int pw, int pl, int ph, int dtype) {
@@ -184,15 +191,17 @@ extern "C" int nrpn_roi_align_rotated_3d_fwd(const void *feat, const float *rois
   const dim3 grid((unsigned)(num_rois * pw * pl * ph));
   if (dtype == NRPN_F32)
     hipLaunchKernelGGL((roi_align_kernel<float, 0>), grid, dim3(64), 0, as_stream(stream), (const float *)feat, rois, x, y, z, c, spatial_scale, pw,
-                       pl, ph, sampling_ratio, (float *)out, (const float *)nullptr, (long long *)nullptr, n);
+                       pl, ph, sampling_ratio, (float *)out, (const float *)nullptr, (long long *)nullptr, n, (unsigned long long *)nullptr);
   else
     hipLaunchKernelGGL((roi_align_kernel<bf16s, 0>), grid, dim3(64), 0, as_stream(stream), (const bf16s *)feat, rois, x, y, z, c, spatial_scale,
-                       pw, pl, ph, sampling_ratio, (bf16s *)out, (const bf16s *)nullptr, (long long *)nullptr, n);
+                       pw, pl, ph, sampling_ratio, (bf16s *)out, (const bf16s *)nullptr, (long long *)nullptr, n, (unsigned long long *)nullptr);
   NRPN_LAUNCH_CHECK("roi_align_rotated_3d_fwd");
   return NRPN_OK;
 }
 
-extern "C" size_t nrpn_roi_align_rotated_3d_bwd_workspace_bytes(int n, int x, int y, int z, int c) { return (size_t)n * x * y * z * c * 8; }
+extern "C" size_t nrpn_roi_align_rotated_3d_bwd_workspace_bytes(int n, int x, int y, int z, int c) {
+  return (size_t)n * x * y * z * c * 8 + 8;      // one 64-bit accumulator per element + the non-finite flag word
+}
 
 extern "C" int nrpn_roi_align_rotated_3d_bwd(const void *grad_out, const float *rois, int num_rois, int n, int x, int y, int z, int c,
                                              float spatial_scale, int pw, int pl, int ph, int sampling_ratio, void *grad_in, void *workspace,
@@ -201,15 +210,15 @@ extern "C" int nrpn_roi_align_rotated_3d_bwd(const void *grad_out, const float *
   NRPN_REQUIRE(grad_in && workspace && (num_rois == 0 || (grad_out && rois)), "roi_align_rotated_3d_bwd: null pointer");
   hipStream_t st = as_stream(stream);
   const long long count = (long long)n * x * y * z * c;
-  NRPN_HIP(hipMemsetAsync(workspace, 0, (size_t)count * 8, st));
+  NRPN_HIP(hipMemsetAsync(workspace, 0, (size_t)count * 8 + 8, st));
   if (num_rois > 0) {
     const dim3 grid((unsigned)(num_rois * pw * pl * ph));
     if (dtype == NRPN_F32)
       hipLaunchKernelGGL((roi_align_kernel<float, 1>), grid, dim3(64), 0, st, (const float *)nullptr, rois, x, y, z, c, spatial_scale, pw, pl, ph,
-                         sampling_ratio, (float *)nullptr, (const float *)grad_out, (long long *)workspace, n);
+                         sampling_ratio, (float *)nullptr, (const float *)grad_out, (long long *)workspace, n, (unsigned long long *)workspace + count);
     else
       hipLaunchKernelGGL((roi_align_kernel<bf16s, 1>), grid, dim3(64), 0, st, (const bf16s *)nullptr, rois, x, y, z, c, spatial_scale, pw, pl, ph,
-                         sampling_ratio, (bf16s *)nullptr, (const bf16s *)grad_out, (long long *)workspace, n);
+                         sampling_ratio, (bf16s *)nullptr, (const bf16s *)grad_out, (long long *)workspace, n, (unsigned long long *)workspace + count);
   }
   const int blocks = (int)min((long long)8192, (count + 255) / 256);
   if (dtype == NRPN_F32) hipLaunchKernelGGL(fixed_to_float_kernel<float>, dim3(blocks), dim3(256), 0, st, (const long long *)workspace, (float *)grad_in, count);

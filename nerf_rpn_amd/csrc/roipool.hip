@@ -20,7 +20,12 @@ typedef unsigned short bf16s;
 constexpr double kFix = 17592186044416.0;     // 2^44
 constexpr float kFixClamp = 262144.f;         // 2^18
 
-__device__ __forceinline__ void fix_add(long long *dst, float g) {
+// A contribution that is not finite (NaN / +-Inf in the upstream gradient, inf * 0 at a zero weight) is not added -- fmaxf(NaN, a) is a: the
+// clamp alone would make it -2^18 -- but raises the flag word behind the accumulators; the conversion then writes NaN to the whole gradient
+// (csrc/roialign.hip, at kFix).
+__device__ __forceinline__ bool fix_finite(float g) { return fabsf(g) <= 3.402823466e38f; }      // false for NaN and +-Inf
+__device__ __forceinline__ void fix_add(long long *dst, float g, unsigned long long *flag) {
+  if (!fix_finite(g)) { atomicOr(flag, 1ull); return; }
   g = fminf(fmaxf(g, -kFixClamp), kFixClamp);
   if (g != 0.f) atomicAdd(reinterpret_cast<unsigned long long *>(dst), (unsigned long long)__double2ll_rn((double)g * kFix));
 }
@@ -34,7 +39,7 @@ struct PoolGeom { int o0, o1, o2; };
 template <typename T, int MODE>
 __global__ void roipool_aabb_kernel(const T *__restrict__ feat, int Y, int Z, int C, const int *__restrict__ crop, const int *__restrict__ level_of,
                                     int level, PoolGeom g, float *__restrict__ out, int *__restrict__ arg, const float *__restrict__ dout,
-                                    long long *__restrict__ ws) {
+                                    long long *__restrict__ ws, unsigned long long *__restrict__ flag) {
   const int bins = g.o0 * g.o1 * g.o2;
   const long long r = blockIdx.x / bins;
   if (level_of[r] != level) return;
@@ -46,7 +51,7 @@ __global__ void roipool_aabb_kernel(const T *__restrict__ feat, int Y, int Z, in
   if (MODE == 1) {
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
       const int a = arg[orow + c];
-      if (a >= 0) fix_add(ws + (long long)a * C + c, dout[orow + c]);
+      if (a >= 0) fix_add(ws + (long long)a * C + c, dout[orow + c], flag);
     }
     return;
   }
@@ -119,10 +124,11 @@ __device__ __forceinline__ float obb_blend(const T *__restrict__ feat, const Cor
   for (int n = 0; n < 8; ++n) acc = acc + elem<T>::ld(feat + (long long)q.vox[n] * C + c) * q.wt[n];
   return acc / 8.f;
 }
-__device__ __forceinline__ void obb_scatter(long long *__restrict__ ws, const Corners &q, int C, int c, float g) {
+__device__ __forceinline__ void obb_scatter(long long *__restrict__ ws, const Corners &q, int C, int c, float g, unsigned long long *flag) {
+  if (!fix_finite(g)) { atomicOr(flag, 1ull); return; }      // also at a point outside the map: the reference multiplies by its 0 mask, NaN * 0
   if (!q.inside || g == 0.f) return;
 #pragma unroll
-  for (int n = 0; n < 8; ++n) fix_add(ws + (long long)q.vox[n] * C + c, g * q.wt[n] / 8.f);
+  for (int n = 0; n < 8; ++n) fix_add(ws + (long long)q.vox[n] * C + c, g * q.wt[n] / 8.f, flag);
 }
 // torch's aligned-corner linear resize of an axis: source coordinate, lower tap, weights (upsample_trilinear3d, align_corners=True)
 __device__ __forceinline__ void lin_tap(int dst, int in, int out, int &i0, int &i1, float &l0, float &l1) {
@@ -138,7 +144,7 @@ __device__ __forceinline__ void lin_tap(int dst, int in, int out, int &i0, int &
 template <typename T, int KIND, int MODE>
 __global__ void roipool_obb_kernel(const T *__restrict__ feat, int X, int Y, int Z, int C, const float *__restrict__ rois,
                                    const int *__restrict__ level_of, int level, float s, PoolGeom g, float *__restrict__ out,
-                                   int *__restrict__ arg, const float *__restrict__ dout, long long *__restrict__ ws) {
+                                   int *__restrict__ arg, const float *__restrict__ dout, long long *__restrict__ ws, unsigned long long *__restrict__ flag) {
   const int bins = g.o0 * g.o1 * g.o2;
   const long long r = blockIdx.x / bins;
   if (level_of[r] != level) return;
@@ -155,7 +161,7 @@ __global__ void roipool_obb_kernel(const T *__restrict__ feat, int X, int Y, int
         const int k = a % o.g2, j = (a / o.g2) % o.g1, i = a / (o.g2 * o.g1);
         float x, y, z;
         obb_point(o, i, j, k, x, y, z);
-        obb_scatter(ws, obb_corners(x, y, z, X, Y, Z), C, c, dout[orow + c]);
+        obb_scatter(ws, obb_corners(x, y, z, X, Y, Z), C, c, dout[orow + c], flag);
       }
       return;
     }
@@ -206,7 +212,7 @@ __global__ void roipool_obb_kernel(const T *__restrict__ feat, int X, int Y, int
       } else {
         const float gout = dout[orow + c];
 #pragma unroll
-        for (int n = 0; n < 8; ++n) obb_scatter(ws, q[n], C, c, gout * tw[n]);
+        for (int n = 0; n < 8; ++n) obb_scatter(ws, q[n], C, c, gout * tw[n], flag);
       }
     }
   }
@@ -214,8 +220,9 @@ __global__ void roipool_obb_kernel(const T *__restrict__ feat, int X, int Y, int
 
 template <typename T>
 __global__ void roipool_fixed_to_float_kernel(const long long *__restrict__ ws, T *__restrict__ dst, long long count) {
+  const bool poisoned = ws[count] != 0;         // the flag word: some contribution was not finite
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (long long)gridDim.x * blockDim.x)
-    elem<T>::st(dst + i, (float)((double)ws[i] * (1.0 / kFix)));
+    elem<T>::st(dst + i, poisoned ? __builtin_nanf("") : (float)((double)ws[i] * (1.0 / kFix)));
 }
 
 int check(const char *who, int num_rois, int x, int y, int z, int c, int o0, int o1, int o2, int dtype) {
@@ -228,7 +235,9 @@ int check(const char *who, int num_rois, int x, int y, int z, int c, int o0, int
 static inline int lanes_for(int c) { return c >= 256 ? 256 : (c >= 128 ? 128 : 64); }
 }  // namespace
 
-extern "C" size_t nrpn_roipool_bwd_workspace_bytes(int x, int y, int z, int c) { return (size_t)x * y * z * c * 8; }
+extern "C" size_t nrpn_roipool_bwd_workspace_bytes(int x, int y, int z, int c) {
+  return (size_t)x * y * z * c * 8 + 8;          // one 64-bit accumulator per element + the non-finite flag word
+}
 
 extern "C" int nrpn_roipool_aabb_fwd(const void *feat, int x, int y, int z, int c, const int32_t *crop, const int32_t *level_of, int level, int num_rois,
                                      int o0, int o1, int o2, float *out, int32_t *argmax, int dtype, nrpn_stream_t stream) {
@@ -239,10 +248,10 @@ extern "C" int nrpn_roipool_aabb_fwd(const void *feat, int x, int y, int z, int 
   const PoolGeom g{o0, o1, o2};
   if (dtype == NRPN_F32)
     hipLaunchKernelGGL((roipool_aabb_kernel<float, 0>), grid, dim3(lanes_for(c)), 0, as_stream(stream), (const float *)feat, y, z, c, crop, level_of, level, g,
-                       out, argmax, (const float *)nullptr, (long long *)nullptr);
+                       out, argmax, (const float *)nullptr, (long long *)nullptr, (unsigned long long *)nullptr);
   else
     hipLaunchKernelGGL((roipool_aabb_kernel<bf16s, 0>), grid, dim3(lanes_for(c)), 0, as_stream(stream), (const bf16s *)feat, y, z, c, crop, level_of, level, g,
-                       out, argmax, (const float *)nullptr, (long long *)nullptr);
+                       out, argmax, (const float *)nullptr, (long long *)nullptr, (unsigned long long *)nullptr);
   NRPN_LAUNCH_CHECK("roipool_aabb_fwd");
   return NRPN_OK;
 }
@@ -253,11 +262,11 @@ extern "C" int nrpn_roipool_aabb_bwd(const float *dout, const int32_t *argmax, c
   NRPN_REQUIRE(dfeat && workspace && (num_rois == 0 || (dout && argmax && crop && level_of)), "roipool_aabb_bwd: null pointer");
   hipStream_t st = as_stream(stream);
   const long long count = (long long)x * y * z * c;
-  NRPN_HIP(hipMemsetAsync(workspace, 0, (size_t)count * 8, st));
+  NRPN_HIP(hipMemsetAsync(workspace, 0, (size_t)count * 8 + 8, st));
   if (num_rois > 0) {
     const PoolGeom g{o0, o1, o2};
     hipLaunchKernelGGL((roipool_aabb_kernel<float, 1>), dim3((unsigned)(num_rois * o0 * o1 * o2)), dim3(lanes_for(c)), 0, st, (const float *)nullptr, y, z, c,
-                       crop, level_of, level, g, (float *)nullptr, const_cast<int32_t *>(argmax), dout, (long long *)workspace);
+                       crop, level_of, level, g, (float *)nullptr, const_cast<int32_t *>(argmax), dout, (long long *)workspace, (unsigned long long *)workspace + count);
   }
   const int blocks = (int)min((long long)8192, (count + 255) / 256);
   if (dtype == NRPN_F32) hipLaunchKernelGGL(roipool_fixed_to_float_kernel<float>, dim3(blocks), dim3(256), 0, st, (const long long *)workspace, (float *)dfeat, count);
@@ -266,9 +275,9 @@ extern "C" int nrpn_roipool_aabb_bwd(const float *dout, const int32_t *argmax, c
   return NRPN_OK;
 }
 
-#define NRPN_OBB_LAUNCH(T_, KIND_, MODE_, feat_, out_, arg_, dout_, ws_)                                                                                 \
+#define NRPN_OBB_LAUNCH(T_, KIND_, MODE_, feat_, out_, arg_, dout_, ws_, flag_)                                                                                 \
   hipLaunchKernelGGL((roipool_obb_kernel<T_, KIND_, MODE_>), grid, dim3(lanes_for(c)), 0, st, (const T_ *)(feat_), x, y, z, c, rois, level_of, level, scale, \
-                     g, out_, arg_, dout_, ws_)
+                     g, out_, arg_, dout_, ws_, flag_)
 
 extern "C" int nrpn_roipool_obb_fwd(const void *feat, int x, int y, int z, int c, const float *rois, const int32_t *level_of, int level, int num_rois,
                                     float scale, int interpolation, int o0, int o1, int o2, float *out, int32_t *argmax, int dtype, nrpn_stream_t stream) {
@@ -279,11 +288,11 @@ extern "C" int nrpn_roipool_obb_fwd(const void *feat, int x, int y, int z, int c
   const dim3 grid((unsigned)(num_rois * o0 * o1 * o2));
   const PoolGeom g{o0, o1, o2};
   if (dtype == NRPN_F32) {
-    if (interpolation) NRPN_OBB_LAUNCH(float, 1, 0, feat, out, argmax, (const float *)nullptr, (long long *)nullptr);
-    else NRPN_OBB_LAUNCH(float, 0, 0, feat, out, argmax, (const float *)nullptr, (long long *)nullptr);
+    if (interpolation) NRPN_OBB_LAUNCH(float, 1, 0, feat, out, argmax, (const float *)nullptr, (long long *)nullptr, (unsigned long long *)nullptr);
+    else NRPN_OBB_LAUNCH(float, 0, 0, feat, out, argmax, (const float *)nullptr, (long long *)nullptr, (unsigned long long *)nullptr);
   } else {
-    if (interpolation) NRPN_OBB_LAUNCH(bf16s, 1, 0, feat, out, argmax, (const float *)nullptr, (long long *)nullptr);
-    else NRPN_OBB_LAUNCH(bf16s, 0, 0, feat, out, argmax, (const float *)nullptr, (long long *)nullptr);
+    if (interpolation) NRPN_OBB_LAUNCH(bf16s, 1, 0, feat, out, argmax, (const float *)nullptr, (long long *)nullptr, (unsigned long long *)nullptr);
+    else NRPN_OBB_LAUNCH(bf16s, 0, 0, feat, out, argmax, (const float *)nullptr, (long long *)nullptr, (unsigned long long *)nullptr);
   }
   NRPN_LAUNCH_CHECK("roipool_obb_fwd");
   return NRPN_OK;
@@ -297,7 +306,7 @@ extern "C" int nrpn_roipool_obb_bwd(const float *dout, const int32_t *argmax, co
                "roipool_obb_bwd: null pointer / bad scale");
   hipStream_t st = as_stream(stream);
   const long long count = (long long)x * y * z * c;
-  NRPN_HIP(hipMemsetAsync(workspace, 0, (size_t)count * 8, st));
+  NRPN_HIP(hipMemsetAsync(workspace, 0, (size_t)count * 8 + 8, st));
   if (num_rois > 0) {
     const dim3 grid((unsigned)(num_rois * o0 * o1 * o2));
     const PoolGeom g{o0, o1, o2};
@@ -305,8 +314,8 @@ extern "C" int nrpn_roipool_obb_bwd(const float *dout, const int32_t *argmax, co
     int32_t *arg = const_cast<int32_t *>(argmax);
     long long *ws = (long long *)workspace;
     const void *no_feat = nullptr;
-    if (interpolation) NRPN_OBB_LAUNCH(float, 1, 1, no_feat, no_out, arg, dout, ws);
-    else NRPN_OBB_LAUNCH(float, 0, 1, no_feat, no_out, arg, dout, ws);
+    if (interpolation) NRPN_OBB_LAUNCH(float, 1, 1, no_feat, no_out, arg, dout, ws, (unsigned long long *)workspace + count);
+    else NRPN_OBB_LAUNCH(float, 0, 1, no_feat, no_out, arg, dout, ws, (unsigned long long *)workspace + count);
   }
   const int blocks = (int)min((long long)8192, (count + 255) / 256);
   if (dtype == NRPN_F32) hipLaunchKernelGGL(roipool_fixed_to_float_kernel<float>, dim3(blocks), dim3(256), 0, st, (const long long *)workspace, (float *)dfeat, count);
