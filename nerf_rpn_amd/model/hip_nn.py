@@ -38,7 +38,11 @@ def conv3d(mod, x, relu=False, out_f32=False, segs=None, chain=0, stats=None, af
     if segs is not None and (k == 7 or mod.stride[0] != 1):
         raise NotImplementedError("ragged voxel lists are supported by the stride-1 k1 / k3 convolutions only")
     mode = (relu, chain, stats, affine) if affine is not None else ((relu, chain, stats) if stats is not None else ((relu, chain) if chain else relu))
-    return ops.ConvFn.apply(x, _pack_of(mod), mod.out_channels, mode, out_f32, 1 if segs is None else (1, tuple(segs)), mod.weight, mod.bias)
+    if segs is None:
+        return ops.ConvFn.apply(x, _pack_of(mod), mod.out_channels, mode, out_f32, 1, mod.weight, mod.bias)
+    # whether this ragged launch is differentiated is decided HERE, where grad mode is visible (ops._x3_ok)
+    diff = torch.is_grad_enabled() and (x.requires_grad or mod.weight.requires_grad or (mod.bias is not None and mod.bias.requires_grad))
+    return ops.ConvFn.apply(x, _pack_of(mod), mod.out_channels, mode, out_f32, (1, tuple(segs), diff), mod.weight, mod.bias)
 
 
 def ragged_cat(feats):

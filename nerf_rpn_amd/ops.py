@@ -730,8 +730,9 @@ def split3(src, ipattern=None, nplanes=0, ppattern=0):
 
 def _x3_ok(x, ksize, segs, rows_total, differentiable):
     # ragged voxel lists (the dense head over all pyramid levels) only when nothing is differentiated: their weight gradient has no batch
-    # axis to stack on and the split dgrad launch knows no segments.  `differentiable` is decided from the operands -- inside
-    # autograd.Function.forward grad mode is always off, so torch.is_grad_enabled() says nothing there
+    # axis to stack on and the split dgrad launch knows no segments.  `differentiable` comes from the caller (hip_nn.conv3d: grad mode on AND
+    # an operand that requires a gradient) -- inside autograd.Function.forward grad mode is always off and ctx.needs_input_grad mirrors
+    # requires_grad even under torch.no_grad(), which sent every eval-mode ragged conv with trainable weights to the fp32 kernels
     return (SPLIT3[0] and x.dtype == torch.float32 and ksize == 3 and (segs is None or not differentiable)
             and x.shape[-1] % 32 == 0 and rows_total % 32 == 0)
 
@@ -755,16 +756,20 @@ def _x3_weights(pack, weights, wp, wpd):
 
 def column_sum_f32(t, out=None, accumulate=False):
     """f32 [rows, C] -> f32 [C] column sums, deterministic; ``out`` += when ``accumulate``.  Shapes the BatchNorm statistics reduction takes
-    (C % 4 == 0, C / 4 dividing 256: every conv width of the VGG / ResNet paths) go through it -- 4-channel lanes over ~1000 row slabs, fp64
-    finish: mean * rows -- the rest (e.g. C = 96) through nrpn_column_sum_f32."""
+    (C % 4 == 0, C / 4 dividing 256: every conv width of the VGG / ResNet paths) go through its slab pass -- 4-channel lanes over ~1000 row
+    slabs -- when they are large, and the slab sums it leaves in the workspace ([slabs][2][C]: sum, sum of squares) are added up in fp64
+    here; the rest (e.g. C = 96) through nrpn_column_sum_f32.  Both: fp32 sums inside a slab, fp64 across slabs, one rounding of the total --
+    on exactly summable data the sum itself.  (The first version returned bn_stats' mean * rows: two more roundings, an ulp off on about
+    one column in eight.)  Measured on an MI355X, slab pass + fp64 finish / nrpn_column_sum_f32: 160^3 x 64: 209 / 490 us, 80^3 x 128:
+    62 / 75 us, 40^3 x 256: 40 / 32 us, 20^3 x 512: 32 / 14 us -- hence the size threshold."""
     t = t.contiguous()
     rows, c = t.shape
     tile = min(c, 1024)
-    if c % 4 == 0 and 256 % (tile // 4) == 0 and c % tile == 0:
+    if rows * c >= (1 << 25) and c % 4 == 0 and 256 % (tile // 4) == 0 and c % tile == 0:
         mean, var = torch.empty(c, dtype=torch.float32, device=t.device), torch.empty(c, dtype=torch.float32, device=t.device)
         ws = torch.empty(query("bn_workspace_bytes", rows, c), dtype=torch.uint8, device=t.device)
         call("bn_stats", _p(t), rows, c, F32, _p(mean), _p(var), 0, 0, 0.1, _p(ws), _s())
-        res = mean * float(rows)
+        res = ws.view(torch.float32).view(-1, 2, c)[:, 0].sum(0, dtype=torch.float64).float()
         if out is None:
             return res
         return out.add_(res) if accumulate else out.copy_(res)
@@ -869,8 +874,11 @@ class ConvFn(torch.autograd.Function):
             relu, chain, *rest = relu
             stats = rest[0] if rest else None
             affine = rest[1] if len(rest) > 1 else None
-        if isinstance(nw, tuple):          # (nw, segs): ragged voxel list, x = [1, sum voxels, 1, 1, C]
-            nw, segs = nw
+        differentiable = any(ctx.needs_input_grad)
+        if isinstance(nw, tuple):          # (nw, segs[, differentiable]): ragged voxel list, x = [1, sum voxels, 1, 1, C]
+            nw, segs, *diff = nw
+            if diff:                       # decided by the caller, where grad mode is visible: needs_input_grad mirrors requires_grad even under no_grad
+                differentiable = bool(diff[0])
         weights, biases = wb[:nw], wb[nw:]
         _chk(x)
         ksize = weights[0].shape[2] if weights[0][0].numel() != x.shape[-1] else 1
@@ -890,7 +898,7 @@ class ConvFn(torch.autograd.Function):
                     pack.bias, pack.bias_key = torch.cat(parts), bkey
                 bias = pack.bias
         out_dtype = torch.float32 if out_f32 else x.dtype
-        x3 = _x3_ok(x, ksize, segs, rows_total, any(ctx.needs_input_grad))
+        x3 = _x3_ok(x, ksize, segs, rows_total, differentiable)
         xin = x
         if x3:      # bf16x3: split operands on the bf16 MFMA kernels, fp32 rows out; BatchNorm statistics then come from their own pass
             wp, wpd = _x3_weights(pack, weights, wp, wpd)

@@ -391,7 +391,9 @@ def test_ragged_conv_under_bf16x3_keeps_its_gradients(dev):
     """with the bf16x3 mode raised, a DIFFERENTIATED ragged conv must not take the split-operand path (its dgrad / wgrad
     launches know no segments: the ragged list would be read as one dense grid) -- the decision is made from the operands' requires_grad,
     not from grad mode (always off inside autograd.Function.forward).  Gradients must equal the fp32 ragged path's; without autograd the
-    ragged forward may use the split operands and must agree with fp32 to the mode's tolerance."""
+    ragged forward may use the split operands and must agree with fp32 to the mode's tolerance.  (That the no_grad leg really runs the
+    split operands -- the decision follows grad mode, passed in by hip_nn.conv3d -- is proved on exactly summable data by
+    test_gpu_conv_exact.py::test_ragged_bf16x3_follows_grad_mode.)"""
     from nerf_rpn_amd import ops
     from nerf_rpn_amd.model import hip_nn
     torch.manual_seed(4)
