@@ -82,17 +82,33 @@ __device__ __forceinline__ void corners(const D &x, const D &y, const D &w, cons
   }
 }
 
-// corners P inside box Q on VALUES (box_intersection_2d.py:54-79)
-__device__ __forceinline__ void inside4(const float *PX, const float *PY, const float *QX, const float *QY, bool *in) {
-  const float abx = QX[1] - QX[0], aby = QY[1] - QY[0];
-  const float adx = QX[3] - QX[0], ady = QY[3] - QY[0];
-  const float nab = abx * abx + aby * aby, nad = adx * adx + ady * ady;
-  const float hi = (float)(1 + 1e-6), lo = -1e-6f;
+// corners P inside box Q on VALUES (box_intersection_2d.py:54-79), decided in fp64 on fp64 corners.  The reference accepts a corner
+// whose normalised projections lie in (-1e-6, 1 + 1e-6).  Corners rounded to fp32 at a centre near 30 sit ~2e-6 off, so the edges ab
+// and ad of a thin box are not orthogonal to ~1e-5 of that scale: a corner ON an edge of the other box -- every corner, when prediction
+// and target coincide -- came out at -1e-5 and was dropped, 6 of the 8 coincident vertices remained and the IoU of identical boxes
+// was 1/3 or 0 (13 of 256 pairs).  The threshold is kept; only the rounding it was never meant to see is taken out.  The polygon
+// area is continuous in this decision (a corner on an edge coincides with the edge intersections), so other values do not move.
+__device__ __forceinline__ void corners_f64(const float *b, double *X, double *Y) {
+  const double s = sin((double)b[6]), c = cos((double)b[6]);
+  const double sx[4] = {0.5, -0.5, -0.5, 0.5};
+  const double sy[4] = {0.5, 0.5, -0.5, -0.5};
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const float amx = PX[i] - QX[0], amy = PY[i] - QY[0];
-    const float r1 = (abx * amx + aby * amy) / nab;
-    const float r2 = (adx * amx + ady * amy) / nad;
+    const double lx = sx[i] * (double)b[3], ly = sy[i] * (double)b[4];
+    X[i] = lx * c - ly * s + (double)b[0];
+    Y[i] = lx * s + ly * c + (double)b[1];
+  }
+}
+__device__ __forceinline__ void inside4(const double *PX, const double *PY, const double *QX, const double *QY, bool *in) {
+  const double abx = QX[1] - QX[0], aby = QY[1] - QY[0];
+  const double adx = QX[3] - QX[0], ady = QY[3] - QY[0];
+  const double nab = abx * abx + aby * aby, nad = adx * adx + ady * ady;
+  const double hi = 1 + 1e-6, lo = -1e-6;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const double amx = PX[i] - QX[0], amy = PY[i] - QY[0];
+    const double r1 = (abx * amx + aby * amy) / nab;
+    const double r2 = (adx * amx + ady * amy) / nad;
     in[i] = (r1 > lo) && (r1 < hi) && (r2 > lo) && (r2 < hi);
   }
 }
@@ -120,13 +136,18 @@ __device__ void iou3d_dual(const float *pv, const float *q, PairOut &o) {
   // ---- 24 candidate vertices: 4 + 4 corners, 16 edge intersections
   D vx[24], vy[24];
   bool ok[24];
-  float AXv[4], AYv[4], BXv[4], BYv[4];
+  float BXv[4], BYv[4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) { AXv[i] = o.X[i].v; AYv[i] = o.Y[i].v; BXv[i] = o.X[4 + i].v; BYv[i] = o.Y[4 + i].v; }
+  for (int i = 0; i < 4; ++i) { BXv[i] = o.X[4 + i].v; BYv[i] = o.Y[4 + i].v; }
 #pragma unroll
   for (int i = 0; i < 8; ++i) { vx[i] = o.X[i]; vy[i] = o.Y[i]; }
-  inside4(AXv, AYv, BXv, BYv, ok);
-  inside4(BXv, BYv, AXv, AYv, ok + 4);
+  {
+    double AXd[4], AYd[4], BXd[4], BYd[4];
+    corners_f64(pv, AXd, AYd);
+    corners_f64(q, BXd, BYd);
+    inside4(AXd, AYd, BXd, BYd, ok);
+    inside4(BXd, BYd, AXd, AYd, ok + 4);
+  }
   for (int i = 0; i < 4; ++i) {
     const D x1 = o.X[i], y1 = o.Y[i], x2 = o.X[(i + 1) & 3], y2 = o.Y[(i + 1) & 3];
     for (int j = 0; j < 4; ++j) {
@@ -207,19 +228,66 @@ __device__ void iou3d_dual(const float *pv, const float *q, PairOut &o) {
 }
 
 // smallest_bounding_box (min_enclosing_box.py:54-125): over the 24 candidate edges through two of the 8 corners
-__device__ void enclosing_wh(const D *X, const D *Y, D &w, D &h) {
-  float best = 0.f;
+// Parallel boxes (equal yaws, or both at multiples of pi/2) make the 8 box edges exact ties of the arg-min: parallel or perpendicular
+// candidates span the same rectangle, and rounding decides between them.  They have one area but different yaw slopes: an edge of
+// the (constant) target box keeps its direction, an edge of the predicted box turns with it.  A candidate that is the minimum at the
+// tie ONLY (its area rises on both sides, faster than another's) carries a slope that no neighbouring box has -- 17-28x the largest
+// neighbouring gradient, in the fp64 reference itself.  So when the yaws differ by a multiple of pi/2 within TIE (`par`, taken from
+// the yaws: fp32 leaves ~1e-7 there, and up to 2e-6 on a direction taken from corners), the box edge with the smallest
+// |d area / d yaw| is kept among the box edges -- yaw alone breaks such a tie -- and the first on equal slopes.  The rectangle and so
+// the loss are the reference's; without such a tie so is the arg-min.  Edges between the boxes are never merged: near the flat minimum over
+// directions their areas come within 1e-6 of each other while they are different functions.
+//
+// Where fp32 cannot tell two areas apart (within NEAR of each other) the arg-min is decided in fp64 on fp64 corners (cand_area_f64),
+// like the containment test: once the prediction is within ~1e-2 of its target, the rectangles of the two boxes' own edges differ in
+// area by 2e-7 ... 5e-7 relative, below what fp32 resolves, and rounding picked the other box's edge on 1-2 of 256 pairs (GIoU
+// gradient off by up to 1.5e-3).  Areas that fp32 does tell apart are compared in fp32, as the reference does: on degenerate candidates
+// (an edge between two coincident corners) its choice is made of rounding and is kept.  w and h stay the fp32 dual numbers.
+constexpr float NEAR = 1e-5f;
+constexpr float TIE = 2e-6f;
+__device__ double cand_area_f64(const double *X, const double *Y, int i, int j) {
+  const double dx = X[j] - X[i], dy = Y[j] - Y[i];
+  const double dxe = dx + 1e-8, nrm = sqrt(dxe * dxe + dy * dy), ux = dxe / nrm, uy = dy / nrm;
+  const double den = sqrt(dy * dy + dx * dx + 1e-14), c0 = X[j] * Y[i] - Y[j] * X[i];
+  double pmax = 0., pmin = 0., dmx = 0., dmn = 0., amax = 0.;
+  bool fd = true;
+  for (int t = 0; t < 8; ++t) {
+    const double pr = X[t] * ux + Y[t] * uy;
+    pmax = t == 0 ? pr : fmax(pmax, pr);
+    pmin = t == 0 ? pr : fmin(pmin, pr);
+    if (t == i || t == j) continue;
+    const double dd = (dy * X[t] - dx * Y[t] + c0) / den;
+    dmx = fd ? dd : fmax(dmx, dd);
+    dmn = fd ? dd : fmin(dmn, dd);
+    amax = fd ? fabs(dd) : fmax(amax, fabs(dd));
+    fd = false;
+  }
+  return (pmax - pmin) * fmax(dmx - dmn, amax);
+}
+
+__device__ void enclosing_wh(const D *X, const D *Y, const float *pv, const float *q, D &w, D &h) {
+  const bool par = fabsf(sinf(2.f * (pv[6] - q[6]))) < 2.f * TIE;
+  double XD[8], YD[8];
+  corners_f64(pv, XD, YD);
+  corners_f64(q, XD + 4, YD + 4);
+  double best = 0.;                                              // fp64 and fp32 area of the kept candidate
+  float best32 = 0.f, slope = 0.f;
+  bool edge = false;                                             // the kept candidate is an edge of one box
   bool have = false;
   for (int i = 0; i < 8; ++i) {
     for (int j = i + 1; j < 8; ++j) {
       if ((i == 0 && j == 2) || (i == 1 && j == 3) || (i == 5 && j == 7) || (i == 4 && j == 6)) continue;
       const D x1 = X[i], y1 = Y[i], x2 = X[j], y2 = Y[j];
-      const D k = (y2 - y1) / (x2 - x1 + 1e-8f);
-      const D nrm = dsqrt(cst(1.f) + k * k);
+      const D dx = x2 - x1, dy = y2 - y1;
+      // The reference projects on (1, k) / sqrt(1 + k^2) with the slope k = dy / (dx + 1e-8).  That is +-(dxe, dy) / |(dxe, dy)| with
+      // dxe = dx + 1e-8, and the range pmax - pmin does not depend on the sign: the same function without the slope, whose partials
+      // (k ~ 1e9 * dy on a near-vertical edge) cancel at ~1e17 and are lost in fp32.
+      const D dxe = dx + 1e-8f;
+      const D nrm = dsqrt(dxe * dxe + dy * dy);
+      const D ux = dxe / nrm, uy = dy / nrm;
       // projections of all 8 points on the edge direction, in the order [edge point 1, edge point 2, the other six]
       D pmax, pmin, dmx, dmn, amax;
       bool fp = true, fd = true;
-      const D dx = x2 - x1, dy = y2 - y1;
       const D den = dsqrt(dy * dy + dx * dx + 1e-14f);
       int order[8];
       order[0] = i; order[1] = j;
@@ -228,7 +296,7 @@ __device__ void enclosing_wh(const D *X, const D *Y, D &w, D &h) {
         if (t != i && t != j) order[c++] = t;
       for (int t = 0; t < 8; ++t) {
         const int pt = order[t];
-        const D pr = (X[pt] + Y[pt] * k) / nrm;
+        const D pr = X[pt] * ux + Y[pt] * uy;
         if (fp) { pmax = pr; pmin = pr; fp = false; } else { pmax = dmax(pmax, pr); pmin = dmin(pmin, pr); }
         if (t >= 2) {
           const D dd = (dy * X[pt] - dx * Y[pt] + x2 * y1 - y2 * x1) / den;
@@ -239,9 +307,18 @@ __device__ void enclosing_wh(const D *X, const D *Y, D &w, D &h) {
       const D prange = pmax - pmin;
       const D dr1 = dmx - dmn;
       const D drange = amax.v > dr1.v ? amax : dr1;            // torch.max(a, b): the larger operand carries the gradient
-      float area = prange.v * drange.v;
-      if (area == 0.f) area += 1e8f;
-      if (!have || area < best) { best = area; have = true; w = prange; h = drange; }
+      float area32 = prange.v * drange.v;
+      if (area32 == 0.f) area32 += 1e8f;
+      double area = cand_area_f64(XD, YD, i, j);
+      if (area == 0.) area += 1e8;
+      const float sl = fabsf(prange.g[6] * drange.v + prange.v * drange.g[6]);
+      const bool own = j < 4 || i >= 4;
+      const bool near = have && fabsf(area32 - best32) <= NEAR * best32;
+      const bool tie = par && near && own && edge && fabs(area - best) <= 1e-5 * best;
+      if (!have || (tie ? sl < slope : near ? area < best : area32 < best32)) {
+        slope = sl; edge = own; best = area; best32 = area32; w = prange; h = drange;
+      }
+      have = true;
     }
   }
 }
@@ -262,7 +339,7 @@ __global__ void rotated_iou_loss_kernel(const float *__restrict__ pred, const fl
     l = (mode == 0) ? -dlog(r) : (1.0f - r);
   } else {
     D w, h;
-    enclosing_wh(o.X, o.Y, w, h);
+    enclosing_wh(o.X, o.Y, p, q, w, h);
     if (mode == 2) {
       const D vc = o.zr * w * h;
       l = 1.0f - o.iou + (vc - o.u3) / vc;

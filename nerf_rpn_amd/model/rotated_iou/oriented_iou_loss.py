@@ -95,9 +95,11 @@ def smallest_bounding_box(c8):
     lines, rest = _hull_tables(c8.device)
     ln, pt = c8[..., lines, :], c8[..., rest, :]
     x1, y1, x2, y2 = ln[..., 0:1, 0], ln[..., 0:1, 1], ln[..., 1:2, 0], ln[..., 1:2, 1]
-    k = (y2 - y1) / (x2 - x1 + 1e-8)
-    vec = torch.cat([torch.ones_like(k), k], dim=-1).unsqueeze(-2)
-    proj = (torch.cat([ln, pt], dim=-2) * vec).sum(-1) / torch.norm(vec, dim=-1)
+    # the reference's (1, k) / sqrt(1 + k^2), k = dy / (dx + 1e-8), is +-(dxe, dy) / |(dxe, dy)| and the range below ignores the sign:
+    # the same function without the slope, whose autograd partials cancel at ~1e17 on a near-vertical edge (csrc/geomloss.hip)
+    vec = torch.cat([x2 - x1 + 1e-8, y2 - y1], dim=-1)
+    vec = (vec / torch.norm(vec, dim=-1, keepdim=True)).unsqueeze(-2)
+    proj = (torch.cat([ln, pt], dim=-2) * vec).sum(-1)
     prange = proj.max(-1)[0] - proj.min(-1)[0]
     x, y = pt[..., 0], pt[..., 1]
     d = ((y2 - y1) * x - (x2 - x1) * y + x2 * y1 - y2 * x1) / torch.sqrt((y2 - y1).square() + (x2 - x1).square() + 1e-14)

@@ -148,10 +148,14 @@ def enclosing_box_wh(c8):
     x1, y1 = ln[..., 0:1, 0], ln[..., 0:1, 1]
     x2, y2 = ln[..., 1:2, 0], ln[..., 1:2, 1]
     # projection range along the edge (:117-134)
-    k = (y2 - y1) / (x2 - x1 + 1e-8)
-    vec = torch.cat([torch.ones_like(k), k], dim=-1).unsqueeze(-2)
+    # The reference projects on (1, k) / sqrt(1 + k^2), k = dy / (dx + 1e-8).  That is +-(dxe, dy) / |(dxe, dy)|, dxe = dx + 1e-8, and
+    # the range ignores the sign: the same function, stated without the slope, whose autograd partials cancel at ~1e17 on a
+    # near-vertical edge and made this fp32 chain miss fp64 (8.5e-3 on golden pair 9 + 34).  tests/geomloss_ref.py keeps the
+    # reference's literal form, in fp64.
+    vec = torch.cat([x2 - x1 + 1e-8, y2 - y1], dim=-1)
+    vec = (vec / torch.norm(vec, dim=-1, keepdim=True)).unsqueeze(-2)
     allp = torch.cat([ln, pt], dim=-2)
-    proj = (allp * vec).sum(-1) / torch.norm(vec, dim=-1)
+    proj = (allp * vec).sum(-1)
     prange = proj.max(-1)[0] - proj.min(-1)[0]
     # distance range perpendicular to it (:87-115)
     x, y = pt[..., 0], pt[..., 1]

@@ -1,11 +1,20 @@
-"""GPU parity of the fused differentiable rotated IoU / GIoU / DIoU loss kernel (csrc/geomloss.hip, forward + gradient in one launch)
-against the CPU oracle's autograd through the reference formulation (oracle/geometry.py == reference oriented_iou_loss.py:82-148,
-box_intersection_2d.py, min_enclosing_box.py:54-125) and against the golden values captured from the reference itself."""
+"""GPU tests of the fused differentiable rotated IoU / GIoU / DIoU loss kernel (csrc/geomloss.hip, forward + gradient in one launch).
+
+The accuracy reference is fp64 (tests/geomloss_ref.py): the loss and its autograd gradient in float64, on seeded input classes that
+cover what training visits -- predictions at or near a multiple of pi/2, equal yaws, predictions close to their target, containment,
+separation in xy or in z.  Every pair that the reference's stability probe does not flag is held to
+    |g - g64| <= 1e-4 + 1e-3 |g64| + dev        |l - l64| <= 5e-5 + 1e-4 |l64| + ldev        |iou - iou64| <= 1e-5
+without exception; a flagged pair sits on a decision of the piecewise formulation (a validity mask, the vertex order, an arg-min, a
+clamp), where another subgradient is legitimate but none may exceed 4x the largest neighbouring fp64 gradient.  tests/test_geomloss_host.py
+caps the share of flagged pairs.  The older parity tests against the CPU oracle's fp32 autograd (oracle/geometry.py == reference
+oriented_iou_loss.py:82-148, box_intersection_2d.py, min_enclosing_box.py:54-125), the torch chain and the reference's golden values stay."""
 import math
 
 import numpy as np
 import pytest
 import torch
+
+import geomloss_ref as R
 
 pytestmark = pytest.mark.gpu
 
@@ -57,9 +66,16 @@ def test_fused_loss_and_gradient_match_oracle_autograd(mode, golden, dev):
         from oracle import geometry as OG
         assert torch.allclose(iou.cpu(), OG.iou_3d(b1.unsqueeze(0), b2.unsqueeze(0))[0], atol=1e-5)
         gerr = (a.grad.cpu() - c.grad).abs()
-        bad = gerr > 1e-4 + 1e-3 * c.grad.abs()
-        # a validity mask / arg-min decided within an ulp of its threshold may differ between CPU and GPU libm: a handful of pairs at most
-        assert bad.any(dim=1).sum() <= 3, (mode, int(bad.any(dim=1).sum()), gerr.max())
+        bad = (gerr > 1e-4 + 1e-3 * c.grad.abs()).any(dim=1)
+        # Who may differ: only a pair that the fp64 reference flags (a validity mask / arg-min decided within an ulp of its threshold
+        # may fall differently with the CPU's and the GPU's libm).  The oracle states the enclosing box without the slope, as the kernel
+        # does; with the slope its own fp32 gradient missed fp64 by 8.5e-3 on golden pair 9 + 34.  Every unflagged pair meets fp64 too.
+        st = R.stability(mode, b1, b2)
+        lim = (R.tol(st["g64"]) + st["dev"]) * w.double()[:, None]
+        kernel_off = ((a.grad.cpu().double() - st["g64"] * w.double()[:, None]).abs() > lim).any(dim=1)
+        print(mode, "bad", bad.nonzero().flatten().tolist(), "flagged", int(st["flagged"].sum()))
+        assert not (bad & ~st["flagged"]).any(), (mode, (bad & ~st["flagged"]).nonzero().flatten().tolist(), gerr.max())
+        assert not (kernel_off & ~st["flagged"]).any(), (mode, (kernel_off & ~st["flagged"]).nonzero().flatten().tolist())
         assert torch.isfinite(a.grad).all()
 
 
@@ -79,7 +95,9 @@ def test_fused_loss_matches_reference_goldens_and_torch_chain(golden, dev):
     ops.rotated_iou_loss(a, b2[9:309], "giou")[0].sum().backward()
     L.cal_giou_3d(c.unsqueeze(0), b2[9:309].unsqueeze(0))[0].sum().backward()
     gerr = (a.grad - c.grad).abs()
-    assert (gerr > 1e-4 + 1e-3 * c.grad.abs()).any(dim=1).sum() <= 3, gerr.max()
+    bad = (gerr > 1e-4 + 1e-3 * c.grad.abs()).any(dim=1).cpu()
+    flagged = R.stability("giou", b1[9:309].cpu(), b2[9:309].cpu())["flagged"]
+    assert not (bad & ~flagged).any(), ((bad & ~flagged).nonzero().flatten().tolist(), gerr.max())
 
 
 def test_loss_classes_use_the_fused_kernel(dev, monkeypatch):
@@ -119,3 +137,89 @@ def test_projection_loss_kernel_matches_torch_chain(box_dim, dev):
     M, K = _view_stack(160, dev)
     from nerf_rpn_amd import ops
     assert torch.isnan(ops.projection_loss(p[:0], t[:0], M, K, 1.0 / 9, 160.0))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# against the fp64 reference (tests/geomloss_ref.py)
+# ---------------------------------------------------------------------------------------------------------------------------------
+def kernel(b1, b2, mode, dev, w=None):
+    """One launch -> (loss, d sum(w * loss) / d pred, iou) on the CPU, fp32 as the kernel wrote them."""
+    from nerf_rpn_amd import ops
+    a = b1.clone().to(dev).requires_grad_(True)
+    loss, iou = ops.rotated_iou_loss(a, b2.to(dev), mode)
+    (loss.sum() if w is None else (loss * w.to(dev)).sum()).backward()
+    return loss.detach().cpu(), a.grad.cpu(), iou.detach().cpu()
+
+
+def check_against_fp64(kind, mode, dev, ties):
+    b1, b2, st = R.case(kind, mode)
+    loss, grad, iou = kernel(b1, b2, mode, dev)
+    keep = ~st["flagged"]
+    gerr = (grad.double() - st["g64"]).abs()
+    lerr = (loss.double() - st["l64"]).abs()
+    ratio = grad.double().abs().amax(dim=1) / (st["gmax"] + 1e-12)
+    print(f"{kind} {mode}: flagged {int(st['flagged'].sum())}/{len(b1)}  unflagged max gerr {float((gerr * keep[:, None]).max()):.2e}"
+          f"  max lerr {float(lerr.max()):.2e}  max ioerr {float(((iou.double() - st['iou64']).abs() * keep).max()):.2e}  max |g|/gmax {float(ratio.max()):.2f}")
+    assert torch.isfinite(loss).all() and torch.isfinite(grad).all() and torch.isfinite(iou).all()
+    lbad = lerr > 5e-5 + 1e-4 * st["l64"].abs() + st["ldev"]
+    assert not lbad.any(), (kind, mode, int(lbad.sum()), float(lerr.max()))
+    if kind == "identical":                 # the reference jumps between IoU 1, 1/3 and 0 there: no gradient to compare with
+        return
+    bad = (gerr > R.tol(st["g64"]) + st["dev"]).any(dim=1)
+    assert not (bad & keep).any(), (kind, mode, (bad & keep).nonzero().flatten().tolist(), float((gerr * keep[:, None]).max()))
+    if ties:
+        # a valid subgradient lies in the hull of the neighbouring gradients (ratio <= 1); 4 covers pieces that 16 samples miss
+        # (2.8 seen); a slope of a candidate that is minimal at the tie only gives 17 and more
+        assert (grad.double().abs().amax(dim=1) <= 4 * st["gmax"] + 1e-3).all(), (kind, mode, float(ratio.max()))
+    else:
+        assert ((iou.double() - st["iou64"]).abs() <= 1e-5).all(), (kind, mode, float((iou.double() - st["iou64"]).abs().max()))
+
+
+@pytest.mark.parametrize("kind,mode", R.STABLE_CASES)
+def test_stable_classes_match_fp64(kind, mode, dev):
+    check_against_fp64(kind, mode, dev, ties=False)
+
+
+@pytest.mark.parametrize("kind,mode", R.TIE_CASES)
+def test_tie_classes_stay_within_neighbouring_fp64_gradients(kind, mode, dev):
+    check_against_fp64(kind, mode, dev, ties=True)
+
+
+@pytest.mark.parametrize("mode", R.MODES)
+def test_identical_boxes_are_finite_and_within_the_loss_bound(mode, dev):
+    """prediction == target, 256 pairs: everything finite, and the loss within 5e-5 + 1e-4 |l64| + ldev of fp64 (l64 = 0: IoU 1).
+    With the containment test of box_intersection_2d.py:54-79 decided on fp32 corners, 13 of the 256 pairs came out at IoU 1/3 or 0
+    (loss up to 7.94): at centres near 30 the rounded edges of a thin box are not orthogonal to 1e-5, past the reference's 1e-6
+    tolerance, and a coincident corner was dropped.  The kernel decides it in fp64."""
+    check_against_fp64("identical", mode, dev, ties=True)
+
+
+@pytest.mark.parametrize("mode", R.MODES)
+@pytest.mark.parametrize("kind", ["generic", "both_axis"])
+def test_partial_waves_and_upstream_gradient_are_bit_equal(kind, mode, dev):
+    """One lane handles one pair: n = 1, 63, 65 (below, and one past, a 64-lane block) reproduce the first rows of n = 256 bit for
+    bit, and a non-uniform upstream gradient is one fp32 multiply of the kernel's gradient."""
+    b1, b2 = R.gen(kind)
+    w = torch.linspace(0.5, 1.5, len(b1))
+    loss, grad, iou = kernel(b1, b2, mode, dev)
+    loss_w, grad_w, iou_w = kernel(b1, b2, mode, dev, w)
+    assert torch.equal(loss_w, loss) and torch.equal(iou_w, iou) and torch.equal(grad_w, grad * w[:, None])
+    for n in (1, 63, 65):
+        ln, gn, un = kernel(b1[:n], b2[:n], mode, dev, w[:n])
+        assert torch.equal(ln, loss[:n]) and torch.equal(un, iou[:n]) and torch.equal(gn, grad_w[:n]), (kind, mode, n)
+
+
+@pytest.mark.parametrize("mode", ["giou", "diou"])
+@pytest.mark.parametrize("kind", ["axis_exact", "nearaxis_1e-4"])
+def test_torch_chain_matches_fp64_near_the_axes(kind, mode, dev):
+    """model/rotated_iou/oriented_iou_loss.py (the path when the target carries a gradient) projects without the slope as well."""
+    from nerf_rpn_amd.model.rotated_iou import oriented_iou_loss as L
+    b1, b2, st = R.case(kind, mode)
+    c = b1.clone().to(dev).requires_grad_(True)
+    loss = (L.cal_giou_3d if mode == "giou" else L.cal_diou_3d)(c.unsqueeze(0), b2.to(dev).unsqueeze(0))[0][0]
+    loss.sum().backward()
+    gerr = (c.grad.cpu().double() - st["g64"]).abs()
+    bad = (gerr > R.tol(st["g64"]) + st["dev"]).any(dim=1) & ~st["flagged"]
+    print(kind, mode, "torch chain: unflagged max gerr", float((gerr * (~st["flagged"])[:, None]).max()))
+    assert not bad.any(), (kind, mode, bad.nonzero().flatten().tolist())
+    assert ((loss.detach().cpu().double() - st["l64"]).abs() <= 5e-5 + 1e-4 * st["l64"].abs() + st["ldev"]).all()
