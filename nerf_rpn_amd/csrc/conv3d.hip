@@ -12,6 +12,7 @@
 //
 // Replaces torch.nn.Conv3d (MIOpen/cuDNN) in reference feature_extractor.py:331-358, fpn.py:109-110, anchor.py:190-198.
 #include "conv_common.cuh"
+#include "conv_plan.h"
 
 // Halo kernel, taps paired across channel-chunk boundaries (conv_halo.hip XP): 0 = never, 1 = whenever Cin % 128 == 0, 2 = from Cin 256 up.
 // Measured (profiles/r05_halo_pairing.json, one MI355X, alternating rounds, bit-identical outputs): 256->256@40^3 176.1 vs 176.5 us (post-ReLU
@@ -1225,7 +1226,6 @@ __global__ void __launch_bounds__(256, 1) conv_igemm_big4_kernel(const ConvArgs 
 }
 
 // conv_halo.hip: the "halo" form of the 3x3x3 implicit GEMM (4 x 8 x 8 voxel blocks, input halo staged once per channel chunk)
-namespace hk { constexpr int TX = 4, TY = 8, TZ = 8; }
 int nrpn_launch_conv_halo(const ConvArgs &a, unsigned workgroups, hipStream_t st, int variant);
 
 template <typename T, bool OUTF32>
@@ -1262,20 +1262,10 @@ __global__ void rows_epilogue_kernel(const float *__restrict__ ws, const float *
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Kernel selection.  Every decision below is a pure function of (shape, Knobs): a call resolves its Knobs from the process-wide
-// defaults (developer switches, tools only) overridden by the caller's nrpn_conv_opts, so two threads with different plans never
-// touch shared state while launching.
+// Kernel selection: conv_plan.h.  A call resolves its Knobs once, from the process-wide defaults (developer switches, tools only)
+// overridden by the caller's nrpn_conv_opts, computes ONE plan from (shape, Knobs, per-call facts) and launches what the plan says;
+// the size / plan queries report fields of the same plan.
 // ---------------------------------------------------------------------------------------------------------------------
-struct Knobs {
-  int glds;        // 1: LDS-DMA loads (buffer_load ... lds), 0: register-staged loads
-  int bm;          // tile selector: 0 auto, 128, 256 (wave-specialised 256x128), 512 (256x256, 8 waves), 1024 (256x256, 4 waves), 2048 (halo form)
-  int stagger;     // 256x256 8-wave kernel: rotated K-step + staggered DMA issue (default) or the plain loop
-  int big_split;   // mid-size grids run the 256x256 kernel on K slices
-  int kb;          // K-step bytes of the k1/k3 kernels (64 or 128)
-  int dbg;         // tools only: NRPN_CONV_DEBUG_* bits
-  int halo_auto;   // 1 (default): the halo form is chosen automatically where it applies (40^3-class grids), 0: only on request (tile 2048)
-  int halo_xp;     // halo form: taps paired across chunk boundaries (54 full K-steps per four chunks; Cin % 128 == 0) instead of 14 per chunk
-};
 static std::atomic<int> g_conv_glds{1}, g_conv_bm{0}, g_conv_stagger{1}, g_conv_big_split{1}, g_conv_kb{128}, g_conv_halo_auto{1}, g_conv_halo_xp{NRPN_HALO_PAIRING_DEFAULT};
 static Knobs resolve_knobs(const nrpn_conv_opts *o, int flags = 0) {
   Knobs k{g_conv_glds.load(std::memory_order_relaxed), g_conv_bm.load(std::memory_order_relaxed), g_conv_stagger.load(std::memory_order_relaxed),
@@ -1311,280 +1301,137 @@ extern "C" int nrpn_set_conv_tile_m(int bm) {
   return NRPN_OK;
 }
 
-// split the K loop when the (M, N) tiling alone cannot fill 256 CUs (the 10^3 / 5^3 pyramid levels)
-static int conv_ksplit(long long M, int cout, int cin, int taps, int elem_bytes, const Knobs &kn) {
-  const int bn = cout <= 64 ? 64 : 128;
-  const long long tiles = cdiv64(M, 128) * ((cout + bn - 1) / bn);
-  const int kb = (kn.kb == 128 && (cin * elem_bytes) % 128 == 0) ? 128 : 64;
-  const int nk = taps * (cin * elem_bytes / kb);
-  if (tiles >= 128 || nk < 16) return 1;
-  long long s = (384 + tiles - 1) / tiles;
-  if (s > nk / 8) s = nk / 8;
-  if (s > 64) s = 64;
-  if (s < 2) return 1;
-  const long long per = (nk + s - 1) / s;
-  s = (nk + per - 1) / per;                  // no empty slice: every slice writes its whole partial
-  return s < 2 ? 1 : (int)s;
-}
-
-// Mid-size grids (20^3: M = 8000) give only 32-64 tiles of 256x256: run the big kernel on K slices whose fp32 partials are
-// written with plain stores to ws[z][M][Cout] and summed by the epilogue (no atomics).  Returns the slice count, 0 = not used.
-static int conv_big_split(long long M, int cout, int cin, int taps, int elem_bytes, const Knobs &kn) {
-  if (!kn.big_split) return 0;
-  if (elem_bytes != 2 || !kn.glds || kn.kb != 128 || (kn.bm != 0 && kn.bm != 512 && kn.bm != 1024) || cout < 256 || (cin * 2) % 128 != 0) return 0;
-  const long long tiles = cdiv64(M, 256) * ((cout + 255) / 256);
-  // measured inside the bench (20^3 maps): 512->512 (64 tiles, 4 slices) 123 us here vs 204 us on the 128-row kernel, but 256->256
-  // (32 tiles, 8 slices of 13 K-steps) 56 us here vs 49 us there -- below ~48 tiles the slices get too short to amortise the 256 KB
-  // partial-tile epilogue
-  if (tiles < 48 || tiles >= 200) return 0;
-  const int nk = taps * (cin / 64);
-  int s = (int)((256 + tiles - 1) / tiles);
-  if (s > 8) s = 8;
-  while (s > 1 && nk / s < 8) --s;
-  return s >= 2 ? s : 0;
-}
-
-// Tail split of a 256x256-tile launch: tiles = whole rounds of the 256 CUs + a short remainder (eval at 200 x 200 x 130: 323 = 256 + 67).  The
-// remainder's M tiles run on K slices so that the second round lasts 1 / ks of a round (+ a small epilogue over those rows) instead of a
-// whole one.  Only single-column tilings (Cout <= 256), bf16 in / bf16 out, no fused statistics.  -> {first tail M tile, ks}; ks 0 = none.
-struct TailSplit { int tile0, ks; };
-static TailSplit conv_tail_split(long long M, int cout, int cin, int taps, int elem_bytes, const Knobs &kn) {
-  TailSplit none{0, 0};
-  if (elem_bytes != 2 || !kn.glds || kn.kb != 128 || !kn.big_split || cout > 256 || cout < 256 || (cin * 2) % 128 != 0) return none;
-  const long long tiles = cdiv64(M, 256);
-  const long long rem = tiles % 256;
-  if (tiles <= 256 || rem == 0 || rem > 128) return none;
-  const int nk = taps * (cin / 64);
-  int ks = (int)(256 / rem);
-  if (ks > 8) ks = 8;
-  while (ks > 1 && nk / ks < 8) --ks;
-  if (ks < 2) return none;
-  const int per = (nk + ks - 1) / ks;
-  ks = (nk + per - 1) / per;                 // no empty slice
-  return ks >= 2 ? TailSplit{(int)(tiles - rem), ks} : none;
-}
-
 template <typename K>
-static int launch_igemm(K kernel, dim3 grid, size_t lds, hipStream_t st, const ConvArgs &a) {
+static int launch_igemm(K kernel, dim3 grid, int threads, size_t lds, hipStream_t st, const ConvArgs &a) {
   if (lds > 64 * 1024) NRPN_LDS(kernel, (int)lds);
-  hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, a);
+  hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, st, a);
   return NRPN_OK;
 }
 
-// Halo form (conv_halo_kernel): bf16 3x3x3 on a classic grid whose 4 x 8 x 8 blocks waste little and still fill the chip.
-struct Grid { int n, gx, gy, gz; };
-static long long halo_tiles(const Grid &g) {
-  return (long long)g.n * ((g.gx + hk::TX - 1) / hk::TX) * ((g.gy + hk::TY - 1) / hk::TY) * ((g.gz + hk::TZ - 1) / hk::TZ);
-}
-static bool halo_ok(const Grid &g, int cin, int cout, int taps, int elem_bytes, bool out_f32, const Knobs &kn) {
-  (void)out_f32;      // round 5: the halo kernel has an fp32-output epilogue (no mask / statistics there: the entry points reject those)
-  if (g.n <= 0 || taps != 27 || elem_bytes != 2 || !kn.glds || (cin % 32) != 0 || (cout & 7) != 0 || cout < 256) return false;
-  if (kn.bm != 2048 && !(kn.bm == 0 && kn.halo_auto)) return false;
-  const long long tiles = halo_tiles(g) * ((cout + 255) / 256);
-  const double waste = (double)halo_tiles(g) * 256.0 / ((double)g.n * g.gx * g.gy * g.gz);
-  if (kn.bm == 2048) return true;                       // forced (tools / tests): any grid
-  return tiles >= 200 && waste <= 1.12;
-}
-
-// the tile family a (shape, Knobs) pair selects: 0 = 128-row, 1 = 256x256 8-wave, 4 = wave-specialised 256x128, 5 = 256x256 4-wave
-static int conv_tile_kind(long long M, int cout, int cin, int elem_bytes, bool sliced_big, bool ragged, const Knobs &kn) {
-  const bool wide = kn.kb == 128 && (cin * elem_bytes) % 128 == 0;
-  const bool can = kn.glds && wide && cout > 64 && elem_bytes == 2;
-  const long long tiles_big = cdiv64(M, 256) * ((cout + 255) / 256);
-  const bool huge = can && cout >= 256 && (sliced_big || kn.bm == 512 || kn.bm == 1024 || (kn.bm == 0 && tiles_big >= 200));
-  if (huge) return (kn.bm == 1024 && !ragged) ? 5 : 1;
-  if (can && kn.bm == 256 && !ragged) return 4;
-  return 0;
+// 128-row tile: BN x MODE x output type x K-step x (LDS-DMA or register-staged loads)
+template <typename T, int BN, int MODE, bool OF>
+static int launch_128(const ConvArgs &a, const FwdPlan &pl, dim3 grid, hipStream_t st, const Knobs &kn) {
+  constexpr bool kDma = (MODE == 0);
+  const bool dma = kDma && kn.glds;
+  if (pl.kb == 128) {      // needs Cin*elemsize % 128 == 0; the stem gather keeps the 64-byte step
+    const size_t lds = 2 * (size_t)(128 + BN) * 128;
+    return dma ? launch_igemm(conv_igemm_kernel<T, BN, MODE, OF, 128, kDma>, grid, 256, lds, st, a)
+               : launch_igemm(conv_igemm_kernel<T, BN, MODE, OF, 128, false>, grid, 256, lds, st, a);
+  }
+  const size_t lds = 2 * (size_t)(128 + BN) * 64;
+  return dma ? launch_igemm(conv_igemm_kernel<T, BN, MODE, OF, 64, kDma>, grid, 256, lds, st, a)
+             : launch_igemm(conv_igemm_kernel<T, BN, MODE, OF, 64, false>, grid, 256, lds, st, a);
 }
 
 template <typename T, int MODE>
-static int launch_conv(const ConvArgs &a, bool out_f32, hipStream_t st, const Knobs &kn) {
-  const int bn = (a.Cout <= 64) ? 64 : 128;
-  constexpr bool kDma = (MODE == 0);
-  // the 128-byte K-step needs Cin*elemsize % 128 == 0; the stem gather keeps the 64-byte step
-  const bool wide = MODE == 0 && kn.kb == 128 && (a.Cin * (int)sizeof(T)) % 128 == 0;
-  const int kind = (kDma && (a.ksplit <= 1 || a.slices)) ? conv_tile_kind(a.M, a.Cout, a.Cin, (int)sizeof(T), a.slices != 0, a.segs.n > 0, kn) : 0;
-  const bool huge = kind == 1 || kind == 5, big = kind == 4;
-  const int bm = (big || huge) ? 256 : 128;
-  if (a.stats) {      // fused BatchNorm statistics exist in the staged bf16 epilogues of the 128-row and 256x256 kernels only
-    const bool staged = MODE == 0 && sizeof(T) == 2 && !out_f32 && (a.Cout & 7) == 0 && a.ksplit <= 1 && !big && (huge || wide);
-    if (!staged) return nrpn_fail(NRPN_ERR_ARG, "conv3d_fwd_stats: this shape does not run a kernel with fused statistics (ask nrpn_conv3d_fwd_stats_rows first)");
-  }
-  dim3 grid((unsigned)(cdiv64(a.M, bm) * ((a.Cout + (huge ? 256 : bn) - 1) / (huge ? 256 : bn)) * (a.ksplit > 1 ? a.ksplit : 1)));
-  if (a.tail_ks > 1) {
-    if (kind != 1) return nrpn_fail(NRPN_ERR_ARG, "conv3d_fwd: internal: tail split planned for a shape that does not run the 256x256 tile");
-    const long long mt = cdiv64(a.M, 256), nt = (a.Cout + 255) / 256;
-    grid = dim3((unsigned)(a.tail_tile0 * nt + (mt - a.tail_tile0) * nt * a.tail_ks));
-  }
+static int launch_conv(const ConvArgs &a, const FwdPlan &pl, bool out_f32, hipStream_t st, const Knobs &kn) {
+  // fused BatchNorm statistics exist in the staged bf16 epilogues of the 128-row and 256x256 kernels only
+  if (a.stats && (!pl.stats_rows || out_f32))
+    return nrpn_fail(NRPN_ERR_ARG, "conv3d_fwd_stats: this shape does not run a kernel with fused statistics (ask nrpn_conv3d_fwd_stats_rows first)");
+  const dim3 grid((unsigned)pl.wgs);
   int rc = 0;
-#define NRPN_LC(BN_, OF_, KB_)                                                                                                    \
-  do {                                                                                                                           \
-    const size_t lds_ = 2 * (size_t)(128 + BN_) * KB_;                                                                           \
-    if (kDma && kn.glds) rc = launch_igemm(conv_igemm_kernel<T, BN_, MODE, OF_, KB_, kDma>, grid, lds_, st, a);                  \
-    else rc = launch_igemm(conv_igemm_kernel<T, BN_, MODE, OF_, KB_, false>, grid, lds_, st, a);                                 \
-  } while (0)
-#define NRPN_LC2(BN_, OF_) do { if (wide) NRPN_LC(BN_, OF_, 128); else NRPN_LC(BN_, OF_, 64); } while (0)
-#define NRPN_LBIG(...)                                                                       \
-  do {                                                                                       \
-    NRPN_LDS((conv_igemm_big_kernel<__VA_ARGS__>), (int)lds_);                               \
-    hipLaunchKernelGGL((conv_igemm_big_kernel<__VA_ARGS__>), grid, dim3(512), lds_, st, a);  \
-  } while (0)
-  if (kind == 5) {
-    if constexpr (MODE == 0 && sizeof(T) == 2) {
-      const size_t lds_ = 2 * (size_t)(256 + 256) * 128;
-      if (out_f32) {
-        NRPN_LDS((conv_igemm_big4_kernel<true>), (int)lds_);
-        hipLaunchKernelGGL(conv_igemm_big4_kernel<true>, grid, dim3(256), lds_, st, a);
-      } else {
-        NRPN_LDS((conv_igemm_big4_kernel<false>), (int)lds_);
-        hipLaunchKernelGGL(conv_igemm_big4_kernel<false>, grid, dim3(256), lds_, st, a);
-      }
+  if (pl.kind == 0) {
+    if (a.Cout <= 64) rc = out_f32 ? launch_128<T, 64, MODE, true>(a, pl, grid, st, kn) : launch_128<T, 64, MODE, false>(a, pl, grid, st, kn);
+    else rc = out_f32 ? launch_128<T, 128, MODE, true>(a, pl, grid, st, kn) : launch_128<T, 128, MODE, false>(a, pl, grid, st, kn);
+  }
+  if constexpr (MODE == 0 && sizeof(T) == 2) {      // the 256-row tiles are bf16 LDS-DMA kernels
+    const size_t lbig = 2 * (size_t)(256 + 256) * 128, lws = 3 * (size_t)(256 + 128) * 128;
+    const int dbg = ((kn.dbg & NRPN_CONV_DEBUG_ALIAS_TAPS) ? 1 : 0) | ((kn.dbg & NRPN_CONV_DEBUG_NO_SYNC) ? 2 : 0);
+    if (pl.kind == 5) {
+      rc = out_f32 ? launch_igemm(conv_igemm_big4_kernel<true>, grid, 256, lbig, st, a) : launch_igemm(conv_igemm_big4_kernel<false>, grid, 256, lbig, st, a);
+    } else if (pl.kind == 4) {
+      rc = out_f32 ? launch_igemm(conv_igemm_ws_kernel<true>, grid, 512, lws, st, a) : launch_igemm(conv_igemm_ws_kernel<false>, grid, 512, lws, st, a);
+    } else if (pl.kind == 1 && out_f32) {
+      rc = launch_igemm(conv_igemm_big_kernel<true, false, 0>, grid, 512, lbig, st, a);
+    } else if (pl.kind == 1 && !(kn.stagger || (kn.dbg & NRPN_CONV_DEBUG_STAGGER))) {
+      rc = launch_igemm(conv_igemm_big_kernel<false, false, 0>, grid, 512, lbig, st, a);
+    } else if (pl.kind == 1) {      // DBG != 0: tools-only timing variants (wrong results by construction); the production instantiation has no such branch
+      rc = dbg == 0 ? launch_igemm(conv_igemm_big_kernel<false, true, 0>, grid, 512, lbig, st, a)
+         : dbg == 1 ? launch_igemm(conv_igemm_big_kernel<false, true, 1>, grid, 512, lbig, st, a)
+         : dbg == 2 ? launch_igemm(conv_igemm_big_kernel<false, true, 2>, grid, 512, lbig, st, a)
+                    : launch_igemm(conv_igemm_big_kernel<false, true, 3>, grid, 512, lbig, st, a);
     }
-  } else if (huge) {
-    if constexpr (MODE == 0 && sizeof(T) == 2) {
-      const size_t lds_ = 2 * (size_t)(256 + 256) * 128;
-      const int dbg = ((kn.dbg & NRPN_CONV_DEBUG_ALIAS_TAPS) ? 1 : 0) | ((kn.dbg & NRPN_CONV_DEBUG_NO_SYNC) ? 2 : 0);
-      if (!out_f32 && (kn.stagger || (kn.dbg & NRPN_CONV_DEBUG_STAGGER))) {
-        // DBG != 0: tools-only timing variants (wrong results by construction); the production instantiation has no such branch
-        if (dbg == 0) NRPN_LBIG(false, true, 0);
-        else if (dbg == 1) NRPN_LBIG(false, true, 1);
-        else if (dbg == 2) NRPN_LBIG(false, true, 2);
-        else NRPN_LBIG(false, true, 3);
-      } else if (out_f32) {
-        NRPN_LBIG(true, false, 0);
-      } else {
-        NRPN_LBIG(false, false, 0);
-      }
-    }
-  } else if (big) {
-    if constexpr (MODE == 0 && sizeof(T) == 2) {
-      const size_t lds_ = 3 * (size_t)(256 + 128) * 128;
-      if (out_f32) {
-        NRPN_LDS((conv_igemm_ws_kernel<true>), (int)lds_);
-        hipLaunchKernelGGL(conv_igemm_ws_kernel<true>, grid, dim3(512), lds_, st, a);
-      } else {
-        NRPN_LDS((conv_igemm_ws_kernel<false>), (int)lds_);
-        hipLaunchKernelGGL(conv_igemm_ws_kernel<false>, grid, dim3(512), lds_, st, a);
-      }
-    }
-  } else if (bn == 64) { if (out_f32) NRPN_LC2(64, true); else NRPN_LC2(64, false); }
-  else { if (out_f32) NRPN_LC2(128, true); else NRPN_LC2(128, false); }
-#undef NRPN_LBIG
-#undef NRPN_LC2
-#undef NRPN_LC
+  }
   if (rc) return rc;
   NRPN_LAUNCH_CHECK("conv_igemm");
   return NRPN_OK;
 }
 
-static size_t fwd_workspace_bytes(long long M, int cin, int cout, int ksize, int dtype, const Knobs &kn, const Grid &g) {
-  if (halo_ok(g, cin, cout, ksize == 3 ? 27 : 1, dtype == NRPN_F32 ? 4 : 2, false, kn)) return 0;
-  const int bs = conv_big_split(M, cout, cin, ksize == 3 ? 27 : 1, dtype == NRPN_F32 ? 4 : 2, kn);
-  if (bs) return (size_t)bs * M * cout * 4;
-  const int s = conv_ksplit(M, cout, cin, ksize == 3 ? 27 : 1, dtype == NRPN_F32 ? 4 : 2, kn);
-  if (s > 1) return (size_t)s * M * cout * 4;
-  if (conv_tile_kind(M, cout, cin, dtype == NRPN_F32 ? 4 : 2, false, false, kn) == 1) {
-    const TailSplit t = conv_tail_split(M, cout, cin, ksize == 3 ? 27 : 1, dtype == NRPN_F32 ? 4 : 2, kn);
-    if (t.ks > 1) return (size_t)t.ks * (M - (long long)t.tile0 * 256) * cout * 4;
-  }
-  return 0;
+// The size / plan queries report the plan of a call with a workspace, outputs in the input dtype and no statistics (fwd_plan's defaults).
+// nrpn_conv3d_fwd_plan lets tests assert that a shape really exercises the kernel they claim to cover (codes: FwdPlan::code).
+static FwdPlan fwd_query(int n, int gx, int gy, int gz, int cin, int cout, int ksize, int dtype, const nrpn_conv_opts *opts) {
+  return fwd_plan(conv_shape(n, gx, gy, gz, cin, cout, cout, ksize, dtype), resolve_knobs(opts));
 }
 extern "C" size_t nrpn_conv3d_fwd_workspace_bytes(int n, int gx, int gy, int gz, int cin, int cout, int ksize, int dtype) {
-  return fwd_workspace_bytes((long long)n * gx * gy * gz, cin, cout, ksize, dtype, resolve_knobs(nullptr), Grid{n, gx, gy, gz});
+  return fwd_query(n, gx, gy, gz, cin, cout, ksize, dtype, nullptr).ws_bytes;
 }
 extern "C" size_t nrpn_conv3d_fwd_workspace_bytes_ex(int n, int gx, int gy, int gz, int cin, int cout, int ksize, int dtype,
                                                      const nrpn_conv_opts *opts) {
-  return fwd_workspace_bytes((long long)n * gx * gy * gz, cin, cout, ksize, dtype, resolve_knobs(opts), Grid{n, gx, gy, gz});
-}
-
-// Which kernel a forward / dgrad launch of this shape selects (mirrors launch_conv + conv3d_fwd_impl; lets tests assert that a
-// shape really exercises the kernel they claim to cover): 0 = 128-row tile, 1 = 256x256 tile (8 waves), 2 = 256x256 tile on K slices,
-// 3 = 128-row tile on K slices, 4 = wave-specialised 256x128 (opt-in), 5 = 256x256 tile on 4 waves, 6 = the same on K slices,
-// 7 = halo form of the 3x3x3 kernel (4 x 8 x 8 voxel blocks).
-static int fwd_plan(long long M, int cin, int cout, int ksize, int dtype, const Knobs &kn, const Grid &g) {
-  const int es = dtype == NRPN_F32 ? 4 : 2, taps = ksize == 3 ? 27 : 1;
-  if (halo_ok(g, cin, cout, taps, es, false, kn)) return 7;
-  if (conv_big_split(M, cout, cin, taps, es, kn)) return conv_tile_kind(M, cout, cin, es, true, false, kn) == 5 ? 6 : 2;
-  if (conv_ksplit(M, cout, cin, taps, es, kn) > 1) return 3;
-  return conv_tile_kind(M, cout, cin, es, false, false, kn);
+  return fwd_query(n, gx, gy, gz, cin, cout, ksize, dtype, opts).ws_bytes;
 }
 extern "C" int nrpn_conv3d_fwd_plan(int n, int gx, int gy, int gz, int cin, int cout, int ksize, int dtype) {
-  return fwd_plan((long long)n * gx * gy * gz, cin, cout, ksize, dtype, resolve_knobs(nullptr), Grid{n, gx, gy, gz});
+  return fwd_query(n, gx, gy, gz, cin, cout, ksize, dtype, nullptr).code;
 }
 extern "C" int nrpn_conv3d_fwd_plan_ex(int n, int gx, int gy, int gz, int cin, int cout, int ksize, int dtype, const nrpn_conv_opts *opts) {
-  return fwd_plan((long long)n * gx * gy * gz, cin, cout, ksize, dtype, resolve_knobs(opts), Grid{n, gx, gy, gz});
+  return fwd_query(n, gx, gy, gz, cin, cout, ksize, dtype, opts).code;
+}
+extern "C" int nrpn_conv3d_fwd_stats_rows(int n, int gx, int gy, int gz, int cin, int cout, int ksize, int dtype) {
+  return fwd_query(n, gx, gy, gz, cin, cout, ksize, dtype, nullptr).stats_rows;
+}
+extern "C" int nrpn_conv3d_fwd_stats_rows_ex(int n, int gx, int gy, int gz, int cin, int cout, int ksize, int dtype, const nrpn_conv_opts *opts) {
+  return fwd_query(n, gx, gy, gz, cin, cout, ksize, dtype, opts).stats_rows;
 }
 
-static int conv3d_fwd_impl(const void *x, const void *wp, const float *bias, const void *mask, void *y, long long M, int gx, int gy, int gz, const Segs *segs,
-                           int cin, int cout, int wrows, int ksize, int dtype, int flags, void *workspace, nrpn_stream_t stream,
-                           float *stats = nullptr, const nrpn_conv_opts *opts = nullptr) {
+static int conv3d_fwd_impl(const void *x, const void *wp, const float *bias, const void *mask, void *y, const ConvShape &s, const Segs *segs,
+                           int ksize, int dtype, int flags, void *workspace, nrpn_stream_t stream, float *stats = nullptr,
+                           const nrpn_conv_opts *opts = nullptr) {
+  const int cin = s.cin, cout = s.cout, wrows = s.wrows, es = s.elem_bytes;
   NRPN_REQUIRE(ksize == 1 || ksize == 3, "conv3d_fwd: ksize must be 1 or 3 (got %d)", ksize);
   NRPN_REQUIRE(dtype == NRPN_F32 || dtype == NRPN_BF16, "conv3d_fwd: bad dtype %d", dtype);
-  NRPN_REQUIRE(M > 0 && gx > 0 && gy > 0 && gz > 0 && cin > 0 && cout > 0 && wrows >= cout, "conv3d_fwd: bad sizes");
-  const int es = dtype == NRPN_F32 ? 4 : 2;
+  NRPN_REQUIRE(s.M > 0 && s.gx > 0 && s.gy > 0 && s.gz > 0 && cin > 0 && cout > 0 && wrows >= cout, "conv3d_fwd: bad sizes");
   NRPN_REQUIRE((cin * es) % 64 == 0, "conv3d_fwd: Cin*elemsize must be a multiple of 64 bytes (Cin=%d)", cin);
   NRPN_REQUIRE(x && wp && y, "conv3d_fwd: null pointer");
   const Knobs kn = resolve_knobs(opts, flags);
   ConvArgs a{};
   a.x = x; a.w = wp; a.bias = bias; a.mask = mask; a.y = y; a.stats = stats;
   a.scale = opts ? opts->scale : nullptr;
-  a.M = M;
-  a.X = gx; a.Y = gy; a.Z = gz; a.OX = gx; a.OY = gy; a.OZ = gz;   // classic layout: the kernel splits v into (batch, x, y, z) with these
+  a.M = s.M;
+  a.X = s.gx; a.Y = s.gy; a.Z = s.gz; a.OX = s.gx; a.OY = s.gy; a.OZ = s.gz;   // classic layout: the kernel splits v into (batch, x, y, z) with these
   if (segs) a.segs = *segs;
-  a.dvz = make_fastdiv((unsigned)gz); a.dvy = make_fastdiv((unsigned)gy);
-  a.dvs = make_fastdiv((unsigned)min((long long)gx * gy * gz, (1ll << 31) - 1));      // a scene of >= 2^31 voxels does not pass the 2 GiB check below
-  a.Cin = cin; a.Cout = cout; a.wrows = wrows; a.taps = ksize == 3 ? 27 : 1; a.stride = 1;
+  a.dvz = make_fastdiv((unsigned)s.gz); a.dvy = make_fastdiv((unsigned)s.gy);
+  a.dvs = make_fastdiv((unsigned)min((long long)s.gx * s.gy * s.gz, (1ll << 31) - 1));      // a scene of >= 2^31 voxels does not pass the 2 GiB check below
+  a.Cin = cin; a.Cout = cout; a.wrows = wrows; a.taps = s.taps; a.stride = 1;
   a.flags = flags & 3;
   NRPN_REQUIRE(a.M * cin * es < (1ll << 31) && (long long)a.taps * wrows * cin * es < (1ll << 31),
                "conv3d_fwd: activation / weight tensors must stay below 2 GiB (32-bit buffer offsets)");
   a.x_bytes = (unsigned)(a.M * cin * es); a.w_bytes = (unsigned)((long long)a.taps * wrows * cin * es);
   const bool out_f32 = (flags & NRPN_CONV_OUT_F32) != 0;
   hipStream_t st = as_stream(stream);
-  if (!segs && dtype == NRPN_BF16) {
-    const Grid g{(int)(M / ((long long)gx * gy * gz)), gx, gy, gz};
-    if (halo_ok(g, cin, cout, a.taps, es, out_f32, kn)) {
-      const long long wgs = halo_tiles(g) * ((cout + 255) / 256);
-      NRPN_REQUIRE(wgs < (1ll << 31), "conv3d_fwd: too many tiles");
-      const bool xp = cin % 128 == 0 && !((kn.dbg >> 12) & 3) && (kn.halo_xp == 1 || (kn.halo_xp == 2 && cin >= 256));
-      const int variant = ((kn.dbg >> 12) & 3) | (xp ? 4 : 0) | (out_f32 ? 8 : 0);
-      return nrpn_launch_conv_halo(a, (unsigned)wgs, st, variant);
-    }
+  const FwdPlan pl = fwd_plan(s, kn, workspace != nullptr, out_f32, stats != nullptr);
+  if (pl.code == 7) {
+    NRPN_REQUIRE(pl.wgs < (1ll << 31), "conv3d_fwd: too many tiles");
+    return nrpn_launch_conv_halo(a, (unsigned)pl.wgs, st, pl.halo_variant);
   }
-  const int bs = workspace ? conv_big_split(a.M, cout, cin, a.taps, es, kn) : 0;
-  if (bs) {
-    a.ksplit = bs; a.slices = 1; a.ws = reinterpret_cast<float *>(workspace);
-  } else {
-    a.ksplit = workspace ? conv_ksplit(a.M, cout, cin, a.taps, es, kn) : 1;
-    if (a.ksplit > 1) a.ws = reinterpret_cast<float *>(workspace);
-  }
-  const int nsl = a.ksplit;
-  if (a.ksplit <= 1 && workspace && !segs && !stats && !out_f32 && dtype == NRPN_BF16 && conv_tile_kind(a.M, cout, cin, es, false, false, kn) == 1) {
-    const TailSplit t = conv_tail_split(a.M, cout, cin, a.taps, es, kn);
-    if (t.ks > 1) { a.tail_tile0 = t.tile0; a.tail_ks = t.ks; a.ws = reinterpret_cast<float *>(workspace); }
-  }
-  int rc = (dtype == NRPN_F32) ? launch_conv<float, 0>(a, true, st, kn) : launch_conv<bf16s, 0>(a, out_f32, st, kn);
-  if (!rc && a.tail_ks > 1) {      // bias / scale / ReLU / mask / cast of the tail rows, from their K-slice partials
-    const long long row0 = (long long)a.tail_tile0 * 256, total = (a.M - row0) * cout;
-    const int blocks = (int)min((long long)2048, (total + 255) / 256);
-    const float *b = (flags & NRPN_CONV_BIAS) ? bias : nullptr;
-    const bf16s *mk = a.mask ? reinterpret_cast<const bf16s *>(a.mask) + row0 * cout : nullptr;
-    hipLaunchKernelGGL((splitk_epilogue_kernel<bf16s, false>), dim3(blocks), dim3(256), 0, st, a.ws, b, reinterpret_cast<bf16s *>(y) + row0 * cout, total, cout,
-                       (flags & NRPN_CONV_RELU) ? 1 : 0, a.tail_ks, mk, a.scale);
-    NRPN_LAUNCH_CHECK("splitk_epilogue (tail)");
-    return NRPN_OK;
-  }
-  if (rc || a.ksplit <= 1) return rc;
-  const long long total = a.M * cout;
-  const int blocks = (int)min((long long)4096, (total + 255) / 256);
+  a.ksplit = pl.ksplit; a.slices = pl.slices; a.tail_tile0 = pl.tail.tile0; a.tail_ks = pl.tail.ks;
+  if (pl.ws_slices) a.ws = reinterpret_cast<float *>(workspace);
+  const int rc = (dtype == NRPN_F32) ? launch_conv<float, 0>(a, pl, true, st, kn) : launch_conv<bf16s, 0>(a, pl, out_f32, st, kn);
+  if (rc || !pl.ws_slices) return rc;
+  // bias / scale / ReLU / mask / cast of the rows that ran on K slices (all of them, or the tail's), from their fp32 partials
+  const bool tail = pl.tail.ks > 1;
+  const long long off = pl.ws_row0 * cout, total = (s.M - pl.ws_row0) * cout;
+  const int blocks = (int)min((long long)(tail ? 2048 : 4096), (total + 255) / 256);
   const float *b = (flags & NRPN_CONV_BIAS) ? bias : nullptr;
   const int relu = (flags & NRPN_CONV_RELU) ? 1 : 0;
-  if (dtype == NRPN_F32 || out_f32) {
-    if (dtype == NRPN_F32) hipLaunchKernelGGL((splitk_epilogue_kernel<float, true>), dim3(blocks), dim3(256), 0, st, a.ws, b, y, total, cout, relu, nsl, (const float *)a.mask, a.scale);
-    else hipLaunchKernelGGL((splitk_epilogue_kernel<bf16s, true>), dim3(blocks), dim3(256), 0, st, a.ws, b, y, total, cout, relu, nsl, (const bf16s *)a.mask, a.scale);
-  } else {
-    hipLaunchKernelGGL((splitk_epilogue_kernel<bf16s, false>), dim3(blocks), dim3(256), 0, st, a.ws, b, y, total, cout, relu, nsl, (const bf16s *)a.mask, a.scale);
+  if (dtype == NRPN_F32) {
+    hipLaunchKernelGGL((splitk_epilogue_kernel<float, true>), dim3(blocks), dim3(256), 0, st, a.ws, b, y, total, cout, relu, pl.ws_slices, (const float *)a.mask, a.scale);
+  } else if (out_f32) {
+    hipLaunchKernelGGL((splitk_epilogue_kernel<bf16s, true>), dim3(blocks), dim3(256), 0, st, a.ws, b, y, total, cout, relu, pl.ws_slices, (const bf16s *)a.mask, a.scale);
+  } else {      // the tail split (off > 0) exists for bf16 in / bf16 out only
+    const bf16s *mk = a.mask ? reinterpret_cast<const bf16s *>(a.mask) + off : nullptr;
+    hipLaunchKernelGGL((splitk_epilogue_kernel<bf16s, false>), dim3(blocks), dim3(256), 0, st, a.ws, b, reinterpret_cast<bf16s *>(y) + off, total, cout, relu,
+                       pl.ws_slices, mk, a.scale);
   }
-  NRPN_LAUNCH_CHECK("splitk_epilogue");
+  NRPN_LAUNCH_CHECK(tail ? "splitk_epilogue (tail)" : "splitk_epilogue");
   return NRPN_OK;
 }
 
@@ -1593,25 +1440,8 @@ extern "C" int nrpn_conv3d_fwd(const void *x, const void *wp, const float *bias,
                                nrpn_stream_t stream) {
   NRPN_REQUIRE(n > 0 && gx > 0 && gy > 0 && gz > 0, "conv3d_fwd: bad sizes");
   NRPN_REQUIRE(!relu_mask || !(flags & NRPN_CONV_OUT_F32) || dtype == NRPN_F32, "conv3d_fwd: relu_mask needs outputs in the input dtype");
-  return conv3d_fwd_impl(x, wp, bias, relu_mask, y, (long long)n * gx * gy * gz, gx, gy, gz, nullptr, cin, cout, wrows, ksize, dtype, flags,
+  return conv3d_fwd_impl(x, wp, bias, relu_mask, y, conv_shape(n, gx, gy, gz, cin, cout, wrows, ksize, dtype), nullptr, ksize, dtype, flags,
                          workspace, stream);
-}
-
-// Rows P of the partial-statistics buffer [P][2][Cout] a forward launch of this shape fills when asked to (0 = the shape runs a kernel
-// without fused statistics: K-sliced, fp32, narrow K-step or the opt-in variants -- use nrpn_bn_stats on the output instead).
-static int fwd_stats_rows(long long M, int cin, int cout, int ksize, int dtype, const Knobs &kn, const Grid &g) {
-  if (dtype != NRPN_BF16 || (cout & 7) != 0 || !kn.glds || kn.bm == 256) return 0;
-  const int plan = fwd_plan(M, cin, cout, ksize, dtype, kn, g);
-  if (plan == 7) return (int)(halo_tiles(g) * 2);
-  if (plan == 1 || plan == 5) return (int)(cdiv64(M, 256) * 2);
-  if (plan != 0 || kn.kb != 128 || (cin * 2) % 128 != 0) return 0;
-  return (int)(cdiv64(M, 128) * (cout <= 64 ? 4 : 2));
-}
-extern "C" int nrpn_conv3d_fwd_stats_rows(int n, int gx, int gy, int gz, int cin, int cout, int ksize, int dtype) {
-  return fwd_stats_rows((long long)n * gx * gy * gz, cin, cout, ksize, dtype, resolve_knobs(nullptr), Grid{n, gx, gy, gz});
-}
-extern "C" int nrpn_conv3d_fwd_stats_rows_ex(int n, int gx, int gy, int gz, int cin, int cout, int ksize, int dtype, const nrpn_conv_opts *opts) {
-  return fwd_stats_rows((long long)n * gx * gy * gz, cin, cout, ksize, dtype, resolve_knobs(opts), Grid{n, gx, gy, gz});
 }
 
 // nrpn_conv3d_fwd + partial BatchNorm statistics of the stored outputs from the same launch (finish them with nrpn_bn_stats_finalize).
@@ -1620,7 +1450,7 @@ extern "C" int nrpn_conv3d_fwd_stats(const void *x, const void *wp, const float 
   NRPN_REQUIRE(n > 0 && gx > 0 && gy > 0 && gz > 0 && stats, "conv3d_fwd_stats: bad sizes / null statistics buffer");
   NRPN_REQUIRE(nrpn_conv3d_fwd_stats_rows(n, gx, gy, gz, cin, cout, ksize, dtype) > 0 && !(flags & NRPN_CONV_OUT_F32) && wrows == cout,
                "conv3d_fwd_stats: this shape does not run a kernel with fused statistics");
-  return conv3d_fwd_impl(x, wp, bias, nullptr, y, (long long)n * gx * gy * gz, gx, gy, gz, nullptr, cin, cout, wrows, ksize, dtype, flags,
+  return conv3d_fwd_impl(x, wp, bias, nullptr, y, conv_shape(n, gx, gy, gz, cin, cout, wrows, ksize, dtype), nullptr, ksize, dtype, flags,
                          nullptr, stream, stats);
 }
 
@@ -1635,12 +1465,11 @@ extern "C" int nrpn_conv3d_fwd_ex(const void *x, const void *wp, const float *bi
   float *stats = opts ? opts->stats : nullptr;
   NRPN_REQUIRE(!mask || !(flags & NRPN_CONV_OUT_F32) || dtype == NRPN_F32, "conv3d_fwd_ex: relu_mask needs outputs in the input dtype");
   if (stats) {
-    NRPN_REQUIRE(fwd_stats_rows((long long)n * gx * gy * gz, cin, cout, ksize, dtype, resolve_knobs(opts), Grid{n, gx, gy, gz}) > 0 && !(flags & NRPN_CONV_OUT_F32) &&
-                     wrows == cout && !mask,
+    NRPN_REQUIRE(nrpn_conv3d_fwd_stats_rows_ex(n, gx, gy, gz, cin, cout, ksize, dtype, opts) > 0 && !(flags & NRPN_CONV_OUT_F32) && wrows == cout && !mask,
                  "conv3d_fwd_ex: this shape / plan does not run a kernel with fused statistics (nrpn_conv3d_fwd_stats_rows_ex)");
     workspace = nullptr;
   }
-  return conv3d_fwd_impl(x, wp, bias, mask, y, (long long)n * gx * gy * gz, gx, gy, gz, nullptr, cin, cout, wrows, ksize, dtype, flags,
+  return conv3d_fwd_impl(x, wp, bias, mask, y, conv_shape(n, gx, gy, gz, cin, cout, wrows, ksize, dtype), nullptr, ksize, dtype, flags,
                          workspace, stream, stats, opts);
 }
 
@@ -1649,58 +1478,23 @@ extern "C" int nrpn_conv3d_fwd_ragged(const void *x, const void *wp, const float
   Segs sg{};
   long long M = 0;
   if (int rc = fill_segs(sg, nseg, dims, M)) return rc;
-  return conv3d_fwd_impl(x, wp, bias, nullptr, y, M, 1, 1, 1, &sg, cin, cout, wrows, ksize, dtype, flags, workspace, stream);
+  return conv3d_fwd_impl(x, wp, bias, nullptr, y, conv_shape_ragged(M, cin, cout, wrows, ksize, dtype), &sg, ksize, dtype, flags, workspace, stream);
 }
 
 // Row-list form of the forward / dgrad launch: output rows = the `nrows` voxels of `rows` ([nrows][2] u32 = {voxel id in the ragged space of
 // `dims`, tap word}; csrc/cone.hip builds such lists) -- x, y and relu_mask are indexed by voxel id, rows outside the list are neither
-// read as outputs nor written.  128-row tiles of conv_igemm_kernel, no K slices (the lists are short: one launch, no workspace).
+// read as outputs nor written.  128-row tiles of conv_igemm_kernel; short lists on K slices, the last round of long ones too (RowsPlan).
 // tools-only A/B switch (include/nerfrpn_tools.h): 256x256 tile for long row lists.  OFF by default -- measured on one box, bench step,
 // S3 = 33 k rows = 130 tiles: 9.47 ms with it against 9.43 ms on 128-row tiles (three alternating runs each): the 8-wave tile's
 // chunk-outer K order counts on an XCD's workgroups sweeping one contiguous voxel slab through its L2, which a gathered list is not.
 static std::atomic<int> g_rows_big{0};
 extern "C" int nrpn_set_rows_big_tile(int on) { g_rows_big = on ? 1 : 0; return NRPN_OK; }
-
-// Short lists (the S0 / S1 cones: 2-70 tiles) would leave the chip idle behind a 54-step K loop: they run on K slices whose fp32 partials
-// ([slices][nrows][Cout], plain stores) are summed in slice order and scattered by rows_epilogue_kernel.
-static int rows_ksplit(long long nrows, int cin, int cout, int taps, int es) {
-  const long long tiles = cdiv64(nrows, 128) * ((cout + 127) / 128);
-  const int nk = taps * (cin * es / 128);
-  if (tiles >= 128 || nk < 12) return 1;
-  long long s = (256 + tiles - 1) / tiles;
-  if (s > nk / 6) s = nk / 6;
-  if (s > 32) s = 32;
-  if (s < 2) return 1;
-  const long long per = (nk + s - 1) / s;
-  s = (nk + per - 1) / per;                  // no empty slice
-  return s < 2 ? 1 : (int)s;
-}
-// Long lists: the 128-row tiling of the S3 cone is a little more than one round of the chip's 512 workgroup slots (33-35 k rows x 2 column
-// tiles = 518-552 workgroups), i.e. two rounds in time.  The M tiles of the short last round run on K slices (cf. conv_tail_split).
-static std::atomic<int> g_rows_tail{1};     // tools-only A/B switch
+static std::atomic<int> g_rows_tail{1};     // tools-only A/B switch of the tail split
 extern "C" int nrpn_set_rows_tail_split(int on) { g_rows_tail = on ? 1 : 0; return NRPN_OK; }
-static TailSplit rows_tail_split(long long nrows, int cin, int cout, int taps, int es) {
-  TailSplit none{0, 0};
-  if (!g_rows_tail.load(std::memory_order_relaxed)) return none;
-  const long long mt = cdiv64(nrows, 128), nt = (cout + 127) / 128, tiles = mt * nt;
-  const long long rem = tiles % 512;
-  if (tiles <= 512 || rem == 0 || rem > 256) return none;
-  const long long tail_mt = (rem + nt - 1) / nt;
-  const int nk = taps * (cin * es / 128);
-  int ks = (int)(512 / (tail_mt * nt));
-  if (ks > 8) ks = 8;
-  while (ks > 1 && nk / ks < 6) --ks;
-  if (ks < 2) return none;
-  const int per = (nk + ks - 1) / ks;
-  ks = (nk + per - 1) / per;
-  return ks >= 2 ? TailSplit{(int)(mt - tail_mt), ks} : none;
-}
+static RowsKnobs rows_knobs() { return RowsKnobs{g_rows_big.load(std::memory_order_relaxed), g_rows_tail.load(std::memory_order_relaxed)}; }
+
 extern "C" size_t nrpn_conv3d_fwd_rows_workspace_bytes(int64_t nrows, int cin, int cout, int ksize, int dtype) {
-  const int es = dtype == NRPN_F32 ? 4 : 2, taps = ksize == 3 ? 27 : 1;
-  const int s = rows_ksplit(nrows, cin, cout, taps, es);
-  if (s > 1) return (size_t)s * nrows * cout * 4;
-  const TailSplit t = rows_tail_split(nrows, cin, cout, taps, es);
-  return t.ks > 1 ? (size_t)t.ks * (nrows - (long long)t.tile0 * 128) * cout * 4 : 0;
+  return rows_plan(conv_shape_ragged(nrows, cin, cout, cout, ksize, dtype), rows_knobs()).ws_bytes;
 }
 
 extern "C" int nrpn_conv3d_fwd_rows(const void *x, const void *wp, const float *bias, void *y, const uint32_t *rows, int64_t nrows, int nseg,
@@ -1710,7 +1504,8 @@ extern "C" int nrpn_conv3d_fwd_rows(const void *x, const void *wp, const float *
   NRPN_REQUIRE(dtype == NRPN_F32 || dtype == NRPN_BF16, "conv3d_fwd_rows: bad dtype %d", dtype);
   NRPN_REQUIRE(x && wp && y && rows && nrows >= 0 && cin > 0 && cout > 0 && wrows >= cout, "conv3d_fwd_rows: bad arguments");
   if (nrows == 0) return NRPN_OK;
-  const int es = dtype == NRPN_F32 ? 4 : 2;
+  const ConvShape s = conv_shape_ragged(nrows, cin, cout, wrows, ksize, dtype);
+  const int es = s.elem_bytes;
   NRPN_REQUIRE((cin * es) % 128 == 0, "conv3d_fwd_rows: Cin*elemsize must be a multiple of 128 bytes (Cin=%d)", cin);
   const bool out_f32 = (flags & NRPN_CONV_OUT_F32) != 0 || dtype == NRPN_F32;
   NRPN_REQUIRE(!relu_mask || !(flags & NRPN_CONV_OUT_F32) || dtype == NRPN_F32, "conv3d_fwd_rows: relu_mask needs outputs in the input dtype");
@@ -1720,50 +1515,36 @@ extern "C" int nrpn_conv3d_fwd_rows(const void *x, const void *wp, const float *
   a.x = x; a.w = wp; a.bias = bias; a.mask = relu_mask; a.y = y; a.rows = rows;
   a.M = nrows;
   a.X = a.Y = a.Z = a.OX = a.OY = a.OZ = 1;
-  a.Cin = cin; a.Cout = cout; a.wrows = wrows; a.taps = ksize == 3 ? 27 : 1; a.stride = 1; a.flags = flags & 3; a.ksplit = 1;
+  a.Cin = cin; a.Cout = cout; a.wrows = wrows; a.taps = s.taps; a.stride = 1; a.flags = flags & 3;
   NRPN_REQUIRE(total * cin * es < (1ll << 31) && total * cout * 4 < (1ll << 32) && (long long)a.taps * wrows * cin * es < (1ll << 31),
                "conv3d_fwd_rows: activation / weight tensors must stay below 2 GiB (32-bit buffer offsets)");
   a.x_bytes = (unsigned)(total * cin * es); a.w_bytes = (unsigned)((long long)a.taps * wrows * cin * es);
   hipStream_t st = as_stream(stream);
-  const int ks = workspace ? rows_ksplit(nrows, cin, cout, a.taps, es) : 1;
-  if (ks > 1) { a.ksplit = ks; a.ws = reinterpret_cast<float *>(workspace); }
-  // opt-in (nrpn_set_rows_big_tile): long bf16 lists (>= 96 tiles of 256 rows) of wide layers on the 256x256 tile
-  if (g_rows_big.load(std::memory_order_relaxed) && dtype == NRPN_BF16 && !out_f32 && ks == 1 && cout >= 256 && (cout & 7) == 0 &&
-      cdiv64(nrows, 256) * ((cout + 255) / 256) >= 96) {
-    const size_t lds_big = 2 * (size_t)(256 + 256) * 128;
-    dim3 gbig((unsigned)(cdiv64(nrows, 256) * ((cout + 255) / 256)));
-    NRPN_LDS((conv_igemm_big_kernel<false, true, 0, true>), (int)lds_big);
-    hipLaunchKernelGGL((conv_igemm_big_kernel<false, true, 0, true>), gbig, dim3(512), lds_big, st, a);
+  const RowsPlan pl = rows_plan(s, rows_knobs(), workspace != nullptr, out_f32);
+  const dim3 grid((unsigned)pl.wgs);
+  a.ksplit = pl.ksplit; a.tail_tile0 = pl.tail.tile0; a.tail_ks = pl.tail.ks;
+  if (pl.big) {
+    if (int rc = launch_igemm(conv_igemm_big_kernel<false, true, 0, true>, grid, 512, 2 * (size_t)(256 + 256) * 128, st, a)) return rc;
     NRPN_LAUNCH_CHECK("conv3d_fwd_rows (256x256 tile)");
     return NRPN_OK;
   }
-  dim3 grid((unsigned)(cdiv64(nrows, 128) * ((cout + 127) / 128) * ks));
-  if (ks == 1 && workspace) {
-    const TailSplit t = rows_tail_split(nrows, cin, cout, a.taps, es);
-    if (t.ks > 1) {
-      a.tail_tile0 = t.tile0; a.tail_ks = t.ks; a.ws = reinterpret_cast<float *>(workspace);
-      const long long mt = cdiv64(nrows, 128), nt = (cout + 127) / 128;
-      grid = dim3((unsigned)(t.tile0 * nt + (mt - t.tile0) * nt * t.ks));
-    }
-  }
+  if (pl.ws_slices) a.ws = reinterpret_cast<float *>(workspace);
   const size_t lds_ = 2 * (size_t)(128 + 128) * 128;
   int rc;
-  if (dtype == NRPN_F32) rc = launch_igemm(conv_igemm_kernel<float, 128, 0, true, 128, true, 128, true>, grid, lds_, st, a);
-  else if (out_f32) rc = launch_igemm(conv_igemm_kernel<bf16s, 128, 0, true, 128, true, 128, true>, grid, lds_, st, a);
-  else rc = launch_igemm(conv_igemm_kernel<bf16s, 128, 0, false, 128, true, 128, true>, grid, lds_, st, a);
+  if (dtype == NRPN_F32) rc = launch_igemm(conv_igemm_kernel<float, 128, 0, true, 128, true, 128, true>, grid, 256, lds_, st, a);
+  else if (out_f32) rc = launch_igemm(conv_igemm_kernel<bf16s, 128, 0, true, 128, true, 128, true>, grid, 256, lds_, st, a);
+  else rc = launch_igemm(conv_igemm_kernel<bf16s, 128, 0, false, 128, true, 128, true>, grid, 256, lds_, st, a);
   if (rc) return rc;
   NRPN_LAUNCH_CHECK("conv3d_fwd_rows");
-  if (ks > 1 || a.tail_ks > 1) {
-    const long long row0 = a.tail_ks > 1 ? (long long)a.tail_tile0 * 128 : 0;      // the partials cover the rows from row0 on
-    const int nsl = a.tail_ks > 1 ? a.tail_ks : ks;
-    const long long total = (nrows - row0) * cout;
-    const int blocks = (int)min((long long)2048, (total + 255) / 256);
+  if (pl.ws_slices) {      // the partials cover the rows from ws_row0 on
+    const long long ptotal = (nrows - pl.ws_row0) * cout;
+    const int blocks = (int)min((long long)2048, (ptotal + 255) / 256);
     const float *b = (flags & NRPN_CONV_BIAS) ? bias : nullptr;
     const int relu = (flags & NRPN_CONV_RELU) ? 1 : 0;
-    const uint32_t *rw = rows + 2 * row0;
-    if (dtype == NRPN_F32) hipLaunchKernelGGL((rows_epilogue_kernel<float, true>), dim3(blocks), dim3(256), 0, st, a.ws, b, y, total, cout, relu, nsl, (const float *)relu_mask, rw);
-    else if (out_f32) hipLaunchKernelGGL((rows_epilogue_kernel<bf16s, true>), dim3(blocks), dim3(256), 0, st, a.ws, b, y, total, cout, relu, nsl, (const bf16s *)relu_mask, rw);
-    else hipLaunchKernelGGL((rows_epilogue_kernel<bf16s, false>), dim3(blocks), dim3(256), 0, st, a.ws, b, y, total, cout, relu, nsl, (const bf16s *)relu_mask, rw);
+    const uint32_t *rw = rows + 2 * pl.ws_row0;
+    if (dtype == NRPN_F32) hipLaunchKernelGGL((rows_epilogue_kernel<float, true>), dim3(blocks), dim3(256), 0, st, a.ws, b, y, ptotal, cout, relu, pl.ws_slices, (const float *)relu_mask, rw);
+    else if (out_f32) hipLaunchKernelGGL((rows_epilogue_kernel<bf16s, true>), dim3(blocks), dim3(256), 0, st, a.ws, b, y, ptotal, cout, relu, pl.ws_slices, (const bf16s *)relu_mask, rw);
+    else hipLaunchKernelGGL((rows_epilogue_kernel<bf16s, false>), dim3(blocks), dim3(256), 0, st, a.ws, b, y, ptotal, cout, relu, pl.ws_slices, (const bf16s *)relu_mask, rw);
     NRPN_LAUNCH_CHECK("rows_epilogue");
   }
   return NRPN_OK;
@@ -1790,8 +1571,10 @@ static int stem_fwd_impl(const void *x, const void *wp, const float *bias, void 
     a.x_bytes = (unsigned)xb; a.w_bytes = 0;
   }
   const Knobs kn = resolve_knobs(opts);
-  if (dtype == NRPN_F32) return launch_conv<float, 1>(a, true, as_stream(stream), kn);
-  return launch_conv<bf16s, 1>(a, false, as_stream(stream), kn);
+  // 4 input channels: the 128-row tile with the 64-byte K-step, never sliced
+  const FwdPlan pl = fwd_plan(ConvShape{a.M, n, a.OX, a.OY, a.OZ, 4, cout, cout, 343, dtype == NRPN_F32 ? 4 : 2, false}, kn, false);
+  if (dtype == NRPN_F32) return launch_conv<float, 1>(a, pl, true, as_stream(stream), kn);
+  return launch_conv<bf16s, 1>(a, pl, false, as_stream(stream), kn);
 }
 
 extern "C" int nrpn_conv3d_stem_fwd(const void *x, const void *wp, const float *bias, void *y, int n, int gx, int gy, int gz, int cout,
@@ -2854,16 +2637,6 @@ __global__ void unpack_stem_zrow_kernel(const float *__restrict__ gp, int cout, 
   gw[i] = accumulate ? gw[i] + v : v;
 }
 
-static bool stem_zrow_ok(int gz, int cout, int stride) { return stride == 2 && gz % 2 == 0 && cout == 64; }
-static int stem_zrow_slices(long long M, int elem_bytes) {
-  const long long chunks = (M + (elem_bytes == 2 ? 64 : 32) - 1) / (elem_bytes == 2 ? 64 : 32);
-  long long s = 73;                                   // 7 dx x 73 slices = 511 workgroups = two per CU
-  if (s > chunks / 8) s = chunks / 8;
-  if (s < 1) s = 1;
-  const long long per = (chunks + s - 1) / s;
-  return (int)((chunks + per - 1) / per);             // no empty slice
-}
-
 // bias gradient = ordered sum of the per-slice column sums the wgrad workgroups left in the workspace
 __global__ void bias_finalize_kernel(const float *__restrict__ part, int slices, int wrows, int cout, float *__restrict__ gbias, int accumulate) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2896,94 +2669,77 @@ __global__ void tap_mask_kernel(unsigned *__restrict__ mask, long long M, int X,
   mask[v] = m;
 }
 
+// Weight-gradient plans: conv_plan.h (WgPlan).  A call snapshots the three tools switches once; the plan and the launch read the snapshot.
 static std::atomic<int> g_wgrad_tr_mode{1};
 extern "C" int nrpn_set_wgrad_transpose_read(int on) { g_wgrad_tr_mode = on ? 1 : 0; return NRPN_OK; }
-
-static std::atomic<int> g_wgrad_big{1};   // 1: 256x256 wgrad tiles for bf16 layers with Cout, Cin >= 256 (tuning knob)
+static std::atomic<int> g_wgrad_big{1};
 extern "C" int nrpn_set_wgrad_big_tile(int on) { g_wgrad_big = on ? 1 : 0; return NRPN_OK; }
-
-// How the voxel axis is cut: every (tile, tap, slice) workgroup writes one partial gradient; the slices are summed by the
-// unpack kernels.  `ksplit` is trimmed so that no slice is empty (every partial is fully written).
-// two taps per workgroup (conv_wgrad_kernel<..., PACK2>): dense k3 layers whose input row fits half a B-tile row (Cin <= 64)
 static std::atomic<int> g_wgrad_pack2{1};
 extern "C" int nrpn_set_wgrad_pack2(int on) { g_wgrad_pack2 = on ? 1 : 0; return NRPN_OK; }
-static bool wgrad_pack2(int cin, int taps, int mode) { return g_wgrad_pack2.load(std::memory_order_relaxed) && mode == 0 && taps == 27 && cin <= 64; }
-struct WgPlan { int ksplit; bool big; };
-static WgPlan wgrad_plan(long long M, int wrows, int ncols, int taps, int elem_bytes, int mode, int cout, int cin) {
-  WgPlan pl{1, false};
-  const int kv = elem_bytes == 4 ? 32 : 64;
-  const long long chunks = (M + kv - 1) / kv;
-  long long ks = 1;
-  const bool big_pack2 = g_wgrad_pack2.load(std::memory_order_relaxed) && taps == 27 && cin == 128;      // conv_wgrad_big_kernel<false, PACK2>
-  if (mode == 0 && elem_bytes == 2 && g_wgrad_big && g_wgrad_tr_mode != 0 && cout >= 256 && (cin >= 256 || big_pack2)) {
-    // 256x256 tiles, one 128 KB-LDS workgroup per CU: pick the slice count with the lowest modelled time
-    //   t(k) = MFMA time / (fill of whole rounds of 256 CUs) + (k + 1) partial-gradient passes through HBM,
-    // e.g. 256->256 @40^3: 27 tiles x 9 slices = 243 workgroups (95 % of a round) instead of 8 (84 %); 512->512 @20^3 stays at 2
-    // slices because each extra slice costs another 28 MB partial.
-    const int tiles = ((wrows + 255) / 256) * ((cin + 255) / 256) * ((big_pack2 && cin == 128) ? 14 : taps);
-    const double flops = 2.0 * (double)M * wrows * cin * taps;
-    const double part_bytes = 4.0 * (double)taps * wrows * cin;
-    double best = 1e30;
-    for (long long k = 1; k <= 64 && k <= max(1ll, chunks / 16); ++k) {
-      const double rounds = (double)tiles * k / 256.0;
-      const long long whole = (long long)rounds + ((double)(long long)rounds < rounds ? 1 : 0);
-      const double fill = rounds / (double)whole;
-      if (fill < 0.5) continue;
-      const double t = flops / (fill * 9.0e14) + (double)(k + 1) * part_bytes / 3.0e12;
-      if (t < best) { best = t; pl.big = true; ks = k; }
-    }
-  }
-  if (!pl.big) {
-    const int tiles = ((wrows + 127) / 128) * ((ncols + 127) / 128) * (wgrad_pack2(cin, taps, mode) ? 14 : taps);
-    ks = (1024 + tiles - 1) / tiles;
-    if (ks > chunks / 16) ks = chunks / 16;     // >= 16 chunks per workgroup so the 128x128 epilogue stays amortised
-    if (ks < 1) ks = 1;
-    if (ks > 4096) ks = 4096;
-  }
-  const long long per = (chunks + ks - 1) / ks;
-  pl.ksplit = (int)((chunks + per - 1) / per);
-  return pl;
+static WgKnobs wg_knobs() {
+  return WgKnobs{g_wgrad_big.load(std::memory_order_relaxed), g_wgrad_tr_mode.load(std::memory_order_relaxed), g_wgrad_pack2.load(std::memory_order_relaxed)};
 }
 
 template <typename T, int MODE>
-static int launch_wgrad(WgradArgs a, int ntiles_n, hipStream_t st) {
-  a.ntiles_n = ntiles_n;
+static int launch_wgrad(WgradArgs a, const WgPlan &pl, hipStream_t st) {
+  a.ksplit = pl.ksplit; a.ntiles_n = pl.ntiles_n;
+  const dim3 grid((unsigned)pl.wgs);
+  if constexpr (MODE == 0 && sizeof(T) == 2) {
+    if (pl.big) {
+      const size_t lds = 2 * 4 * (size_t)64 * 256;
+      if (pl.form == WG_BIG_ROWS) {
+        NRPN_LDS(conv_wgrad_big_kernel<true>, (int)lds);
+        hipLaunchKernelGGL(conv_wgrad_big_kernel<true>, grid, dim3(512), lds, st, a);
+      } else if (pl.form == WG_BIG_PAIR) {
+        NRPN_LDS((conv_wgrad_big_kernel<false, true>), (int)lds);
+        hipLaunchKernelGGL((conv_wgrad_big_kernel<false, true>), grid, dim3(512), lds, st, a);
+      } else {
+        NRPN_LDS(conv_wgrad_big_kernel<false>, (int)lds);
+        hipLaunchKernelGGL(conv_wgrad_big_kernel<false>, grid, dim3(512), lds, st, a);
+      }
+      NRPN_LAUNCH_CHECK("conv_wgrad_big");
+      return NRPN_OK;
+    }
+  }
   const size_t lds = 4 * (size_t)WgCfg<T>::KV * WgCfg<T>::RS;
-  const bool tr = g_wgrad_tr_mode != 0;
-  dim3 grid((unsigned)(((a.wrows + 127) / 128) * ntiles_n * (MODE == 0 ? a.taps : 1) * a.ksplit));
   if constexpr (MODE == 0) {
-    if (a.rows) {      // row-list form (transpose-read fragments only)
+    if (pl.form == WG_ROWS) {      // row-list form (transpose-read fragments only)
       NRPN_LDS((conv_wgrad_kernel<T, 0, true, true>), (int)lds);
       hipLaunchKernelGGL((conv_wgrad_kernel<T, 0, true, true>), grid, dim3(256), lds, st, a);
       NRPN_LAUNCH_CHECK("conv_wgrad_rows");
       return NRPN_OK;
     }
-  }
-  if constexpr (MODE == 0) {
-    if (tr && !a.rows && wgrad_pack2(a.Cin, a.taps, 0)) {        // two taps per workgroup: 14 instead of 27 workgroups per (tile, slice)
-      grid = dim3((unsigned)(((a.wrows + 127) / 128) * 14 * a.ksplit));
-      a.ntiles_n = 1;
+    if (pl.form == WG_PAIR) {      // two taps per workgroup: 14 instead of 27 workgroups per (tile, slice)
       NRPN_LDS((conv_wgrad_kernel<T, 0, true, false, true>), (int)lds);
       hipLaunchKernelGGL((conv_wgrad_kernel<T, 0, true, false, true>), grid, dim3(256), lds, st, a);
       NRPN_LAUNCH_CHECK("conv_wgrad_pack2");
       return NRPN_OK;
     }
   }
-  if (tr) NRPN_LDS((conv_wgrad_kernel<T, MODE, true>), (int)lds);
+  if (pl.tr) NRPN_LDS((conv_wgrad_kernel<T, MODE, true>), (int)lds);
   else NRPN_LDS((conv_wgrad_kernel<T, MODE, false>), (int)lds);
-  if (tr) hipLaunchKernelGGL((conv_wgrad_kernel<T, MODE, true>), grid, dim3(256), lds, st, a);
+  if (pl.tr) hipLaunchKernelGGL((conv_wgrad_kernel<T, MODE, true>), grid, dim3(256), lds, st, a);
   else hipLaunchKernelGGL((conv_wgrad_kernel<T, MODE, false>), grid, dim3(256), lds, st, a);
   NRPN_LAUNCH_CHECK("conv_wgrad");
   return NRPN_OK;
 }
 
-// workspace = [tap mask: M u32 (k3 only)][bias partials: slices * wrows f32]
-static size_t wgrad_mask_bytes(long long M, int ksize) { return ksize == 3 ? (size_t)((M * 4 + 255) / 256 * 256) : 0; }
-extern "C" size_t nrpn_conv3d_wgrad_bias_offset(int n, int gx, int gy, int gz, int ksize) { return wgrad_mask_bytes((long long)n * gx * gy * gz, ksize); }
+static WgPlan wgrad_query(int n, int gx, int gy, int gz, int cin, int cout, int wrows, int ksize, int dtype) {
+  return wgrad_plan(conv_shape(n, gx, gy, gz, cin, cout, wrows, ksize, dtype), cin, 0, wg_knobs());
+}
+extern "C" size_t nrpn_conv3d_wgrad_bias_offset(int n, int gx, int gy, int gz, int ksize) {
+  return wgrad_mask_bytes((long long)n * gx * gy * gz, ksize == 3 ? 27 : 1);
+}
 extern "C" size_t nrpn_conv3d_wgrad_workspace_bytes(int n, int gx, int gy, int gz, int cin, int cout, int wrows, int ksize, int dtype) {
-  const long long M = (long long)n * gx * gy * gz;
-  const int slices = wgrad_plan(M, wrows, cin, ksize == 3 ? 27 : 1, dtype == NRPN_F32 ? 4 : 2, 0, cout, cin).ksplit;
-  return wgrad_mask_bytes(M, ksize) + (size_t)slices * wrows * 4;
+  const WgPlan pl = wgrad_query(n, gx, gy, gz, cin, cout, wrows, ksize, dtype);
+  return pl.bias_off + pl.bias_bytes;
+}
+// 1 when a wgrad launch of this shape runs conv_wgrad_big_kernel (256x256 tile), 0 for the 128x128 kernel
+extern "C" int nrpn_conv3d_wgrad_plan(int n, int gx, int gy, int gz, int cin, int cout, int wrows, int ksize, int dtype) {
+  return wgrad_query(n, gx, gy, gz, cin, cout, wrows, ksize, dtype).big ? 1 : 0;
+}
+extern "C" int nrpn_conv3d_wgrad_slices(int n, int gx, int gy, int gz, int cin, int cout, int wrows, int ksize, int dtype) {
+  return wgrad_query(n, gx, gy, gz, cin, cout, wrows, ksize, dtype).ksplit;
 }
 
 static int conv3d_wgrad_impl(const void *x, const void *dy, float *gw_packed, float *gbias, long long M, int gx, int gy, int gz,
@@ -3015,34 +2771,13 @@ static int conv3d_wgrad_impl(const void *x, const void *dy, float *gw_packed, fl
   if (ksize == 3 && !mask_ready && !rows)
     hipLaunchKernelGGL(tap_mask_kernel, dim3((unsigned)cdiv64(a.M, 256)), dim3(256), 0, st, reinterpret_cast<unsigned *>(workspace), a.M, gx, gy, gz,
                        a.segs);
-  float *bias_part = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + (rows ? 0 : wgrad_mask_bytes(a.M, ksize)));
+  const WgPlan pl = wgrad_plan(ConvShape{M, 0, gx, gy, gz, cin, cout, wrows, a.taps, es, segs != nullptr}, cin, 0, wg_knobs(), rows != nullptr);
+  float *bias_part = reinterpret_cast<float *>(reinterpret_cast<char *>(workspace) + pl.bias_off);
   a.gbias = gbias ? bias_part : nullptr;
-  const WgPlan pl = wgrad_plan(a.M, wrows, cin, a.taps, es, 0, cout, cin);
-  a.ksplit = pl.ksplit;
   a.slice_stride = (long long)a.taps * wrows * cin;
-  int rc = NRPN_OK;
-  if (dtype == NRPN_F32) rc = launch_wgrad<float, 0>(a, (cin + 127) / 128, st);
-  else if (!pl.big) rc = launch_wgrad<bf16s, 0>(a, (cin + 127) / 128, st);
-  else {
-    a.ntiles_n = (cin + 255) / 256;
-    const int tiles = ((wrows + 255) / 256) * a.ntiles_n * a.taps;
-    const size_t lds = 2 * 4 * (size_t)64 * 256;
-    if (a.rows) {
-      NRPN_LDS(conv_wgrad_big_kernel<true>, (int)lds);
-      hipLaunchKernelGGL(conv_wgrad_big_kernel<true>, dim3((unsigned)(tiles * a.ksplit)), dim3(512), lds, st, a);
-    } else if (cin == 128 && a.taps == 27) {          // wgrad_plan only says `big` for Cin 128 when the pair form is on
-      const int tiles2 = ((wrows + 255) / 256) * 14;
-      a.ntiles_n = 1;
-      NRPN_LDS((conv_wgrad_big_kernel<false, true>), (int)lds);
-      hipLaunchKernelGGL((conv_wgrad_big_kernel<false, true>), dim3((unsigned)(tiles2 * a.ksplit)), dim3(512), lds, st, a);
-    } else {
-      NRPN_LDS(conv_wgrad_big_kernel<false>, (int)lds);
-      hipLaunchKernelGGL(conv_wgrad_big_kernel<false>, dim3((unsigned)(tiles * a.ksplit)), dim3(512), lds, st, a);
-    }
-    NRPN_LAUNCH_CHECK("conv_wgrad_big");
-  }
+  const int rc = (dtype == NRPN_F32) ? launch_wgrad<float, 0>(a, pl, st) : launch_wgrad<bf16s, 0>(a, pl, st);
   if (rc || !gbias || defer_bias) return rc;
-  hipLaunchKernelGGL(bias_finalize_kernel, dim3((unsigned)((cout + 255) / 256)), dim3(256), 0, st, bias_part, a.ksplit, wrows, cout, gbias,
+  hipLaunchKernelGGL(bias_finalize_kernel, dim3((unsigned)((cout + 255) / 256)), dim3(256), 0, st, bias_part, pl.ksplit, wrows, cout, gbias,
                      accumulate_bias);
   NRPN_LAUNCH_CHECK("bias_finalize");
   return NRPN_OK;
@@ -3079,32 +2814,22 @@ extern "C" int nrpn_conv3d_wgrad_rows(const void *x, const void *dy, float *gw_p
                            workspace, stream, rows, total);
 }
 
-// 1 when a wgrad launch of this shape runs conv_wgrad_big_kernel (256x256 tile), 0 for the 128x128 kernel
-extern "C" int nrpn_conv3d_wgrad_plan(int n, int gx, int gy, int gz, int cin, int cout, int wrows, int ksize, int dtype) {
-  return wgrad_plan((long long)n * gx * gy * gz, wrows, cin, ksize == 3 ? 27 : 1, dtype == NRPN_F32 ? 4 : 2, 0, cout, cin).big ? 1 : 0;
-}
-
-extern "C" int nrpn_conv3d_wgrad_slices(int n, int gx, int gy, int gz, int cin, int cout, int wrows, int ksize, int dtype) {
-  return wgrad_plan((long long)n * gx * gy * gz, wrows, cin, ksize == 3 ? 27 : 1, dtype == NRPN_F32 ? 4 : 2, 0, cout, cin).ksplit;
-}
-
 static long long stem_out_voxels(int n, int gx, int gy, int gz, int stride) {
   return (long long)n * ((gx - 1) / stride + 1) * ((gy - 1) / stride + 1) * ((gz - 1) / stride + 1);
 }
 
-extern "C" int nrpn_stem_wgrad_slices(int n, int gx, int gy, int gz, int cout, int stride, int dtype) {
-  if (stem_zrow_ok(gz, cout, stride)) return stem_zrow_slices(stem_out_voxels(n, gx, gy, gz, stride), dtype == NRPN_F32 ? 4 : 2);
-  return wgrad_plan(stem_out_voxels(n, gx, gy, gz, stride), cout, nrpn_stem_kpad(dtype), 1, dtype == NRPN_F32 ? 4 : 2, 1, cout, 4).ksplit;
+static StemWgPlan stem_wgrad_query(int n, int gx, int gy, int gz, int cout, int stride, int dtype) {
+  return stem_wgrad_plan(stem_out_voxels(n, gx, gy, gz, stride), gz, cout, stride, dtype == NRPN_F32 ? 4 : 2, wg_knobs());
 }
-
+extern "C" int nrpn_stem_wgrad_slices(int n, int gx, int gy, int gz, int cout, int stride, int dtype) {
+  return stem_wgrad_query(n, gx, gy, gz, cout, stride, dtype).slices;
+}
 // floats of ONE slice partial: z-row form [49][cout][32] (stride 2, even Z, Cout 64), otherwise [cout][Kpad]
 extern "C" int64_t nrpn_stem_wgrad_slice_floats(int n, int gx, int gy, int gz, int cout, int stride, int dtype) {
-  (void)n; (void)gx; (void)gy;
-  return stem_zrow_ok(gz, cout, stride) ? (int64_t)49 * cout * 32 : (int64_t)cout * nrpn_stem_kpad(dtype);
+  return stem_wgrad_query(n, gx, gy, gz, cout, stride, dtype).slice_floats;
 }
-
 extern "C" size_t nrpn_stem_wgrad_workspace_bytes(int n, int gx, int gy, int gz, int cout, int stride, int dtype) {
-  return (size_t)nrpn_stem_wgrad_slices(n, gx, gy, gz, cout, stride, dtype) * cout * 4;
+  return stem_wgrad_query(n, gx, gy, gz, cout, stride, dtype).ws_bytes;
 }
 
 extern "C" int nrpn_conv3d_stem_wgrad(const void *x, const void *dy, float *gw_packed, float *gbias, int n, int gx, int gy, int gz,
@@ -3120,8 +2845,7 @@ extern "C" int nrpn_conv3d_stem_wgrad(const void *x, const void *dy, float *gw_p
   a.OX = (gx - 1) / stride + 1; a.OY = (gy - 1) / stride + 1; a.OZ = (gz - 1) / stride + 1;
   a.M = (long long)n * a.OX * a.OY * a.OZ;
   a.Cin = 4; a.Cout = cout; a.wrows = cout; a.taps = 343; a.stride = stride;
-  const int ke = 64 / es;
-  a.kpad = ((343 * 4 + ke - 1) / ke) * ke;
+  a.kpad = stem_kpad(es);
   hipStream_t st = as_stream(stream);
   {
     const long long xb = (long long)n * gx * gy * gz * 4 * es, db = a.M * cout * es;
@@ -3129,11 +2853,12 @@ extern "C" int nrpn_conv3d_stem_wgrad(const void *x, const void *dy, float *gw_p
     a.x_bytes = (unsigned)xb; a.dy_bytes = (unsigned)db; a.vmask = nullptr;
   }
   NRPN_REQUIRE(!gbias || workspace, "stem wgrad: the bias gradient needs the workspace (nrpn_stem_wgrad_workspace_bytes)");
-  if (stem_zrow_ok(gz, cout, stride)) {
+  const StemWgPlan pl = stem_wgrad_plan(a.M, gz, cout, stride, es, wg_knobs());
+  if (pl.zrow) {
     StemZrArgs z{};
     z.x = x; z.dy = dy; z.gw = gw_packed; z.gbias = gbias ? reinterpret_cast<float *>(workspace) : nullptr;
     z.M = a.M; z.X = gx; z.Y = gy; z.Z = gz; z.OX = a.OX; z.OY = a.OY; z.OZ = a.OZ;
-    z.slices = stem_zrow_slices(a.M, es);
+    z.slices = pl.slices;
     z.x_bytes = a.x_bytes; z.dy_bytes = a.dy_bytes;
     const dim3 grid((unsigned)(7 * z.slices));
     if (dtype == NRPN_F32) {
@@ -3152,11 +2877,10 @@ extern "C" int nrpn_conv3d_stem_wgrad(const void *x, const void *dy, float *gw_p
     return NRPN_OK;
   }
   a.gbias = gbias ? reinterpret_cast<float *>(workspace) : nullptr;
-  a.ksplit = wgrad_plan(a.M, cout, a.kpad, 1, es, 1, cout, 4).ksplit;
-  a.slice_stride = (long long)cout * a.kpad;
-  const int rc = (dtype == NRPN_F32) ? launch_wgrad<float, 1>(a, (a.kpad + 127) / 128, st) : launch_wgrad<bf16s, 1>(a, (a.kpad + 127) / 128, st);
+  a.slice_stride = pl.slice_floats;
+  const int rc = (dtype == NRPN_F32) ? launch_wgrad<float, 1>(a, pl.gemm, st) : launch_wgrad<bf16s, 1>(a, pl.gemm, st);
   if (rc || !gbias) return rc;
-  hipLaunchKernelGGL(bias_finalize_kernel, dim3((unsigned)((cout + 255) / 256)), dim3(256), 0, st, a.gbias, a.ksplit, cout, cout, gbias,
+  hipLaunchKernelGGL(bias_finalize_kernel, dim3((unsigned)((cout + 255) / 256)), dim3(256), 0, st, a.gbias, pl.slices, cout, cout, gbias,
                      accumulate_bias);
   NRPN_LAUNCH_CHECK("bias_finalize");
   return NRPN_OK;
@@ -3241,7 +2965,7 @@ __global__ void pack_stem_kernel(const float *__restrict__ w, int cout, int kpad
   elem<T>::st(out + i, tap < 343 ? w[((long long)o * 4 + c) * 343 + tap] : 0.f);
 }
 
-extern "C" int nrpn_stem_kpad(int dtype) { const int ke = dtype == NRPN_F32 ? 16 : 32; return ((343 * 4 + ke - 1) / ke) * ke; }
+extern "C" int nrpn_stem_kpad(int dtype) { return stem_kpad(dtype == NRPN_F32 ? 4 : 2); }
 
 extern "C" int nrpn_pack_stem_weight(const float *w_ref, int cout, int dtype, void *wp, nrpn_stream_t stream) {
   NRPN_REQUIRE(w_ref && wp && cout > 0, "pack_stem_weight: bad args");
