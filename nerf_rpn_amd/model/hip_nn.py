@@ -37,12 +37,12 @@ def conv3d(mod, x, relu=False, out_f32=False, segs=None, chain=0, stats=None, af
         raise NotImplementedError(f"Conv3d k={k} stride={mod.stride} padding={mod.padding} has no HIP kernel yet")
     if segs is not None and (k == 7 or mod.stride[0] != 1):
         raise NotImplementedError("ragged voxel lists are supported by the stride-1 k1 / k3 convolutions only")
-    mode = (relu, chain, stats, affine) if affine is not None else ((relu, chain, stats) if stats is not None else ((relu, chain) if chain else relu))
-    if segs is None:
-        return ops.ConvFn.apply(x, _pack_of(mod), mod.out_channels, mode, out_f32, 1, mod.weight, mod.bias)
-    # whether this ragged launch is differentiated is decided HERE, where grad mode is visible (ops._x3_ok)
-    diff = torch.is_grad_enabled() and (x.requires_grad or mod.weight.requires_grad or (mod.bias is not None and mod.bias.requires_grad))
-    return ops.ConvFn.apply(x, _pack_of(mod), mod.out_channels, mode, out_f32, (1, tuple(segs), diff), mod.weight, mod.bias)
+    mode = ops.ConvMode(relu, chain, stats, affine)
+    if segs is not None:
+        # whether this ragged launch is differentiated is decided HERE, where grad mode is visible (ops._x3_ok)
+        diff = torch.is_grad_enabled() and (x.requires_grad or mod.weight.requires_grad or (mod.bias is not None and mod.bias.requires_grad))
+        mode = mode._replace(segs=tuple(segs), differentiable=diff)
+    return ops.ConvFn.apply(x, _pack_of(mod), mod.out_channels, mode, out_f32, 1, mod.weight, mod.bias)
 
 
 def ragged_cat(feats):

@@ -4,8 +4,10 @@ PyTorch is used only for device memory, streams and autograd graph stitching: ev
 pointers + the current HIP stream to ``libnerfrpn_hip.so``.  Activations are channels-last tensors of shape
 ``[N, X, Y, Z, C]`` (fp32 or bf16).  There is no CPU / eager fallback: non-CUDA tensors raise.
 """
+import ctypes
 import itertools
 import math
+from collections import namedtuple
 from types import SimpleNamespace
 
 import torch
@@ -43,7 +45,6 @@ def _query_opts(name, opts, *args):
 
 
 import os as _os
-_SEPARATE_BIAS = bool(int(_os.environ.get('NRPN_SEPARATE_BIAS', '0')))
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -60,18 +61,10 @@ def _p(t):
     return 0 if t is None else t.data_ptr()
 
 
-# Weight-gradient side stream.  The wgrad of a conv layer (and the reduction of its slice partials into the gradient arena) is not on
-# the backward's critical path -- only the optimiser needs it -- so ConvFn.backward can enqueue it on a second HIP stream: the
-# memory-bound tails (slice reduction, BatchNorm backward of the next layer, split-K epilogues) then overlap with MFMA-bound kernels
-# instead of each draining the chip on its own.  Consumers of the arena (optimiser step, bucket all-reduce) call wgrad_stream_join().
-# On by default for arena training (every gradient of the layer has a GradSink); NRPN_WGRAD_STREAM=0 or set_wgrad_stream(False) keeps
-# everything on the current stream.  Measured on the 160^3 VGG19-FPN step: 12.8 -> 12.0 ms.
+# Weight-gradient side stream (_on_wgrad_stream; DESIGN.md 3.10, "Where a parameter gradient goes").  Consumers of the arena (optimiser
+# step, bucket all-reduce) call wgrad_stream_join(); NRPN_WGRAD_STREAM=0 or set_wgrad_stream(False) keeps everything on the current stream.
+# "keep": the tensors side-stream kernels of this backward pass read, referenced until the main stream has joined the side stream.
 _WGRAD_SIDE = {"enabled": _os.environ.get("NRPN_WGRAD_STREAM", "1") != "0", "streams": {}, "dirty": False, "prefetch": False, "keep": []}
-# "keep": the tensors side-stream kernels of this backward pass read (dY, X), referenced until the main stream has joined the side stream.
-# record_stream only defers the REUSE of their memory; it does not stop autograd from WRITING into them: the engine accumulates gradients
-# in place when it holds the only reference (a residual join hands the same dY to both branches -- ScaleAddFn -- and the copy waiting in the
-# other branch's input buffer is then added into on the main stream while the weight-gradient kernel still reads it: Swin, found in round 4
-# by the graph-capture bit-identity tests).  A second reference makes the engine add out of place.
 
 
 def set_wgrad_stream(enabled):
@@ -276,7 +269,6 @@ def nms3d_sorted(boxes, levels, thr, count=None):
 
 def segmented_topk(scores, offsets, k):
     """Per-segment top-k in (score desc, index asc) order.  offsets: python list of nseg+1 ints."""
-    import ctypes
     scores = scores.contiguous()
     _chk(scores)
     nseg = len(offsets) - 1
@@ -407,7 +399,6 @@ def obb_to_aabb(obb):
 # proposal filter / target assignment / losses
 # ======================================================================================================================
 def filter_candidates(boxes, logits, levels, valid, grid_size, min_size, score_thresh, fix_obb_clip=False):
-    import ctypes
     _chk(boxes, logits, levels, valid)
     n, w = boxes.shape
     dev = boxes.device
@@ -437,7 +428,6 @@ def select_kept(boxes, scores, levels, keep, count, post_top_n):
 
 def match_anchors(table, gt_aabb, fg, bg, ori_size=None):
     """labels f32 [T] in {1,0,-1} and clamped match index int32 [T] (reference assign_targets_to_anchors + Matcher)."""
-    import ctypes
     gt_aabb = _f32(gt_aabb).contiguous()
     _chk(gt_aabb)
     dev = gt_aabb.device
@@ -645,6 +635,21 @@ def _sink(t):
     return getattr(t, "_nrpn_sink", None) if t is not None else None
 
 
+def hand_in(sink, grad, copy=False):
+    """A finished gradient goes into its sink (added to the slot, the sink notified; -> None) or, without one, back to autograd
+    (-> ``grad``; ``copy``: it is a slice of a buffer shared with other gradients)."""
+    if sink is None:
+        return grad.clone() if copy else grad
+    sink.slot.add_(grad)
+    sink.notify()
+    return None
+
+
+def _sinks_cover(params, sinks):
+    """Every parameter of a layer that exists (is not None) has a GradSink: the layer hands nothing back to autograd."""
+    return all(s is not None for p, s in zip(params, sinks) if p is not None)
+
+
 # Parameters can be rewritten behind autograd's back (engine.FlatTrainer updates its flat arena through the raw-pointer AdamW
 # kernel, which never bumps tensor._version), so every GEMM-layout cache is also keyed on this epoch; whoever writes
 # parameter memory outside torch calls ``weights_changed()``.
@@ -701,6 +706,17 @@ class PackedWeight:
         self.key, self.fwd, self.dgrad = key, fwd, dgrad
         return fwd, dgrad
 
+    def fused_bias(self, biases, rows_total):
+        """fp32 bias row of a fused multi-weight GEMM, zero-padded to rows_total: assembled once per parameter update, not once per
+        pyramid level."""
+        bkey = tuple((b.data_ptr(), b._version) for b in biases) + (rows_total, _weight_epoch)
+        if getattr(self, "bias_key", None) != bkey:
+            parts = [b.detach().float().reshape(-1) for b in biases]
+            used = sum(p.numel() for p in parts)
+            if used < rows_total:
+                parts.append(parts[0].new_zeros(rows_total - used))
+            self.bias, self.bias_key = torch.cat(parts), bkey
+        return self.bias
 
 
 # ======================================================================================================================
@@ -849,11 +865,18 @@ def _wgrad_workspace(device, key, nbytes):
     return ent[0], ready
 
 
-# Layer-chain hints for ConvFn (passed as relu=(bool, flags) by modules that own a conv+ReLU -> conv chain, e.g. RPNHead):
+# Layer-chain hints for ConvFn (ConvMode.chain, set by modules that own a conv+ReLU -> conv chain, e.g. RPNHead):
 #   CHAIN_MASK_INPUT_GRAD  this conv is the ONLY consumer of its input, and the input is the output of a fused conv+ReLU
 #   CHAIN_GRAD_PREMASKED   this conv+ReLU's output goes only to a conv with CHAIN_MASK_INPUT_GRAD: the incoming gradient is
 #                          already multiplied by the ReLU mask, so the separate relu_backward pass is skipped
 CHAIN_MASK_INPUT_GRAD, CHAIN_GRAD_PREMASKED = 1, 2
+
+# What a ConvFn launch does besides the GEMM.  chain: CHAIN_* above; stats: holder dict for BatchNorm statistics out of the epilogue and
+# affine: (scale, shift) of a folded eval-mode BatchNorm (both: _conv_fwd); segs: x is a ragged voxel list [1, sum voxels, 1, 1, C] of grids
+# with these (X, Y, Z) dims; differentiable: decided by the caller, where grad mode is visible (None: ctx.needs_input_grad, which mirrors
+# requires_grad even under no_grad).  A plain bool in its place means ConvMode(relu).
+ConvMode = namedtuple("ConvMode", "relu chain stats affine segs differentiable", defaults=(False, 0, None, None, None, None))
+_RELU_ONLY = {False: ConvMode(False), True: ConvMode(True)}
 
 
 IN_BACKWARD = [0]       # > 0 while ConvFn.backward is enqueuing (bench.py tells forward launches from dgrad launches of the same entry point)
@@ -865,20 +888,10 @@ class ConvFn(torch.autograd.Function):
     ``rows_total``); the output has rows_total channels."""
 
     @staticmethod
-    def forward(ctx, x, pack, rows_total, relu, out_f32, nw, *wb):
-        segs = None
-        chain = 0
-        stats = None
-        affine = None
-        if isinstance(relu, tuple):        # (relu, chain[, stats holder[, affine]]): see CHAIN_* below and _conv_fwd
-            relu, chain, *rest = relu
-            stats = rest[0] if rest else None
-            affine = rest[1] if len(rest) > 1 else None
-        differentiable = any(ctx.needs_input_grad)
-        if isinstance(nw, tuple):          # (nw, segs[, differentiable]): ragged voxel list, x = [1, sum voxels, 1, 1, C]
-            nw, segs, *diff = nw
-            if diff:                       # decided by the caller, where grad mode is visible: needs_input_grad mirrors requires_grad even under no_grad
-                differentiable = bool(diff[0])
+    def forward(ctx, x, pack, rows_total, mode, out_f32, nw, *wb):
+        relu, chain, stats, affine, segs, differentiable = mode if isinstance(mode, ConvMode) else _RELU_ONLY[bool(mode)]
+        if differentiable is None:
+            differentiable = any(ctx.needs_input_grad)
         weights, biases = wb[:nw], wb[nw:]
         _chk(x)
         ksize = weights[0].shape[2] if weights[0][0].numel() != x.shape[-1] else 1
@@ -886,17 +899,8 @@ class ConvFn(torch.autograd.Function):
         wp, wpd = pack.get(weights, x.dtype, rows_total, need_dgrad, x.shape[-1])
         bias = None
         if biases[0] is not None:
-            if nw == 1 and biases[0].numel() == rows_total:
-                bias = biases[0].detach().float().contiguous()
-            else:       # rows of a fused multi-weight GEMM, zero-padded: assembled once per parameter update, not once per pyramid level
-                bkey = tuple((b.data_ptr(), b._version) for b in biases) + (rows_total, _weight_epoch)
-                if getattr(pack, "bias_key", None) != bkey:
-                    parts = [b.detach().float().reshape(-1) for b in biases]
-                    used = sum(p.numel() for p in parts)
-                    if used < rows_total:
-                        parts.append(parts[0].new_zeros(rows_total - used))
-                    pack.bias, pack.bias_key = torch.cat(parts), bkey
-                bias = pack.bias
+            single = nw == 1 and biases[0].numel() == rows_total
+            bias = biases[0].detach().float().contiguous() if single else pack.fused_bias(biases, rows_total)
         out_dtype = torch.float32 if out_f32 else x.dtype
         x3 = _x3_ok(x, ksize, segs, rows_total, differentiable)
         xin = x
@@ -915,6 +919,7 @@ class ConvFn(torch.autograd.Function):
         ctx.x3 = x3
         ctx.meta = (rows_total, relu, nw, ksize, biases[0] is not None, segs, chain)
         ctx.sinks = ([_sink(w) for w in weights], [_sink(b) for b in biases])
+        ctx.sinks_complete = _sinks_cover(wb, ctx.sinks[0] + ctx.sinks[1])
         return y
 
     @staticmethod
@@ -939,7 +944,7 @@ class ConvFn(torch.autograd.Function):
             call("relu_backward", _p(yy), _p(dy), _p(dyr), dy.numel(), _dt(dy), _s())
             dy = dyr
         dx = None
-        x3 = getattr(ctx, "x3", False)
+        x3 = ctx.x3
         dyp = None
         if x3 and segs is not None:
             raise lib.NrpnError("bf16x3 backward of a ragged conv: the split dgrad / wgrad launches take no segments")
@@ -959,141 +964,110 @@ class ConvFn(torch.autograd.Function):
                     dx = dxm
             else:
                 dx = _conv_fwd(dy, wpd, None, cin, cin, ksize, 0, x.dtype, segs, mask)
-        taps = ksize ** 3
-        wsinks, bsinks = ctx.sinks
-        side = _wgrad_side_stream(x.device) if all(k is not None for k in wsinks) and (not has_bias or all(k is not None for k in bsinks)) else None
-        wgrad = (lambda: ConvFn._wgrad_x3(ctx, x, dy, dyp, weights)) if x3 else (lambda: ConvFn._wgrad(ctx, x, dy, weights))
-        if side is None:
-            return (dx, None, None, None, None, None, *wgrad())
-        main = torch.cuda.current_stream(x.device)
-        side.wait_stream(main)              # dy (after the ReLU mask) is ready; also orders this wgrad behind the arena's zero fill
-        x.record_stream(side)
-        dy.record_stream(side)
-        if dyp is not None:
-            dyp.record_stream(side)
-        _WGRAD_SIDE["keep"].append((x, dy, dyp))
-        with torch.cuda.stream(side):       # every gradient goes straight into the arena here: nothing is handed back to autograd
-            res = wgrad()
-        if not _WGRAD_SIDE["dirty"]:        # first side-stream wgrad of this backward pass: join when the pass ends
-            _WGRAD_SIDE["dirty"] = True
-            torch.autograd.Variable._execution_engine.queue_callback(wgrad_stream_join)
-        return (dx, None, None, None, None, None, *res)
+        return (dx, None, None, None, None, None,
+                *_on_wgrad_stream(x.device, (x, dy, dyp), ctx.sinks_complete, lambda: ConvFn._wgrad(ctx, x, dy, dyp, weights)))
 
     @staticmethod
-    def _wgrad_x3(ctx, x, dy, dyp, weights):
-        """bf16x3 weight gradient: dW = dy_hi (x) x_hi + dy_hi (x) x_lo + dy_lo (x) x_hi as ONE bf16 wgrad launch over three "scenes"
-        (planes stacked on the batch axis, which the kernel sums over); the bias gradient is the fp32 column sum of dy."""
+    def _wgrad(ctx, x, dy, dyp, weights):
+        """Weight (+ bias) gradient of the layer.  With ``dyp`` (bf16x3): dW = dy_hi (x) x_hi + dy_hi (x) x_lo + dy_lo (x) x_hi as ONE bf16
+        wgrad launch over three "scenes" (planes stacked on the batch axis, which the kernel sums over), and the bias gradient is the fp32
+        column sum of dy."""
         rows_total, relu, nw, ksize, has_bias, segs, chain = ctx.meta
         n, gx, gy, gz, cin = x.shape
-        taps = ksize ** 3
-        wsinks, bsinks = ctx.sinks
-        xp = split3(x, None, 3, _X_P)[1]
-        n3 = 3 * n
-        slices = query("conv3d_wgrad_slices", n3, gx, gy, gz, cin, rows_total, rows_total, ksize, BF16)
-        gwp = torch.empty((slices, taps, rows_total, cin), dtype=torch.float32, device=x.device)
-        ws, mask_ready = _wgrad_workspace(x.device, (n3, gx, gy, gz, ksize, None),
-                                          query("conv3d_wgrad_workspace_bytes", n3, gx, gy, gz, cin, rows_total, rows_total, ksize, BF16))
-        call("conv3d_wgrad", _p(xp), _p(dyp), _p(gwp), 0, n3, gx, gy, gz, cin, rows_total, rows_total, ksize, BF16, 2 if mask_ready else 0, _p(ws), _s())
-        res = _deliver_wgrad(weights, wsinks, bsinks, gwp, None, 0, slices, rows_total, cin, taps, False, False, False)
-        gbs = _deliver_bias_x3(dy.reshape(-1, rows_total), weights, bsinks) if has_bias else tuple([None] * nw)
-        return (*res[:nw], *gbs)
-
-    @staticmethod
-    def _wgrad(ctx, x, dy, weights):
-        rows_total, relu, nw, ksize, has_bias, segs, chain = ctx.meta
-        n, gx, gy, gz, cin = x.shape
-        taps = ksize ** 3
-        wsinks, bsinks = ctx.sinks
-        slices = query("conv3d_wgrad_slices", n, gx, gy, gz, cin, rows_total, rows_total, ksize, _dt(x))
-        gwp = torch.empty((slices, taps, rows_total, cin), dtype=torch.float32, device=x.device)     # per-slice partials, summed by the unpack
-        direct_bias = has_bias and nw == 1 and bsinks[0] is not None
-        gb = bsinks[0].slot if direct_bias else (torch.empty(rows_total, dtype=torch.float32, device=x.device) if has_bias else None)
-        ws, mask_ready = _wgrad_workspace(x.device, (n, gx, gy, gz, ksize, segs),
-                                          query("conv3d_wgrad_workspace_bytes", n, gx, gy, gz, cin, rows_total, rows_total, ksize, _dt(x)))
-        # arena path: weight-slice sum and bias-slice sum of this layer go out as ONE launch (reduce_slices), so the wgrad call leaves
-        # the bias partials in the workspace
-        fused_reduce = nw == 1 and wsinks[0] is not None and wsinks[0].flat is not None and rows_total == weights[0].shape[0]
-        defer_bias = fused_reduce and direct_bias
-        wflags = int(direct_bias) | (2 if mask_ready else 0) | (4 if defer_bias else 0)
+        x3, dt = dyp is not None, _dt(x)
+        if x3:
+            x, dy, dy2d, n, dt = split3(x, None, 3, _X_P)[1], dyp, dy.reshape(-1, rows_total), 3 * n, BF16
+        dest = _WgradDest(weights, *ctx.sinks, has_bias and not x3, rows_total)
+        shape = (n, gx, gy, gz, cin, rows_total, rows_total, ksize, dt)
+        slices = query("conv3d_wgrad_slices", *shape)
+        gwp = torch.empty((slices, ksize ** 3, rows_total, cin), dtype=torch.float32, device=x.device)     # per-slice partials, summed by deliver()
+        ws, mask_ready = _wgrad_workspace(x.device, (n, gx, gy, gz, ksize, segs), query("conv3d_wgrad_workspace_bytes", *shape))
+        wflags = dest.flags | (2 if mask_ready else 0)
         if segs is None or ksize == 1:
-            call("conv3d_wgrad", _p(x), _p(dy), _p(gwp), _p(gb), n, gx, gy, gz, cin, rows_total, rows_total, ksize, _dt(x), wflags, _p(ws), _s())
+            call("conv3d_wgrad", _p(x), _p(dy), _p(gwp), _p(dest.gb), n, gx, gy, gz, cin, rows_total, rows_total, ksize, dt, wflags, _p(ws), _s())
         else:
-            import ctypes
             dims = _seg_dims(segs)
-            call("conv3d_wgrad_ragged", _p(x), _p(dy), _p(gwp), _p(gb), len(segs), ctypes.addressof(dims), cin, rows_total, rows_total, ksize,
-                 _dt(x), wflags, _p(ws), _s())
-        bias_part = ws.data_ptr() + query("conv3d_wgrad_bias_offset", n, gx, gy, gz, ksize) if defer_bias else 0
-        return _deliver_wgrad(weights, wsinks, bsinks, gwp, gb, bias_part, slices, rows_total, cin, taps, has_bias, direct_bias, defer_bias)
+            call("conv3d_wgrad_ragged", _p(x), _p(dy), _p(gwp), _p(dest.gb), len(segs), ctypes.addressof(dims), cin, rows_total, rows_total, ksize,
+                 dt, wflags, _p(ws), _s())
+        bias_part = ws.data_ptr() + query("conv3d_wgrad_bias_offset", n, gx, gy, gz, ksize) if dest.defer_bias else 0
+        res = dest.deliver(gwp, slices, bias_part)
+        return (*res[:nw], *dest.summed_bias(dy2d)) if x3 and has_bias else res
 
 
-def _deliver_wgrad(weights, wsinks, bsinks, gwp, gb, bias_part, slices, rows_total, cin, taps, has_bias, direct_bias, defer_bias):
-    """Sum the per-slice partial gradients ``gwp`` [slices, taps, rows_total, cin] of a (possibly fused multi-weight) GEMM into their
-    destinations: the flat gradient arena (GradSink) or fresh tensors handed back to autograd.  -> (*weight grads, *bias grads), None where
-    a sink took the gradient."""
-    nw = len(weights)
-    gws, gbs, row = [], [], 0
-    for i, w in enumerate(weights):
-        if wsinks[i] is not None and wsinks[i].flat is not None and nw == 1 and rows_total == w.shape[0]:
-            # the arena keeps this gradient in the partials' own layout: ordered sum of the slices, added in place
-            call("reduce_slices", _p(gwp), slices, gwp[0].numel(), _p(wsinks[i].flat), 1, bias_part if defer_bias else 0, rows_total, rows_total,
-                 _p(gb) if defer_bias else 0, 1, _s())
-            wsinks[i].notify()
-            gws.append(None)
-        elif wsinks[i] is not None:
-            if not wsinks[i].slot.is_contiguous():
-                raise lib.NrpnError("a GEMM-layout arena weight reached a fused multi-weight GEMM (mark the module _nrpn_fused_gemm)")
-            call("unpack_conv_wgrad", _p(gwp), w.shape[0], cin, taps, rows_total, row, _p(wsinks[i].slot), 1, slices, _s())
-            wsinks[i].notify()
-            gws.append(None)
-        else:
-            gw = torch.empty_like(w, dtype=torch.float32)
-            call("unpack_conv_wgrad", _p(gwp), w.shape[0], cin, taps, rows_total, row, _p(gw), 0, slices, _s())
-            gws.append(gw)
-        if not has_bias:
-            gbs.append(None)
-        elif direct_bias:
-            bsinks[0].notify()
-            gbs.append(None)
-        elif bsinks[i] is not None:
-            bsinks[i].slot.add_(gb[row:row + w.shape[0]])
-            bsinks[i].notify()
-            gbs.append(None)
-        else:
-            gbs.append(gb[row:row + w.shape[0]].clone())
-        row += w.shape[0]
-    return (*gws, *gbs)
+class _WgradDest:
+    """Where the weight / bias gradients of one conv GEMM go (one weight, or several sharing the GEMM's rows), decided once per wgrad launch:
+    the table in DESIGN.md 3.10, "Where a parameter gradient goes".  ``has_bias``: the launch produces the bias gradient (False for a conv
+    without bias and for the bf16x3 forms, which call ``summed_bias`` instead).  The launch gets ``gb`` as its bias pointer and ``flags``:
+    1 = add the bias gradient into gb, the sink's slot; 4 = leave the per-slice bias partials in the workspace for ``deliver``."""
 
+    def __init__(self, weights, wsinks, bsinks, has_bias, rows_total):
+        self.weights, self.wsinks, self.bsinks, self.has_bias, self.rows_total = weights, wsinks, bsinks, has_bias, rows_total
+        one = len(weights) == 1
+        self.direct_bias = has_bias and one and bsinks[0] is not None
+        # arena layout = the partials' own layout: weight-slice sum and bias-slice sum go out as ONE launch (reduce_slices)
+        self.fused_reduce = one and wsinks[0] is not None and wsinks[0].flat is not None and rows_total == weights[0].shape[0]
+        self.defer_bias = self.fused_reduce and self.direct_bias
+        self.flags = int(self.direct_bias) | (4 if self.defer_bias else 0)
+        self.gb = bsinks[0].slot if self.direct_bias else (torch.empty(rows_total, dtype=torch.float32, device=weights[0].device) if has_bias else None)
 
-def _deliver_bias_x3(dy2d, weights, bsinks):
-    """Bias gradients of a (possibly fused multi-weight) GEMM from the fp32 column sums of dy: into the sinks, or handed back."""
-    gb = column_sum_f32(dy2d)
-    out, row = [], 0
-    for i, w in enumerate(weights):
-        part = gb[row:row + w.shape[0]]
-        if bsinks[i] is not None:
-            bsinks[i].slot.add_(part)
-            bsinks[i].notify()
-            out.append(None)
-        else:
-            out.append(part.clone())
-        row += w.shape[0]
-    return tuple(out)
+    def deliver(self, gwp, slices, bias_part):
+        """Sum the per-slice partials ``gwp`` [slices, taps, rows_total, cin] into their destinations; ``bias_part``: address of the per-slice
+        bias partials (read when defer_bias).  -> (*weight grads, *bias grads), None where a sink took the gradient."""
+        taps, cin = gwp.shape[1], gwp.shape[3]
+        gws, gbs, row = [], [], 0
+        for w, sk, bsk in zip(self.weights, self.wsinks, self.bsinks):
+            rows = w.shape[0]
+            if self.fused_reduce:        # ordered sum of the slices, added in place
+                call("reduce_slices", _p(gwp), slices, gwp[0].numel(), _p(sk.flat), 1, bias_part if self.defer_bias else 0, self.rows_total,
+                     self.rows_total, _p(self.gb) if self.defer_bias else 0, 1, _s())
+            elif sk is not None:
+                if not sk.slot.is_contiguous():
+                    raise lib.NrpnError("a GEMM-layout arena weight reached a fused multi-weight GEMM (mark the module _nrpn_fused_gemm)")
+                call("unpack_conv_wgrad", _p(gwp), rows, cin, taps, self.rows_total, row, _p(sk.slot), 1, slices, _s())
+            else:
+                gw = torch.empty_like(w, dtype=torch.float32)
+                call("unpack_conv_wgrad", _p(gwp), rows, cin, taps, self.rows_total, row, _p(gw), 0, slices, _s())
+            if sk is not None:
+                sk.notify()
+            gws.append(None if sk is not None else gw)
+            if self.direct_bias:
+                bsk.notify()
+            gbs.append(hand_in(bsk, self.gb[row:row + rows], copy=True) if self.has_bias and not self.direct_bias else None)
+            row += rows
+        return (*gws, *gbs)
+
+    def summed_bias(self, dy2d):
+        """Bias gradients from the fp32 column sums of dy [voxels, rows_total]."""
+        gb, out, row = column_sum_f32(dy2d), [], 0
+        for w, bsk in zip(self.weights, self.bsinks):
+            out.append(hand_in(bsk, gb[row:row + w.shape[0]], copy=True))
+            row += w.shape[0]
+        return out
+
+    def nothing(self):
+        """No voxel contributed: zero gradients are handed back; sinks are only told that this use of the parameter is done."""
+        def zero(sk, shape):
+            if sk is None:
+                return torch.zeros(tuple(shape), dtype=torch.float32, device=self.weights[0].device)
+            sk.notify()
+        gws = [zero(sk, w.shape) for w, sk in zip(self.weights, self.wsinks)]
+        return (*gws, *[zero(sk, w.shape[:1]) if self.has_bias else None for w, sk in zip(self.weights, self.bsinks)])
 
 
 def _on_wgrad_stream(device, tensors, sinks_complete, fn):
-    """Run ``fn()`` (a weight-gradient launch sequence whose results all go into GradSinks) on the weight-gradient side stream behind the
-    current stream, or inline when the side stream is off / a gradient has to be handed back to autograd."""
+    """Run ``fn()`` (a weight-gradient launch sequence) on the weight-gradient side stream behind the current stream when all its results
+    go into GradSinks, or inline when one has to be handed back to autograd / the side stream is off.  ``tensors``: what fn's kernels read."""
     side = _wgrad_side_stream(device) if sinks_complete else None
     if side is None:
         return fn()
-    main = torch.cuda.current_stream(device)
-    side.wait_stream(main)
+    side.wait_stream(torch.cuda.current_stream(device))      # the operands are ready; also orders fn behind the arena's zero fill
+    tensors = tuple(t for t in tensors if t is not None)
     for t in tensors:
         t.record_stream(side)
-    _WGRAD_SIDE["keep"].append(tuple(tensors))
+    _WGRAD_SIDE["keep"].append(tensors)
     with torch.cuda.stream(side):
         res = fn()
-    if not _WGRAD_SIDE["dirty"]:
+    if not _WGRAD_SIDE["dirty"]:        # first side-stream work of this backward pass: join when the pass ends
         _WGRAD_SIDE["dirty"] = True
         torch.autograd.Variable._execution_engine.queue_callback(wgrad_stream_join)
     return res
@@ -1110,7 +1084,6 @@ class ConePlan:
     of the pyramid: ``lists`` int32 [depth + 1, total, 2] on the device, ``counts`` on the host once the sampler's read-back has happened."""
 
     def __init__(self, grids, n_scenes, depth, device):
-        import ctypes
         self.grids = [tuple(int(v) for v in g) for g in grids]
         self.n, self.depth = int(n_scenes), int(depth)
         self.segs = [g for g in self.grids for _ in range(self.n)]
@@ -1159,7 +1132,6 @@ def cone_from_indices(plan, pos, neg, table):
 
 def cone_build(plan, out_pos, out_neg, counts, table):
     """Enqueue the list build of ``plan`` on the current stream from the sampler's raw output (see sample_pos_neg); no synchronisation."""
-    import ctypes
     if table.A * sum(plan.cells) != table.total or len(table.counts) != len(plan.grids):
         raise lib.NrpnError("cone_build: the anchor table and the feature grids disagree")
     offs = (ctypes.c_int64 * (len(table.offsets)))(*[int(v) for v in table.offsets])
@@ -1190,32 +1162,16 @@ def conv_rows_wgrad(x, dy, weights, biases, rows_total, ksize, plan, k, sinks=No
     ``sinks``: (weight sinks, bias sinks) looked up by the caller on the original Parameter objects; default: on ``weights`` / ``biases``."""
     rows, nrows = plan.rows(k)
     cin = x.shape[-1]
-    taps = ksize ** 3
-    nw = len(weights)
     wsinks, bsinks = sinks if sinks is not None else ([_sink(w) for w in weights], [_sink(b) for b in biases])
-    has_bias = biases[0] is not None
-    if nrows == 0:      # nothing sampled: zero gradients (sinks are only told that this use of the parameter is done)
-        out = []
-        for t, sk in list(zip(weights, wsinks)) + list(zip(biases, bsinks)):
-            if t is None:
-                out.append(None)
-            elif sk is not None:
-                sk.notify()
-                out.append(None)
-            else:
-                out.append(torch.zeros_like(t, dtype=torch.float32))
-        return tuple(out)
+    dest = _WgradDest(weights, wsinks, bsinks, biases[0] is not None, rows_total)
+    if nrows == 0:      # nothing sampled
+        return dest.nothing()
     slices = lib.query("conv3d_wgrad_slices", 1, nrows, 1, 1, cin, rows_total, rows_total, ksize, _dt(x))      # (not memoised: nrows changes every step)
-    gwp = torch.empty((slices, taps, rows_total, cin), dtype=torch.float32, device=x.device)
-    direct_bias = has_bias and nw == 1 and bsinks[0] is not None
-    gb = bsinks[0].slot if direct_bias else (torch.empty(rows_total, dtype=torch.float32, device=x.device) if has_bias else None)
+    gwp = torch.empty((slices, ksize ** 3, rows_total, cin), dtype=torch.float32, device=x.device)
     ws = torch.empty(max(256, slices * rows_total * 4), dtype=torch.uint8, device=x.device)
-    fused_reduce = nw == 1 and wsinks[0] is not None and wsinks[0].flat is not None and rows_total == weights[0].shape[0]
-    defer_bias = fused_reduce and direct_bias
-    wflags = int(direct_bias) | (4 if defer_bias else 0)
-    call("conv3d_wgrad_rows", _p(x), _p(dy), _p(gwp), _p(gb), rows, nrows, plan.nseg, plan.dims_ptr, cin, rows_total, rows_total, ksize, _dt(x),
-         wflags, _p(ws), _s())
-    return _deliver_wgrad(weights, wsinks, bsinks, gwp, gb, ws.data_ptr(), slices, rows_total, cin, taps, has_bias, direct_bias, defer_bias)
+    call("conv3d_wgrad_rows", _p(x), _p(dy), _p(gwp), _p(dest.gb), rows, nrows, plan.nseg, plan.dims_ptr, cin, rows_total, rows_total, ksize, _dt(x),
+         dest.flags, _p(ws), _s())
+    return dest.deliver(gwp, slices, ws.data_ptr())
 
 
 def conv_rows_wgrad_x3(x, dy, weights, biases, rows_total, ksize, plan, k, sinks=None):
@@ -1226,20 +1182,18 @@ def conv_rows_wgrad_x3(x, dy, weights, biases, rows_total, ksize, plan, k, sinks
     if nrows == 0 or len(weights) != 1:
         return conv_rows_wgrad(x, dy, weights, biases, rows_total, ksize, plan, k, sinks)
     cin = x.shape[-1]
-    taps = ksize ** 3
     wsinks, bsinks = sinks if sinks is not None else ([_sink(w) for w in weights], [_sink(b) for b in biases])
-    has_bias = biases[0] is not None
+    dest = _WgradDest(weights, wsinks, bsinks, False, rows_total)
     xpl = split3(x, None, 2, 0b10)[1]          # [hi ; lo]
     dpl = split3(dy, None, 2, 0b10)[1]
     slices = lib.query("conv3d_wgrad_slices", 1, nrows, 1, 1, cin, rows_total, rows_total, ksize, BF16)
-    gwp = torch.empty((3 * slices, taps, rows_total, cin), dtype=torch.float32, device=x.device)
+    gwp = torch.empty((3 * slices, ksize ** 3, rows_total, cin), dtype=torch.float32, device=x.device)
     ws = torch.empty(max(256, slices * rows_total * 4), dtype=torch.uint8, device=x.device)
     for j, (di, xi) in enumerate(((0, 0), (0, 1), (1, 0))):
         call("conv3d_wgrad_rows", _p(xpl[xi]), _p(dpl[di]), gwp[j * slices].data_ptr(), 0, rows, nrows, plan.nseg, plan.dims_ptr, cin, rows_total,
              rows_total, ksize, BF16, 0, _p(ws), _s())
-    res = _deliver_wgrad(weights, wsinks, bsinks, gwp, None, 0, 3 * slices, rows_total, cin, taps, False, False, False)
-    gbs = _deliver_bias_x3(dy.reshape(-1, rows_total), weights, bsinks) if has_bias else (None,)
-    return (res[0], *gbs)
+    gw = dest.deliver(gwp, 3 * slices, 0)[0]
+    return (gw, *(dest.summed_bias(dy.reshape(-1, rows_total)) if biases[0] is not None else (None,)))
 
 
 class ConeHeadFn(torch.autograd.Function):
@@ -1287,17 +1241,7 @@ class ConeHeadFn(torch.autograd.Function):
             ops_w.append(wpd)
         rows_total = head.head_rows
         wpo, wpdo = head._pack.get(list(ow), dt, rows_total, True, C)
-        bias_o = None
-        if ob[0] is not None:
-            pack = head._pack
-            bkey = tuple((b.data_ptr(), b._version) for b in ob) + (rows_total, _weight_epoch)
-            if getattr(pack, "bias_key", None) != bkey:
-                parts = [b.detach().float().reshape(-1) for b in ob]
-                used = sum(p.numel() for p in parts)
-                if used < rows_total:
-                    parts.append(parts[0].new_zeros(rows_total - used))
-                pack.bias, pack.bias_key = torch.cat(parts), bkey
-            bias_o = pack.bias
+        bias_o = head._pack.fused_bias(ob, rows_total) if ob[0] is not None else None
         out = torch.zeros((V, rows_total), dtype=torch.float32, device=dev)
         conv_rows_fwd(hs[-1], wpo, bias_o, out, plan, 0, C, rows_total, rows_total, 1, 0)
         T = sum(plan.cells) * A
@@ -1350,12 +1294,8 @@ class ConeHeadFn(torch.autograd.Function):
         _wait_dgrad_operands()
 
         cws, cbs, ows, obs = ctx.sinks
-
-        def sinks_ok(ws_, bs_, bt_):
-            return all(k_ is not None for k_ in ws_) and all(k_ is not None for k_, b in zip(bs_, bt_) if b is not None)
-
         # output GEMM: weight / bias gradients from the rows of S_0; input gradient on S_0 with the last layer's ReLU mask
-        g_ow = _on_wgrad_stream(dev, [hs[D], dout, plan.lists], sinks_ok(ows, obs, ob),
+        g_ow = _on_wgrad_stream(dev, [hs[D], dout, plan.lists], _sinks_cover((*ow, *ob), (*ows, *obs)),
                                 lambda: conv_rows_wgrad(hs[D], dout, list(ow), list(ob), rows_total, 1, plan, 0, (ows, obs)))
         dh = torch.zeros((V, C), dtype=dt, device=dev)
         conv_rows_fwd(dout, wpdo, None, dh, plan, 0, rows_total, C, C, 1, 0, mask=hs[D] if D > 0 else None)
@@ -1365,12 +1305,12 @@ class ConeHeadFn(torch.autograd.Function):
             for l in range(L):
                 g = plan.grids[l]
                 g_feats[l] = dh[plan.level_start[l]:plan.level_start[l + 1]].view(n, g[0], g[1], g[2], C)
-        x3 = getattr(ctx, "x3", False)
+        x3 = ctx.x3
         rows_wgrad = conv_rows_wgrad_x3 if x3 else conv_rows_wgrad
         for i in range(D - 1, -1, -1):
             k = D - 1 - i
             x_i, dy_i = hs[i], dh
-            res = _on_wgrad_stream(dev, [x_i, dy_i, plan.lists], sinks_ok([cws[i]], [cbs[i]], [cb[i]]),
+            res = _on_wgrad_stream(dev, [x_i, dy_i, plan.lists], _sinks_cover((cw[i], cb[i]), (cws[i], cbs[i])),
                                    lambda x_i=x_i, dy_i=dy_i, i=i, k=k: rows_wgrad(x_i, dy_i, [cw[i]], [cb[i]], C, 3, plan, k, ([cws[i]], [cbs[i]])))
             g_cw[i] = res[0]
             g_cb[i] = res[1] if len(res) > 1 else None
@@ -1685,15 +1625,7 @@ class LayerNormFn(torch.autograd.Function):
         dg = torch.empty(c, dtype=torch.float32, device=x.device)
         db = torch.empty(c, dtype=torch.float32, device=x.device)
         call("layernorm_bwd", _p(x), _p(dy), _p(dx), _p(g32), _p(mean), _p(rstd), _p(dg), _p(db), x.numel() // c, c, _dt(x), 0, _p(ws), _s())
-        if gs is not None:
-            gs.slot.add_(dg)
-            gs.notify()
-            dg = None
-        if bs is not None:
-            bs.slot.add_(db)
-            bs.notify()
-            db = None
-        return dx, dg, db, None
+        return dx, hand_in(gs, dg), hand_in(bs, db), None
 
 
 class GeluFn(torch.autograd.Function):
@@ -1801,17 +1733,15 @@ class WindowAttnFn(torch.autograd.Function):
         dtable = torch.empty_like(t32)
         call("window_attn_bwd", _p(qkv), _p(qb), _p(t32), _p(rel_index), _p(dout), _p(dqkv), _p(dtable), _p(dpad), n, gx, gy, gz, c, heads,
              shift, _dt(qkv), 0, _p(ws), _s())
-        if tsink is not None and (dpad is None or bsink is not None):
+        if _sinks_cover((dtable, dpad), (tsink, bsink)):
             # arena training: both parameter gradients are added to their slots here instead of travelling through autograd's AccumulateGrad
             # (which runs on the stream it was created on and would fall out of a captured backward, graphs.py).  The qkv bias also receives
             # the bias gradient of the qkv Linear on the weight-gradient stream: same stream, enqueue order = a fixed summation order.
             def deliver():
-                tsink.slot.add_(dtable.view_as(tsink.slot))
-                tsink.notify()
+                hand_in(tsink, dtable.view_as(tsink.slot))
                 if dpad is not None:
-                    bsink.slot.add_(dpad.view_as(bsink.slot))
-                    bsink.notify()
-            _on_wgrad_stream(qkv.device, [dtable] + ([dpad] if dpad is not None else []), True, deliver)
+                    hand_in(bsink, dpad.view_as(bsink.slot))
+            _on_wgrad_stream(qkv.device, (dtable, dpad), True, deliver)
             return dqkv, None, None, None, None, None
         return dqkv, dpad, dtable, None, None, None
 
@@ -1858,15 +1788,7 @@ class GroupNormFn(torch.autograd.Function):
         db = torch.empty(c, dtype=torch.float32, device=x.device)
         call("groupnorm_bwd", _p(x), _p(y), _p(dy), _p(dx), _p(g32), _p(mean), _p(rstd), _p(dg), _p(db), n, x[0].numel() // c, c, groups,
              int(relu), _dt(x), 0, _p(ws), _s())
-        if gs is not None:
-            gs.slot.add_(dg)
-            gs.notify()
-            dg = None
-        if bs is not None:
-            bs.slot.add_(db)
-            bs.notify()
-            db = None
-        return dx, dg, db, None, None, None
+        return dx, hand_in(gs, dg), hand_in(bs, db), None, None, None
 
 
 class FcosHeadOutFn(torch.autograd.Function):
@@ -1913,7 +1835,6 @@ class FcosGeometry:
     """Host description of the flattened FCOS location list (level-major, then scene, then voxel)."""
 
     def __init__(self, n, dims, strides):
-        import ctypes
         self.n, self.levels = int(n), len(dims)
         self.dims = [tuple(int(v) for v in d) for d in dims]
         self.strides = [int(s) for s in strides]
@@ -1927,12 +1848,10 @@ class FcosGeometry:
                 self.segment_offsets.append(self.segment_offsets[-1] + c)
 
     def args(self):
-        import ctypes
         return self.n, self.levels, ctypes.addressof(self._dims), ctypes.addressof(self._strides)
 
     @staticmethod
     def sizes(ori_sizes):
-        import ctypes
         if ori_sizes is None:
             return None, 0
         buf = (ctypes.c_float * (3 * len(ori_sizes)))(*[float(v) for s in ori_sizes for v in s])
@@ -1950,7 +1869,6 @@ def fcos_gt_summary(gt):
 
 def fcos_targets(geom, targets, ori_sizes, radius, norm_reg, reg_dim, device):
     """labels int8 [total] in {1,0,-1}, reg_targets f32 [total, reg_dim], num_pos int32 [1] (reference loss.py:270-437)."""
-    import ctypes
     summ = [fcos_gt_summary(t) for t in targets]
     offs = [0]
     for t in targets:
@@ -2086,7 +2004,6 @@ def roi_align_rotated_3d_bwd(grad_cl, rois, feat_shape, spatial_scale, output_si
 def ingest_augment(raw, alpha_mode, dtype, plan):
     """``ingest_rgbsigma`` + the training augmentation of ``plan`` (datasets.AugPlan) in one pass on the device: 90-degree rotation and
     flips as index remaps, rotate_and_scale_scene as a trilinear resample (reference datasets.py:109-163, 291-329)."""
-    import ctypes
     raw = raw.contiguous()
     _chk(raw)
     if raw.dim() != 4 or raw.shape[-1] != 4 or raw.dtype not in (torch.float32, torch.uint8):

@@ -817,3 +817,40 @@ def test_wgrad_two_taps_per_workgroup(n, grid, cin, cout, dtype, dev):
     for on in (1, 0):
         assert relerr(got[on][0], conv.weight.grad) < tol and relerr(got[on][1], conv.bias.grad) < tol, (on, relerr(got[on][0], conv.weight.grad))
     assert relerr(got[1][0], got[0][0]) < 2e-5 and relerr(got[1][1], got[0][1]) < 2e-5
+
+
+@pytest.mark.parametrize("sunk", ["weight", "bias"])
+def test_conv_with_an_incomplete_set_of_sinks(sunk, dev):
+    """ConvFn k3 fp32 on a (1, 6, 5, 4) grid, Cin = Cout = 32, with a GradSink (zero-filled slot) on ONE of its two parameters: that
+    gradient lands in the slot and its position in the returned tuple is None, the other one is handed back, both bit-equal to the
+    gradients of the same call without sinks -- and no launch leaves the main stream (the side stream is for layers whose gradients ALL
+    have sinks)."""
+    from nerf_rpn_amd import ops
+    from nerf_rpn_amd.model import hip_nn
+    from step_trace import Recorder
+    torch.manual_seed(5)
+    conv = nn.Conv3d(32, 32, 3, padding=1).to(dev)
+    x = torch.randn(1, 6, 5, 4, 32, device=dev, requires_grad=True)
+    dy = torch.randn(1, 6, 5, 4, 32, device=dev)
+    assert ops._WGRAD_SIDE["enabled"]
+
+    def grads():
+        y = ops.ConvFn.apply(x, hip_nn._pack_of(conv), 32, False, False, 1, conv.weight, conv.bias)
+        return torch.autograd.grad(y, [x, conv.weight, conv.bias], dy, allow_unused=True)
+    _, gw, gb = grads()
+    param = conv.weight if sunk == "weight" else conv.bias
+    slot = torch.zeros_like(param, dtype=torch.float32)
+    param._nrpn_sink = ops.GradSink(slot, lambda: None)
+    try:
+        with Recorder(ops) as rec:
+            rec.on = True
+            _, sw, sb = grads()
+        torch.cuda.synchronize()
+    finally:
+        del param._nrpn_sink
+    launches = [e for e in rec.trace if not e[0].startswith("py:")]
+    assert any(e[0] == "conv3d_wgrad" for e in launches) and all(e[1][-1] == 0 for e in launches), launches
+    if sunk == "weight":
+        assert sw is None and torch.equal(slot, gw) and torch.equal(sb, gb)
+    else:
+        assert sb is None and torch.equal(slot, gb) and torch.equal(sw, gw)
