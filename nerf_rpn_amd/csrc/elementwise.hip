@@ -1,62 +1,13 @@
 // HBM-bound companions of the conv kernels (gfx950): BatchNorm3d statistics / apply / backward, ReLU backward,
 // MaxPool3d, nearest-upsample-add (FPN top-down), layout + dtype conversion, and the flat-arena AdamW step.
-// All tensors channels-last [rows = N*X*Y*Z][C]; each lane handles 4 consecutive channels (16-byte fp32 / 8-byte bf16
-// accesses, fully coalesced along C); per-channel reductions are block partials in fp32 finished in fp64.
+// All tensors channels-last [rows = N*X*Y*Z][C]; each lane handles 4 consecutive channels (16-byte fp32 / 8-byte bf16 accesses,
+// fully coalesced along C), or 8 for bf16 with C % 8 == 0; loads, stores, the width rule and the voxel index come from chanlast.cuh.
+// Per-channel reductions are block partials in fp32 finished in fp64.
 //
 // Replaces BatchNorm3d / ReLU / MaxPool3d / F.interpolate+add in reference feature_extractor.py:337-358, fpn.py:150-155
 // and clip_grad_norm_ + AdamW of run_rpn.py:345-349,390-395.
-#include "common.h"
+#include "chanlast.cuh"
 #include <atomic>
-
-typedef unsigned short bf16s;
-typedef __attribute__((ext_vector_type(4))) float f4;
-typedef __attribute__((ext_vector_type(4))) unsigned short us4;
-
-// bf16 stores of this file round on the conversion unit (fptrunc -> v_cvt_pk_bf16_f32, two values per instruction) instead of common.h's
-// integer routine (~7 VALU instructions per value): the same round-to-nearest-even result for every non-NaN input (these kernels keep
-// fp32 denormals), and the companions are VALU-, not bandwidth-limited when they share the chip with the weight-gradient stream.
-template <typename T> struct vec4;
-template <> struct vec4<float> {
-  static __device__ __forceinline__ f4 ld(const float *p) { return *reinterpret_cast<const f4 *>(p); }
-  static __device__ __forceinline__ void st(float *p, f4 v) { *reinterpret_cast<f4 *>(p) = v; }
-};
-template <> struct vec4<bf16s> {
-  static __device__ __forceinline__ f4 ld(const bf16s *p) {
-    const us4 u = *reinterpret_cast<const us4 *>(p);
-    f4 v = {bf16_bits_to_f32(u[0]), bf16_bits_to_f32(u[1]), bf16_bits_to_f32(u[2]), bf16_bits_to_f32(u[3])};
-    return v;
-  }
-  static __device__ __forceinline__ void st(bf16s *p, f4 v) {
-    typedef __attribute__((ext_vector_type(4))) __bf16 b4;
-    *reinterpret_cast<us4 *>(p) = __builtin_bit_cast(us4, __builtin_convertvector(v, b4));      // v_cvt_pk_bf16_f32, see below
-  }
-};
-
-// V consecutive channels per thread: 4 (8 / 16-byte accesses) or, for bf16 with C % 8 == 0, 8 (16-byte accesses): half the
-// instructions per byte on kernels that are issue-bound (27 window positions per output of the 3/2/1 pool)
-template <typename T, int V> struct vecv;
-template <typename T> struct vecv<T, 4> {
-  static __device__ __forceinline__ void ld(const T *p, float *o) { const f4 v = vec4<T>::ld(p); o[0] = v[0]; o[1] = v[1]; o[2] = v[2]; o[3] = v[3]; }
-  static __device__ __forceinline__ void st(T *p, const float *o) { vec4<T>::st(p, f4{o[0], o[1], o[2], o[3]}); }
-};
-template <> struct vecv<bf16s, 8> {
-  typedef __attribute__((ext_vector_type(8))) unsigned short us8;
-  static __device__ __forceinline__ void ld(const bf16s *p, float *o) {
-    const us8 u = *reinterpret_cast<const us8 *>(p);
-#pragma unroll
-    for (int q = 0; q < 8; ++q) o[q] = bf16_bits_to_f32(u[q]);
-  }
-  static __device__ __forceinline__ void st(bf16s *p, const float *o) {
-    typedef __attribute__((ext_vector_type(8))) float f8;
-    typedef __attribute__((ext_vector_type(8))) __bf16 b8;
-    const f8 v = {o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7]};
-    *reinterpret_cast<us8 *>(p) = __builtin_bit_cast(us8, __builtin_convertvector(v, b8));
-  }
-};
-
-#define DISPATCH_T(dtype, ...)                       \
-  if ((dtype) == NRPN_F32) { typedef float T; __VA_ARGS__; } \
-  else { typedef bf16s T; __VA_ARGS__; }
 
 // =====================================================================================================================
 // per-channel reductions: slabs of 256 rows per block; thread = (4-channel group, row lane)
@@ -66,6 +17,16 @@ template <> struct vecv<bf16s, 8> {
 // MI355X (bn_stats / bn_backward on 256 ch x 64000 rows, us incl. the finish): 512 blocks 11.6 / 41.2, 1024 12.7 / 38.4, 2048 17.6 / 47.8,
 // 4096 25.7 / 60.2 -- more partial rows cost the latency-bound finish more than the reduction gains
 static inline int slab_rows(long long rows) { const long long s = (rows + 1023) / 1024; return (int)(s < 64 ? 64 : s); }
+
+// The BatchNorm expressions, each stated once: forward, the ReLU mask both backward kernels and the MODE 1 reduction recompute from x
+// (bn_affine(..) > 0 has to agree with the sign of what the forward wrote, and this unit contracts to FMA: one text, one contraction),
+// and dx = gamma * invstd * (dy' - dbeta / R - xhat * dgamma / R).
+__device__ __forceinline__ float bn_xhat(float x, float mu, float is) { return (x - mu) * is; }
+__device__ __forceinline__ float bn_affine(float x, float mu, float is, float ga, float be) { return (x - mu) * is * ga + be; }
+__device__ __forceinline__ float bn_dx(float x, float g, float mu, float is, float ga, float dg, float db, float invr) {
+  const float xh = bn_xhat(x, mu, is);
+  return ga * is * (g - db * invr - xh * dg * invr);
+}
 
 // MODE 0: (sum x, sum x^2)           MODE 1: (sum dy', sum dy' * xhat) with dy' = dy * (y > 0 if relu)
 // V channels per lane: 4, or 8 for bf16 with C % 8 == 0 (16-byte loads: half the load instructions and address arithmetic per byte; round 5 --
@@ -116,7 +77,7 @@ chan_partial_kernel(const T *__restrict__ x, const T *__restrict__ y, const T *_
         vecv<T, V>::ld(dy + r * c + tx * V, g);
         if (relu && beta) {   // ReLU mask recomputed from x (the bn_apply expression) instead of reading y: one tensor less
 #pragma unroll
-          for (int k = 0; k < V; ++k) g[k] = ((xv[k] - mu[k]) * is[k] * ga[k] + be[k]) > 0.f ? g[k] : 0.f;
+          for (int k = 0; k < V; ++k) g[k] = bn_affine(xv[k], mu[k], is[k], ga[k], be[k]) > 0.f ? g[k] : 0.f;
         } else if (relu) {
           float yv[V];
           vecv<T, V>::ld(y + r * c + tx * V, yv);
@@ -124,7 +85,7 @@ chan_partial_kernel(const T *__restrict__ x, const T *__restrict__ y, const T *_
           for (int k = 0; k < V; ++k) g[k] = yv[k] > 0.f ? g[k] : 0.f;
         }
 #pragma unroll
-        for (int k = 0; k < V; ++k) { s0[k] += g[k]; s1[k] += g[k] * ((xv[k] - mu[k]) * is[k]); }
+        for (int k = 0; k < V; ++k) { s0[k] += g[k]; s1[k] += g[k] * bn_xhat(xv[k], mu[k], is[k]); }
       }
     }
   }
@@ -154,8 +115,7 @@ static std::atomic<int> g_chan_v8{0};
 extern "C" int nrpn_set_bn_reduce_v8(int on) { g_chan_v8 = on ? 1 : 0; return NRPN_OK; }
 static inline bool chan_v8(int dtype, int c, const void *a, const void *b, const void *d) {
   const int tile = c > 1024 ? 1024 : c;
-  return dtype == NRPN_BF16 && c % 8 == 0 && tile % 8 == 0 && 256 % (tile / 8) == 0 &&
-         ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(d)) & 15) == 0;
+  return g_chan_v8.load(std::memory_order_relaxed) && cl_width(dtype, c, a, b, d) == 8 && tile % 8 == 0 && 256 % (tile / 8) == 0;
 }
 
 // finalize: block = (16 channels, 64 partial-lanes); fp64 accumulation of the fp32 block partials in a fixed order (lane l takes rows l, l + 64,
@@ -246,14 +206,11 @@ extern "C" int nrpn_bn_stats(const void *x, int64_t rows, int c, int dtype, floa
   const int kSlab = slab_rows(rows);
   const int nb = (int)cdiv64(rows, kSlab);
   hipStream_t st = as_stream(stream);
-  if (g_chan_v8.load(std::memory_order_relaxed) && chan_v8(dtype, c, x, nullptr, nullptr)) {
-    hipLaunchKernelGGL((chan_partial_kernel<bf16s, 0, 8>), dim3(nb, (c + 1023) / 1024), dim3(256), 0, st, (const bf16s *)x, (const bf16s *)nullptr,
-                       (const bf16s *)nullptr, (long long)rows, c, (const float *)nullptr, (const float *)nullptr, 0.f, 0, (float *)workspace, kSlab);
-  } else {
-    DISPATCH_T(dtype, hipLaunchKernelGGL((chan_partial_kernel<T, 0, 4>), dim3(nb, (c + 1023) / 1024), dim3(256), 0, st, (const T *)x, (const T *)nullptr,
-                                         (const T *)nullptr, (long long)rows, c, (const float *)nullptr, (const float *)nullptr, 0.f, 0,
-                                         (float *)workspace, kSlab));
-  }
+  cl_dispatch(dtype, chan_v8(dtype, c, x, nullptr, nullptr) ? 8 : 4, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    hipLaunchKernelGGL((chan_partial_kernel<T, 0, decltype(tag)::V>), dim3(nb, (c + 1023) / 1024), dim3(256), 0, st, (const T *)x, (const T *)nullptr,
+                       (const T *)nullptr, (long long)rows, c, (const float *)nullptr, (const float *)nullptr, 0.f, 0, (float *)workspace, kSlab);
+  });
   hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3((c + kFinCh - 1) / kFinCh), dim3(kFinCh, kFinLanes), 0, st, (const float *)workspace, nb, (long long)rows, c, mean,
                      var, running_mean, running_var, momentum);
   NRPN_LAUNCH_CHECK("bn_stats");
@@ -279,45 +236,34 @@ __global__ void bn_apply_kernel(const T *__restrict__ x, T *__restrict__ y, long
   const int ct = c / 4;
   for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += (long long)gridDim.x * blockDim.x) {
     const int cg = (int)(g % ct) * 4;
-    const f4 xv = vec4<T>::ld(x + g * 4);
-    const f4 mu = *reinterpret_cast<const f4 *>(mean + cg), vv = *reinterpret_cast<const f4 *>(var + cg);
-    const f4 ga = *reinterpret_cast<const f4 *>(gamma + cg), be = *reinterpret_cast<const f4 *>(beta + cg);
-    f4 o;
+    float xv[4], mu[4], vv[4], ga[4], be[4], o[4];
+    vecv<T, 4>::ld(x + g * 4, xv);
+    ld_params<4>(mean + cg, mu); ld_params<4>(var + cg, vv); ld_params<4>(gamma + cg, ga); ld_params<4>(beta + cg, be);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const float is = 1.0f / sqrtf(vv[k] + eps);
-      o[k] = (xv[k] - mu[k]) * is * ga[k] + be[k];
+      o[k] = bn_affine(xv[k], mu[k], is, ga[k], be[k]);
       if (relu) o[k] = fmaxf(o[k], 0.f);
     }
-    vec4<T>::st(y + g * 4, o);
+    vecv<T, 4>::st(y + g * 4, o);
   }
 }
-
-static inline int ew_blocks(long long work) { long long b = (work + 255) / 256; return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b)); }
 
 // Fast forms of bn_apply / bn_bwd_apply.  V channels per lane in 16-byte accesses (8 bf16 / 4 fp32) and a grid stride that is a multiple
 // of C / V: a lane then meets the SAME channels in every iteration, so the per-channel parameters, the rsqrt and the 64-bit "g % (C / V)"
 // leave the loop, whose body is the loads plus a handful of VALU operations per element.  These kernels run next to the weight-gradient
 // stream's MFMA kernels (3x their stand-alone time there): every VALU slot they take is one the MFMA waves wait for.  The arithmetic is
-// the expression of the general kernels, term for term (the ReLU mask recomputed in backward has to agree with what forward wrote).
-// Launch condition (bn_fast_v): 256 % (C / V) == 0, i.e. C / V a power of two <= 256 -- every BatchNorm of the three backbones.
+// that of the general kernels: both call bn_affine / bn_dx.
+// Launch condition (bn_fast_v): 256 % (C / V) == 0, i.e. C / V a power of two <= 256 -- every BatchNorm of the three backbones -- and, for
+// V = 8, tensors that allow 16-byte accesses; 0 = the general kernels.
 static std::atomic<int> g_bn_fast{1};      // tools-only A/B switch (nerfrpn_tools.h)
 extern "C" int nrpn_set_bn_fast(int on) { g_bn_fast = on ? 1 : 0; return NRPN_OK; }
-static inline int bn_fast_v(int c, int dtype) {
+template <typename... P>
+static inline int bn_fast_v(int c, int dtype, const P *...tensors) {
   if (!g_bn_fast) return 0;
-  const int v = (dtype != NRPN_F32 && c % 8 == 0) ? 8 : 4;
-  const int ctv = c / v;
-  return (c % v == 0 && ctv > 0 && ctv <= 256 && 256 % ctv == 0) ? v : 0;
-}
-
-// V per-channel fp32 parameters as 16-byte loads (cg is a multiple of V >= 4 floats)
-template <int V>
-__device__ __forceinline__ void ld_params(const float *__restrict__ p, float *o) {
-#pragma unroll
-  for (int q = 0; q < V; q += 4) {
-    const f4 v = *reinterpret_cast<const f4 *>(p + q);
-    o[q] = v[0]; o[q + 1] = v[1]; o[q + 2] = v[2]; o[q + 3] = v[3];
-  }
+  const int v = cl_width(dtype, c), ctv = c / v;
+  if (!(ctv > 0 && ctv <= 256 && 256 % ctv == 0)) return 0;
+  return cl_width(dtype, c, tensors...) == v ? v : 0;
 }
 
 // grid of the fast apply kernels: one group per lane up to one resident round of the chip (256 CUs x `per_cu` blocks at the kernel's register
@@ -345,7 +291,7 @@ __global__ void __launch_bounds__(256) bn_apply_fast_kernel(const T *__restrict_
     vecv<T, V>::ld(x + g * V, xv);
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-      o[k] = (xv[k] - mu[k]) * is[k] * ga[k] + be[k];
+      o[k] = bn_affine(xv[k], mu[k], is[k], ga[k], be[k]);
       if (relu) o[k] = fmaxf(o[k], 0.f);
     }
     vecv<T, V>::st(y + g * V, o);
@@ -381,9 +327,8 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_fast_kernel(const T *__restr
     }
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-      if (relu && beta && !(((xv[k] - mu[k]) * is[k] * ga[k] + be[k]) > 0.f)) gv[k] = 0.f;    // mask recomputed from x, y is not read
-      const float xh = (xv[k] - mu[k]) * is[k];
-      o[k] = ga[k] * is[k] * (gv[k] - db[k] * invr - xh * dg[k] * invr);
+      if (relu && beta && !(bn_affine(xv[k], mu[k], is[k], ga[k], be[k]) > 0.f)) gv[k] = 0.f;    // mask recomputed from x, y is not read
+      o[k] = bn_dx(xv[k], gv[k], mu[k], is[k], ga[k], dg[k], db[k], invr);
     }
     vecv<T, V>::st(dx + g * V, o);
   }
@@ -393,19 +338,18 @@ extern "C" int nrpn_bn_apply(const void *x, void *y, int64_t rows, int c, int dt
                              const float *gamma, const float *beta, float eps, int relu, nrpn_stream_t stream) {
   NRPN_REQUIRE(rows > 0 && c > 0 && c % 4 == 0, "bn_apply: C=%d must be a multiple of 4", c);
   NRPN_REQUIRE(x && y && mean && var && gamma && beta, "bn_apply: null pointer");
-  int fv = bn_fast_v(c, dtype);
-  if (fv == 8 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15)) fv = 0;      // 16-byte accesses
+  const int fv = bn_fast_v(c, dtype, x, y);
   const long long groups = rows * (c / (fv ? fv : 4));
-  if (fv == 8)
-    hipLaunchKernelGGL((bn_apply_fast_kernel<bf16s, 8>), dim3(bn_fast_blocks(groups, 8)), dim3(256), 0, as_stream(stream), (const bf16s *)x, (bf16s *)y,
-                       groups, c, mean, var, gamma, beta, eps, relu);
-  else if (fv == 4) {
-    DISPATCH_T(dtype, hipLaunchKernelGGL((bn_apply_fast_kernel<T, 4>), dim3(bn_fast_blocks(groups, 8)), dim3(256), 0, as_stream(stream), (const T *)x,
-                                         (T *)y, groups, c, mean, var, gamma, beta, eps, relu));
-  } else {
-    DISPATCH_T(dtype, hipLaunchKernelGGL(bn_apply_kernel<T>, dim3(ew_blocks(groups)), dim3(256), 0, as_stream(stream), (const T *)x, (T *)y,
-                                         groups, c, mean, var, gamma, beta, eps, relu));
-  }
+  cl_dispatch(dtype, fv, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    constexpr int V = decltype(tag)::V;
+    if (fv)
+      hipLaunchKernelGGL((bn_apply_fast_kernel<T, V>), dim3(bn_fast_blocks(groups, 8)), dim3(256), 0, as_stream(stream), (const T *)x, (T *)y, groups, c,
+                         mean, var, gamma, beta, eps, relu);
+    else if constexpr (V == 4)
+      hipLaunchKernelGGL(bn_apply_kernel<T>, dim3(ew_blocks(groups)), dim3(256), 0, as_stream(stream), (const T *)x, (T *)y, groups, c, mean, var,
+                         gamma, beta, eps, relu);
+  });
   NRPN_LAUNCH_CHECK("bn_apply");
   return NRPN_OK;
 }
@@ -420,27 +364,24 @@ __global__ void bn_bwd_apply_kernel(const T *__restrict__ x, const T *__restrict
   const float invr = 1.0f / (float)rows;
   for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += (long long)gridDim.x * blockDim.x) {
     const int cg = (int)(g % ct) * 4;
-    const f4 xv = vec4<T>::ld(x + g * 4);
-    f4 gv = vec4<T>::ld(dy + g * 4);
-    const f4 mu = *reinterpret_cast<const f4 *>(mean + cg), vv = *reinterpret_cast<const f4 *>(var + cg);
-    const f4 ga = *reinterpret_cast<const f4 *>(gamma + cg);
-    const f4 dg = *reinterpret_cast<const f4 *>(dgamma + cg), db = *reinterpret_cast<const f4 *>(dbeta + cg);
+    float xv[4], gv[4], mu[4], vv[4], ga[4], dg[4], db[4], be[4] = {0.f, 0.f, 0.f, 0.f}, o[4];
+    vecv<T, 4>::ld(x + g * 4, xv);
+    vecv<T, 4>::ld(dy + g * 4, gv);
+    ld_params<4>(mean + cg, mu); ld_params<4>(var + cg, vv); ld_params<4>(gamma + cg, ga); ld_params<4>(dgamma + cg, dg); ld_params<4>(dbeta + cg, db);
     if (relu && !beta) {
-      const f4 yv = vec4<T>::ld(y + g * 4);
+      float yv[4];
+      vecv<T, 4>::ld(y + g * 4, yv);
 #pragma unroll
       for (int k = 0; k < 4; ++k) gv[k] = yv[k] > 0.f ? gv[k] : 0.f;
     }
-    f4 be = {0, 0, 0, 0};
-    if (relu && beta) be = *reinterpret_cast<const f4 *>(beta + cg);
-    f4 o;
+    if (relu && beta) ld_params<4>(beta + cg, be);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const float is = 1.0f / sqrtf(vv[k] + eps);
-      if (relu && beta && !(((xv[k] - mu[k]) * is * ga[k] + be[k]) > 0.f)) gv[k] = 0.f;    // mask recomputed from x, y is not read
-      const float xh = (xv[k] - mu[k]) * is;
-      o[k] = ga[k] * is * (gv[k] - db[k] * invr - xh * dg[k] * invr);
+      if (relu && beta && !(bn_affine(xv[k], mu[k], is, ga[k], be[k]) > 0.f)) gv[k] = 0.f;    // mask recomputed from x, y is not read
+      o[k] = bn_dx(xv[k], gv[k], mu[k], is, ga[k], dg[k], db[k], invr);
     }
-    vec4<T>::st(dx + g * 4, o);
+    vecv<T, 4>::st(dx + g * 4, o);
   }
 }
 
@@ -452,31 +393,24 @@ extern "C" int nrpn_bn_backward(const void *x, const void *y, const void *dy, vo
   const int kSlab = slab_rows(rows);
   const int nb = (int)cdiv64(rows, kSlab);
   hipStream_t st = as_stream(stream);
-  if (g_chan_v8.load(std::memory_order_relaxed) && chan_v8(dtype, c, x, y, dy)) {
-    hipLaunchKernelGGL((chan_partial_kernel<bf16s, 1, 8>), dim3(nb, (c + 1023) / 1024), dim3(256), 0, st, (const bf16s *)x, (const bf16s *)y,
-                       (const bf16s *)dy, (long long)rows, c, mean, var, eps, relu, (float *)workspace, kSlab, gamma, beta);
-  } else {
-    DISPATCH_T(dtype, hipLaunchKernelGGL((chan_partial_kernel<T, 1, 4>), dim3(nb, (c + 1023) / 1024), dim3(256), 0, st, (const T *)x, (const T *)y, (const T *)dy,
-                                         (long long)rows, c, mean, var, eps, relu, (float *)workspace, kSlab, gamma, beta));
-  }
+  cl_dispatch(dtype, chan_v8(dtype, c, x, y, dy) ? 8 : 4, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    hipLaunchKernelGGL((chan_partial_kernel<T, 1, decltype(tag)::V>), dim3(nb, (c + 1023) / 1024), dim3(256), 0, st, (const T *)x, (const T *)y, (const T *)dy,
+                       (long long)rows, c, mean, var, eps, relu, (float *)workspace, kSlab, gamma, beta);
+  });
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((c + kFinCh - 1) / kFinCh), dim3(kFinCh, kFinLanes), 0, st, (const float *)workspace, nb, c, dbeta, dgamma, acc_dbeta, acc_dgamma);
-  int fv = bn_fast_v(c, dtype);
-  if (fv == 8 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 15))
-    fv = 0;                                                                                                // 16-byte accesses
+  const int fv = bn_fast_v(c, dtype, x, y, dy, (const void *)dx);
   const long long groups = rows * (c / (fv ? fv : 4));
-  if (fv == 8)
-    hipLaunchKernelGGL((bn_bwd_apply_fast_kernel<bf16s, 8>), dim3(bn_fast_blocks(groups, 5)), dim3(256), 0, st, (const bf16s *)x, (const bf16s *)y,
-                       (const bf16s *)dy, (bf16s *)dx, groups, c, (long long)rows, mean, var, gamma, eps, relu, (const float *)dgamma,
-                       (const float *)dbeta, beta);
-  else if (fv == 4) {
-    DISPATCH_T(dtype, hipLaunchKernelGGL((bn_bwd_apply_fast_kernel<T, 4>), dim3(bn_fast_blocks(groups, 8)), dim3(256), 0, st, (const T *)x, (const T *)y,
-                                         (const T *)dy, (T *)dx, groups, c, (long long)rows, mean, var, gamma, eps, relu,
-                                         (const float *)dgamma, (const float *)dbeta, beta));
-  } else {
-    DISPATCH_T(dtype, hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3(ew_blocks(groups)), dim3(256), 0, st, (const T *)x, (const T *)y,
-                                         (const T *)dy, (T *)dx, groups, c, (long long)rows, mean, var, gamma, eps, relu,
-                                         (const float *)dgamma, (const float *)dbeta, beta));
-  }
+  cl_dispatch(dtype, fv, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    constexpr int V = decltype(tag)::V;
+    if (fv)       // blocks per CU at the kernel's register count: 5 for the 8-wide form, 8 for the 4-wide
+      hipLaunchKernelGGL((bn_bwd_apply_fast_kernel<T, V>), dim3(bn_fast_blocks(groups, V == 8 ? 5 : 8)), dim3(256), 0, st, (const T *)x, (const T *)y,
+                         (const T *)dy, (T *)dx, groups, c, (long long)rows, mean, var, gamma, eps, relu, (const float *)dgamma, (const float *)dbeta, beta);
+    else if constexpr (V == 4)
+      hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3(ew_blocks(groups)), dim3(256), 0, st, (const T *)x, (const T *)y, (const T *)dy, (T *)dx, groups, c,
+                         (long long)rows, mean, var, gamma, eps, relu, (const float *)dgamma, (const float *)dbeta, beta);
+  });
   NRPN_LAUNCH_CHECK("bn_backward");
   return NRPN_OK;
 }
@@ -484,11 +418,12 @@ extern "C" int nrpn_bn_backward(const void *x, const void *y, const void *dy, vo
 template <typename T>
 __global__ void relu_bwd_kernel(const T *__restrict__ y, const T *__restrict__ dy, T *__restrict__ dx, long long groups) {
   for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += (long long)gridDim.x * blockDim.x) {
-    const f4 yv = vec4<T>::ld(y + g * 4);
-    f4 gv = vec4<T>::ld(dy + g * 4);
+    float yv[4], gv[4];
+    vecv<T, 4>::ld(y + g * 4, yv);
+    vecv<T, 4>::ld(dy + g * 4, gv);
 #pragma unroll
     for (int k = 0; k < 4; ++k) gv[k] = yv[k] > 0.f ? gv[k] : 0.f;
-    vec4<T>::st(dx + g * 4, gv);
+    vecv<T, 4>::st(dx + g * 4, gv);
   }
 }
 
@@ -512,90 +447,147 @@ static inline int pool_out(int in, int k, int s, int p, int ceil_mode) {
 }
 extern "C" int nrpn_pool_out_size(int in, int k, int s, int p, int ceil_mode) { return pool_out(in, k, s, p, ceil_mode); }
 
-// I = index type of the flat group / voxel arithmetic: unsigned (one 32-bit division per axis) whenever the tensors hold < 2^31 elements --
-// the 64-bit divisions of the first version were ~4x the VALU work of everything else in these kernels and bound them at a third of the HBM
-// rate (round 5) -- long long otherwise.
+// The rules both pool forms share, each stated once.  A window is scanned in ascending (a, b, d) order; the first in-grid element is taken
+// whatever its value, later ones only if strictly greater (torch: -inf padding, first maximum wins); the argmax is the window offset
+// code (a * k + b) * k + d, V codes stored as one 4- / 8-byte word.
 template <int V> struct argpack;
 template <> struct argpack<4> { typedef unsigned int type; };
 template <> struct argpack<8> { typedef unsigned long long type; };
+template <int V>
+__device__ __forceinline__ typename argpack<V>::type pack_codes(const int *bi) {
+  typename argpack<V>::type pk = 0;
+#pragma unroll
+  for (int q = 0; q < V; ++q) pk |= (typename argpack<V>::type)(unsigned char)bi[q] << (8 * q);
+  return pk;
+}
+template <typename P> __device__ __forceinline__ int code_at(P pk, int q) { return (int)((pk >> (8 * q)) & 0xff); }
 
+template <int V>
+__device__ __forceinline__ void pool_take(const float (&xv)[V], int code, bool in, bool &first, float (&best)[V], int (&bi)[V]) {
+#pragma unroll
+  for (int q = 0; q < V; ++q)
+    if (in && (first || xv[q] > best[q])) { best[q] = xv[q]; bi[q] = code; }
+  first = first && !in;
+}
+
+template <typename T, int V>
+__device__ __forceinline__ void pool_store(T *__restrict__ y, int8_t *__restrict__ arg, long long o, const float *best, const int *bi) {
+  vecv<T, V>::st(y + o, best);
+  if (arg) *reinterpret_cast<typename argpack<V>::type *>(arg + o) = pack_codes<V>(bi);
+}
+
+// The general forward scan of output voxel (xx, yy, z): the window clipped to the grid once per axis, scanned in ascending order; xb = the
+// scene's first voxel plus the lane's channel offset.  (The fast kernel keeps its own copy of these loops, with 32-bit offsets and the
+// 3-wide z run issued up front: routed through this function its 3/2/1 stem pool measured 26.65 us against 25.75 us.)
+template <typename T, int V>
+__device__ __forceinline__ void pool_scan(const T *__restrict__ xb, int xx, int yy, int z, int gx, int gy, int gz, int c, int k, int s, int p,
+                                          float (&best)[V], int (&bi)[V]) {
+  bool first = true;
+  const int a0 = max(0, p - xx * s), a1 = min(k, gx + p - xx * s);
+  const int b0 = max(0, p - yy * s), b1 = min(k, gy + p - yy * s);
+  const int d0 = max(0, p - z * s), d1 = min(k, gz + p - z * s);
+  for (int a = a0; a < a1; ++a) {
+    const int ix = xx * s - p + a;
+    for (int bq = b0; bq < b1; ++bq) {
+      const int iy = yy * s - p + bq;
+      for (int d = d0; d < d1; ++d) {
+        float xv[V];
+        vecv<T, V>::ld(xb + (((long long)ix * gy + iy) * gz + (z * s - p + d)) * (long long)c, xv);
+        pool_take<V>(xv, (a * k + bq) * k + d, true, first, best, bi);
+      }
+    }
+  }
+  if (first) {
+#pragma unroll
+    for (int q = 0; q < V; ++q) { best[q] = -INFINITY; bi[q] = 0; }
+  }
+}
+
+// Backward, gather form: every input voxel sums the dy of the windows whose argmax points at it (no atomics, deterministic).  Per axis the
+// windows containing coordinate x are those with offset a = (x + p) mod s, + s, + 2s, ... < k: at most ceil(k / s) candidates, enumerated
+// directly (8 for the 3/2/1 pool instead of testing all 27 offsets) and added in ascending (a, b, d) order.  ob = the scene's first output
+// voxel.  S = the stride as a template argument (1 or 2: shifts and masks, 32-bit voxel offsets inside the scene), 0 = runtime stride s.
+template <typename T, int V, int S>
+__device__ __forceinline__ void pool_gather(const T *__restrict__ dy, const int8_t *__restrict__ arg, long long ob, int cg, int xx, int yy, int z,
+                                            int ox, int oy, int oz, int c, int k, int s, int p, float *acc) {
+  typedef typename std::conditional<S != 0, int, long long>::type J;
+  const int st = S ? S : s;
+  auto rem = [&](int t) { return S ? t & (S - 1) : t % s; };
+  auto quo = [&](int t) { return S == 2 ? t >> 1 : S == 1 ? t : t / s; };
+  for (int a = rem(xx + p); a < k; a += st) {
+    const int tx = xx + p - a, wx = quo(tx);
+    if (tx < 0 || wx >= ox) continue;
+    for (int bq = rem(yy + p); bq < k; bq += st) {
+      const int ty = yy + p - bq, wy = quo(ty);
+      if (ty < 0 || wy >= oy) continue;
+      const long long orow = (ob + (long long)((J)wx * oy + wy) * oz) * c + cg;
+      const int code0 = (a * k + bq) * k;
+      for (int d = rem(z + p); d < k; d += st) {
+        const int tz = z + p - d, wz = quo(tz);
+        if (tz < 0 || wz >= oz) continue;
+        const long long o = orow + (long long)wz * c;
+        float gv[V];
+        vecv<T, V>::ld(dy + o, gv);
+        const typename argpack<V>::type pk = *reinterpret_cast<const typename argpack<V>::type *>(arg + o);      // V codes in one load
+#pragma unroll
+        for (int q = 0; q < V; ++q) acc[q] += code_at(pk, q) == code0 + d ? gv[q] : 0.f;
+      }
+    }
+  }
+}
+
+// General forms.  I = index type of the flat group / voxel arithmetic: unsigned (one 32-bit division per axis) whenever the tensors hold
+// < 2^31 elements -- the 64-bit divisions of the first version were ~4x the VALU work of everything else in these kernels and bound them
+// at a third of the HBM rate (round 5) -- long long otherwise.
 template <typename T, int V, typename I>
 __global__ void maxpool_fwd_kernel(const T *__restrict__ x, T *__restrict__ y, int8_t *__restrict__ arg, int n, int gx, int gy, int gz, int ox,
                                    int oy, int oz, int c, int k, int s, int p) {
   const I ct = (I)(c / V);
   const I total = (I)n * ox * oy * oz * ct;
   for (I g = (I)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (I)gridDim.x * blockDim.x) {
-    const I vox = g / ct;
-    const int cg = (int)(g - vox * ct) * V;
-    I v = vox;
-    const int z = (int)(v % (I)oz); v /= (I)oz;
-    const int yy = (int)(v % (I)oy); v /= (I)oy;
-    const int xx = (int)(v % (I)ox);
-    const long long b = (long long)(v / (I)ox);
+    const VoxelIdx v = voxel_index<V, I>(g, ct, ox, oy, oz);
     float best[V];
     int bi[V];
-    bool first = true;
-    // window clipped to the grid once per axis (torch: -inf padding, first maximum wins => ascending scan order is kept)
-    const int a0 = max(0, p - xx * s), a1 = min(k, gx + p - xx * s);
-    const int b0 = max(0, p - yy * s), b1 = min(k, gy + p - yy * s);
-    const int d0 = max(0, p - z * s), d1 = min(k, gz + p - z * s);
-    for (int a = a0; a < a1; ++a) {
-      const int ix = xx * s - p + a;
-      for (int bq = b0; bq < b1; ++bq) {
-        const int iy = yy * s - p + bq;
-        for (int d = d0; d < d1; ++d) {
-          const int iz = z * s - p + d;
-          float xv[V];
-          vecv<T, V>::ld(x + ((((b * gx + ix) * gy + iy) * gz + iz) * (long long)c + cg), xv);
-          const int code = (a * k + bq) * k + d;
+    pool_scan<T, V>(x + v.b * gx * gy * gz * c + v.cg, v.x, v.y, v.z, gx, gy, gz, c, k, s, p, best, bi);
+    pool_store<T, V>(y, arg, v.vox * c + v.cg, best, bi);
+  }
+}
+
+template <typename T, int V, typename I>
+__global__ void maxpool_bwd_kernel(const T *__restrict__ dy, const int8_t *__restrict__ arg, T *__restrict__ dx, int n, int gx, int gy, int gz,
+                                   int ox, int oy, int oz, int c, int k, int s, int p) {
+  const I ct = (I)(c / V);
+  const I total = (I)n * gx * gy * gz * ct;
+  for (I g = (I)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (I)gridDim.x * blockDim.x) {
+    const VoxelIdx v = voxel_index<V, I>(g, ct, gx, gy, gz);
+    float acc[V];
 #pragma unroll
-          for (int q = 0; q < V; ++q)
-            if (first || xv[q] > best[q]) { best[q] = xv[q]; bi[q] = code; }
-          first = false;
-        }
-      }
-    }
-    if (first) {
-#pragma unroll
-      for (int q = 0; q < V; ++q) { best[q] = -INFINITY; bi[q] = 0; }
-    }
-    const long long o = (long long)vox * c + cg;
-    vecv<T, V>::st(y + o, best);
-    if (arg) {           // V argmax codes as one 4- / 8-byte store
-      typename argpack<V>::type pk = 0;
-#pragma unroll
-      for (int q = 0; q < V; ++q) pk |= (typename argpack<V>::type)(unsigned char)bi[q] << (8 * q);
-      *reinterpret_cast<typename argpack<V>::type *>(arg + o) = pk;
-    }
+    for (int q = 0; q < V; ++q) acc[q] = 0.f;
+    pool_gather<T, V, 0>(dy, arg, v.b * ox * oy * oz, v.cg, v.x, v.y, v.z, ox, oy, oz, c, k, s, p, acc);
+    vecv<T, V>::st(dx + v.vox * c + v.cg, acc);
   }
 }
 
 // Round 6: the 32-bit forms above still spent most of their time dividing -- four runtime udivs per lane for the voxel decomposition and, in
 // the backward, a runtime `% s` and `/ s` per axis and per candidate window: ~200 VALU instructions per lane against 8 - 27 loads, VALU-bound at
-// 0.18 - 0.31 of the HBM rate.  The fast forms take the divisors as multiply-shift pairs (common.h FastDiv) and the stride as
-// a template argument (1 or 2: shifts and masks); results are those of the general kernels, bit for bit (same scan order, same first-maximum rule).
-struct PoolDiv { FastDiv ct, z, y, x; };
+// 0.18 - 0.31 of the HBM rate.  The fast forms take the divisors as multiply-shift pairs (chanlast.cuh VoxelDiv) and the stride as
+// a template argument; results are those of the general kernels, bit for bit (same scan order, same pool_take rule, the same pool_gather).
 static std::atomic<int> g_pool_fast{1};      // tools-only A/B switch (nerfrpn_tools.h): 0 = the general index arithmetic (pools, upsample-add)
 extern "C" int nrpn_set_pool_fast(int on) { g_pool_fast = on ? 1 : 0; return NRPN_OK; }
 
-// K = window size as a template argument (2 or 3; 0 = runtime loops): every load of a lane is then issued before the first comparison -- the
-// runtime-bounded loops with their data-dependent compare chain serialised 27 load latencies per lane (31 us for the 3/2/1 pool of the stem).
-// Out-of-grid window positions read a clamped address and are masked out of the comparison; `first` keeps torch's rule (the first in-grid
-// element is taken whatever its value, later ones only if strictly greater): same bits as the general kernel.
+// K = window size as a template argument (2 or 3; 0 = runtime loops): every load of a lane is then issued before the first
+// comparison -- the runtime-bounded loops with their data-dependent compare chain serialised 27 load latencies per lane (31 us for the 3/2/1
+// pool of the stem).  Out-of-grid window positions read a clamped address and are masked out of the comparison.
 template <typename T, int V, int K>
 __global__ void __launch_bounds__(256) maxpool_fwd_fast_kernel(const T *__restrict__ x, T *__restrict__ y, int8_t *__restrict__ arg, unsigned total,
-                                                               int gx, int gy, int gz, int ox, int oy, int oz, int c, int k, int s, int p, PoolDiv dv) {
+                                                               int gx, int gy, int gz, int ox, int oy, int oz, int c, int k, int s, int p, VoxelDiv dv) {
   for (unsigned g = blockIdx.x * 256u + threadIdx.x; g < total; g += gridDim.x * 256u) {
-    const unsigned vox = fastdiv(g, dv.ct);
-    const int cg = (int)(g - vox * dv.ct.d) * V;
-    const unsigned t1 = fastdiv(vox, dv.z), t2 = fastdiv(t1, dv.y), b = fastdiv(t2, dv.x);
-    const int z = (int)(vox - t1 * dv.z.d), yy = (int)(t1 - t2 * dv.y.d), xx = (int)(t2 - b * dv.x.d);
+    const VoxelIdx v = voxel_index<V>(g, dv);
     float best[V];
     int bi[V];
-    bool first = true;
-    const T *xb = x + (long long)b * gx * gy * gz * c + cg;
+    const T *xb = x + v.b * gx * gy * gz * c + v.cg;
     if constexpr (K > 0) {
-      const int x0 = xx * s - p, y0 = yy * s - p, z0 = z * s - p;
+      const int x0 = v.x * s - p, y0 = v.y * s - p, z0 = v.z * s - p;
       float xv[K * K * K][V];
 #pragma unroll
       for (int a = 0; a < K; ++a)
@@ -606,6 +598,7 @@ __global__ void __launch_bounds__(256) maxpool_fwd_fast_kernel(const T *__restri
             const int ix = min(max(x0 + a, 0), gx - 1), iy = min(max(y0 + bq, 0), gy - 1), iz = min(max(z0 + d, 0), gz - 1);
             vecv<T, V>::ld(xb + (long long)((ix * gy + iy) * gz + iz) * c, xv[(a * K + bq) * K + d]);
           }
+      bool first = true;
 #pragma unroll
       for (int q = 0; q < V; ++q) { best[q] = -INFINITY; bi[q] = 0; }
 #pragma unroll
@@ -616,12 +609,15 @@ __global__ void __launch_bounds__(256) maxpool_fwd_fast_kernel(const T *__restri
           for (int d = 0; d < K; ++d) {
             const bool in = (unsigned)(x0 + a) < (unsigned)gx && (unsigned)(y0 + bq) < (unsigned)gy && (unsigned)(z0 + d) < (unsigned)gz;
             const int code = (a * K + bq) * K + d;
+            // pool_take, spelled out: called as a function on rows of xv, the unrolled form needs 48 / 62 VGPRs instead of 39 / 47
 #pragma unroll
             for (int q = 0; q < V; ++q)
               if (in && (first || xv[code][q] > best[q])) { best[q] = xv[code][q]; bi[q] = code; }
             first = first && !in;
           }
     } else {
+      const int xx = v.x, yy = v.y, z = v.z;
+      bool first = true;
       const int a0 = max(0, p - xx * s), a1 = min(k, gx + p - xx * s);
       const int b0 = max(0, p - yy * s), b1 = min(k, gy + p - yy * s);
       const int d0 = max(0, p - z * s), d1 = min(k, gz + p - z * s);
@@ -631,8 +627,8 @@ __global__ void __launch_bounds__(256) maxpool_fwd_fast_kernel(const T *__restri
           const int iy = yy * s - p + bq;
           const T *row = xb + (long long)((ix * gy + iy) * gz + (z * s - p)) * c;
           const int code0 = (a * k + bq) * k;
-          if (k == 3) {       // the z run of a 3-wide window as three loads in flight (clamped address, masked compare): 9 latencies per lane, not 27
-            float xv[3][V];
+          if (k == 3) {
+            float xv[3][V];      // the z run of a 3-wide window as three loads in flight (clamped address, masked compare; in bounds because 2 * p <= k): 9 latencies per lane, not 27
 #pragma unroll
             for (int d = 0; d < 3; ++d) vecv<T, V>::ld(row + (long long)min(max(d, d0), d1 - 1) * c, xv[d]);
 #pragma unroll
@@ -660,31 +656,22 @@ __global__ void __launch_bounds__(256) maxpool_fwd_fast_kernel(const T *__restri
         for (int q = 0; q < V; ++q) { best[q] = -INFINITY; bi[q] = 0; }
       }
     }
-    const long long o = (long long)vox * c + cg;
-    vecv<T, V>::st(y + o, best);
-    if (arg) {
-      typename argpack<V>::type pk = 0;
-#pragma unroll
-      for (int q = 0; q < V; ++q) pk |= (typename argpack<V>::type)(unsigned char)bi[q] << (8 * q);
-      *reinterpret_cast<typename argpack<V>::type *>(arg + o) = pk;
-    }
+    pool_store<T, V>(y, arg, v.vox * c + v.cg, best, bi);
   }
 }
 
 // S = stride (1 or 2), K = window size (2 or 3: at most NC = ceil(K / S) candidate windows per axis, all NC^3 loads issued up front;
-// 0 = runtime loops).  Per axis the candidate windows of coordinate x are those with offset a = (x + p) mod S, + S, ... < k.
+// 0 = pool_gather's runtime loops).
 template <typename T, int V, int S, int K>
 __global__ void __launch_bounds__(256) maxpool_bwd_fast_kernel(const T *__restrict__ dy, const int8_t *__restrict__ arg, T *__restrict__ dx, unsigned total,
-                                                               int ox, int oy, int oz, int c, int k, int p, PoolDiv dv) {
+                                                               int ox, int oy, int oz, int c, int k, int p, VoxelDiv dv) {
   for (unsigned g = blockIdx.x * 256u + threadIdx.x; g < total; g += gridDim.x * 256u) {
-    const unsigned vox = fastdiv(g, dv.ct);
-    const int cg = (int)(g - vox * dv.ct.d) * V;
-    const unsigned t1 = fastdiv(vox, dv.z), t2 = fastdiv(t1, dv.y), b = fastdiv(t2, dv.x);
-    const int z = (int)(vox - t1 * dv.z.d), yy = (int)(t1 - t2 * dv.y.d), xx = (int)(t2 - b * dv.x.d);
+    const VoxelIdx v = voxel_index<V>(g, dv);
+    const int xx = v.x, yy = v.y, z = v.z, cg = v.cg;
     float acc[V];
 #pragma unroll
     for (int q = 0; q < V; ++q) acc[q] = 0.f;
-    const long long ob = (long long)b * ox * oy * oz;
+    const long long ob = v.b * ox * oy * oz;
     if constexpr (K > 0) {
       constexpr int NC = (K + S - 1) / S;
       const int ra = (xx + p) & (S - 1), rb = (yy + p) & (S - 1), rd = (z + p) & (S - 1);
@@ -703,7 +690,7 @@ __global__ void __launch_bounds__(256) maxpool_bwd_fast_kernel(const T *__restri
             vecv<T, V>::ld(dy + o, gv[(ja * NC + jb) * NC + jd]);
             pk[(ja * NC + jb) * NC + jd] = *reinterpret_cast<const typename argpack<V>::type *>(arg + o);
           }
-      // the general kernel adds the candidates in ascending (a, b, d) order: keep it (fp32 sums of up to 8 terms)
+      // pool_gather adds the candidates in ascending (a, b, d) order: keep it (fp32 sums of up to 8 terms)
 #pragma unroll
       for (int ja = 0; ja < NC; ++ja)
 #pragma unroll
@@ -717,103 +704,42 @@ __global__ void __launch_bounds__(256) maxpool_bwd_fast_kernel(const T *__restri
             const int code = (a * K + bq) * K + d;
             const int idx = (ja * NC + jb) * NC + jd;
 #pragma unroll
-            for (int q = 0; q < V; ++q) acc[q] += (ok && (int)((pk[idx] >> (8 * q)) & 0xff) == code) ? gv[idx][q] : 0.f;
+            for (int q = 0; q < V; ++q) acc[q] += (ok && code_at(pk[idx], q) == code) ? gv[idx][q] : 0.f;
           }
     } else {
-      for (int a = (xx + p) & (S - 1); a < k; a += S) {
-        const int tx = xx + p - a, wx = S == 2 ? tx >> 1 : tx;
-        if (tx < 0 || wx >= ox) continue;
-        for (int bq = (yy + p) & (S - 1); bq < k; bq += S) {
-          const int ty = yy + p - bq, wy = S == 2 ? ty >> 1 : ty;
-          if (ty < 0 || wy >= oy) continue;
-          const long long orow = (ob + (long long)(wx * oy + wy) * oz) * c + cg;
-          const int code0 = (a * k + bq) * k;
-          for (int d = (z + p) & (S - 1); d < k; d += S) {
-            const int tz = z + p - d, wz = S == 2 ? tz >> 1 : tz;
-            if (tz < 0 || wz >= oz) continue;
-            const long long o = orow + (long long)wz * c;
-            float gvv[V];
-            vecv<T, V>::ld(dy + o, gvv);
-            const typename argpack<V>::type pkk = *reinterpret_cast<const typename argpack<V>::type *>(arg + o);
-            const int code = code0 + d;
-#pragma unroll
-            for (int q = 0; q < V; ++q) acc[q] += ((int)((pkk >> (8 * q)) & 0xff) == code) ? gvv[q] : 0.f;
-          }
-        }
-      }
+      pool_gather<T, V, S>(dy, arg, ob, cg, xx, yy, z, ox, oy, oz, c, k, S, p, acc);
     }
-    vecv<T, V>::st(dx + (long long)vox * c + cg, acc);
-  }
-}
-
-// gather form: every input voxel sums the dy of the windows whose argmax points at it (no atomics, deterministic).  Per axis the
-// windows containing coordinate x are those with offset a = (x + p) mod s, + s, + 2s, ... < k: at most ceil(k / s) candidates,
-// enumerated directly (8 for the 3/2/1 pool instead of testing all 27 offsets).
-template <typename T, int V, typename I>
-__global__ void maxpool_bwd_kernel(const T *__restrict__ dy, const int8_t *__restrict__ arg, T *__restrict__ dx, int n, int gx, int gy, int gz,
-                                   int ox, int oy, int oz, int c, int k, int s, int p) {
-  const I ct = (I)(c / V);
-  const I total = (I)n * gx * gy * gz * ct;
-  for (I g = (I)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (I)gridDim.x * blockDim.x) {
-    const I vox = g / ct;
-    const int cg = (int)(g - vox * ct) * V;
-    I v = vox;
-    const int z = (int)(v % (I)gz); v /= (I)gz;
-    const int yy = (int)(v % (I)gy); v /= (I)gy;
-    const int xx = (int)(v % (I)gx);
-    const long long b = (long long)(v / (I)gx);
-    float acc[V];
-#pragma unroll
-    for (int q = 0; q < V; ++q) acc[q] = 0.f;
-    for (int a = (xx + p) % s; a < k; a += s) {
-      const int wx = (xx + p - a) / s;
-      if (xx + p - a < 0 || wx >= ox) continue;
-      for (int bq = (yy + p) % s; bq < k; bq += s) {
-        const int wy = (yy + p - bq) / s;
-        if (yy + p - bq < 0 || wy >= oy) continue;
-        for (int d = (z + p) % s; d < k; d += s) {
-          const int wz = (z + p - d) / s;
-          if (z + p - d < 0 || wz >= oz) continue;
-          const long long o = ((((b * ox + wx) * oy + wy) * oz + wz) * (long long)c + cg);
-          const int code = (a * k + bq) * k + d;
-          float gv[V];
-          vecv<T, V>::ld(dy + o, gv);
-          const typename argpack<V>::type pk = *reinterpret_cast<const typename argpack<V>::type *>(arg + o);      // V codes in one load
-#pragma unroll
-          for (int q = 0; q < V; ++q) acc[q] += ((int)((pk >> (8 * q)) & 0xff) == code) ? gv[q] : 0.f;
-        }
-      }
-    }
-    vecv<T, V>::st(dx + (long long)vox * c + cg, acc);
+    vecv<T, V>::st(dx + v.vox * c + cg, acc);
   }
 }
 
 extern "C" int nrpn_maxpool3d_fwd(const void *x, void *y, int8_t *argmax, int n, int gx, int gy, int gz, int c, int k, int s, int p,
                                   int ceil_mode, int dtype, nrpn_stream_t stream) {
   NRPN_REQUIRE(n > 0 && gx > 0 && gy > 0 && gz > 0 && c > 0 && c % 4 == 0 && k >= 1 && k <= 5 && s >= 1 && p >= 0, "maxpool_fwd: bad sizes");
+  NRPN_REQUIRE(2 * p <= k, "maxpool_fwd: padding %d is more than half the window %d (2 * p <= k, torch's rule)", p, k);
   NRPN_REQUIRE(x && y, "maxpool_fwd: null pointer");
   const int ox = pool_out(gx, k, s, p, ceil_mode), oy = pool_out(gy, k, s, p, ceil_mode), oz = pool_out(gz, k, s, p, ceil_mode);
   const bool small = (long long)n * gx * gy * gz * c < (1ll << 31);      // 32-bit index arithmetic (every real shape); 64-bit beyond
-#define NRPN_POOL_FWD(T_, V_, I_) hipLaunchKernelGGL((maxpool_fwd_kernel<T_, V_, I_>), dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream), \
-                                                     (const T_ *)x, (T_ *)y, argmax, n, gx, gy, gz, ox, oy, oz, c, k, s, p)
-  if (small && g_pool_fast.load(std::memory_order_relaxed)) {
-    const int v = (dtype == NRPN_BF16 && c % 8 == 0) ? 8 : 4;
-    const long long total = (long long)n * ox * oy * oz * (c / v);
-    const PoolDiv dv{make_fastdiv((unsigned)(c / v)), make_fastdiv((unsigned)oz), make_fastdiv((unsigned)oy), make_fastdiv((unsigned)ox)};
-#define NRPN_POOL_FWDF(T_, V_, K_) hipLaunchKernelGGL((maxpool_fwd_fast_kernel<T_, V_, K_>), dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream), \
-                                                      (const T_ *)x, (T_ *)y, argmax, (unsigned)total, gx, gy, gz, ox, oy, oz, c, k, s, p, dv)
-#define NRPN_POOL_FWDK(T_, V_) do { if (k == 2) NRPN_POOL_FWDF(T_, V_, 2); else NRPN_POOL_FWDF(T_, V_, 0); } while (0)   /* k = 3 fully unrolled: 216 registers of loads, measured slower (35.2 vs 31.5 us) */
-    if (v == 8) NRPN_POOL_FWDK(bf16s, 8); else { DISPATCH_T(dtype, NRPN_POOL_FWDK(T, 4)); }
-#undef NRPN_POOL_FWDK
-#undef NRPN_POOL_FWDF
-  } else if (dtype == NRPN_BF16 && c % 8 == 0) {
-    const long long total = (long long)n * ox * oy * oz * (c / 8);
-    if (small) NRPN_POOL_FWD(bf16s, 8, unsigned); else NRPN_POOL_FWD(bf16s, 8, long long);
-  } else {
-    const long long total = (long long)n * ox * oy * oz * (c / 4);
-    if (small) { DISPATCH_T(dtype, NRPN_POOL_FWD(T, 4, unsigned)); } else { DISPATCH_T(dtype, NRPN_POOL_FWD(T, 4, long long)); }
-  }
-#undef NRPN_POOL_FWD
+  const bool fast = small && g_pool_fast.load(std::memory_order_relaxed);
+  const int v = cl_width(dtype, c);
+  const long long total = (long long)n * ox * oy * oz * (c / v);
+  const VoxelDiv dv = make_voxel_div(c / v, ox, oy, oz);
+  const dim3 grid(ew_blocks(total)), block(256);
+  hipStream_t st = as_stream(stream);
+  cl_dispatch(dtype, v, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    constexpr int V = decltype(tag)::V;
+    const T *xp = (const T *)x;
+    T *yp = (T *)y;
+    if (fast && k == 2)
+      hipLaunchKernelGGL((maxpool_fwd_fast_kernel<T, V, 2>), grid, block, 0, st, xp, yp, argmax, (unsigned)total, gx, gy, gz, ox, oy, oz, c, k, s, p, dv);
+    else if (fast)      // k = 3 fully unrolled: 216 registers of loads, measured slower (35.2 vs 31.5 us)
+      hipLaunchKernelGGL((maxpool_fwd_fast_kernel<T, V, 0>), grid, block, 0, st, xp, yp, argmax, (unsigned)total, gx, gy, gz, ox, oy, oz, c, k, s, p, dv);
+    else if (small)
+      hipLaunchKernelGGL((maxpool_fwd_kernel<T, V, unsigned>), grid, block, 0, st, xp, yp, argmax, n, gx, gy, gz, ox, oy, oz, c, k, s, p);
+    else
+      hipLaunchKernelGGL((maxpool_fwd_kernel<T, V, long long>), grid, block, 0, st, xp, yp, argmax, n, gx, gy, gz, ox, oy, oz, c, k, s, p);
+  });
   NRPN_LAUNCH_CHECK("maxpool_fwd");
   return NRPN_OK;
 }
@@ -821,34 +747,38 @@ extern "C" int nrpn_maxpool3d_fwd(const void *x, void *y, int8_t *argmax, int n,
 extern "C" int nrpn_maxpool3d_bwd(const void *dy, const int8_t *argmax, void *dx, int n, int gx, int gy, int gz, int c, int k, int s, int p,
                                   int ceil_mode, int dtype, nrpn_stream_t stream) {
   NRPN_REQUIRE(n > 0 && gx > 0 && gy > 0 && gz > 0 && c > 0 && c % 4 == 0 && k >= 1 && k <= 5 && s >= 1 && p >= 0, "maxpool_bwd: bad sizes");
+  NRPN_REQUIRE(2 * p <= k, "maxpool_bwd: padding %d is more than half the window %d (2 * p <= k, torch's rule)", p, k);
   NRPN_REQUIRE(dy && argmax && dx, "maxpool_bwd: null pointer");
   const int ox = pool_out(gx, k, s, p, ceil_mode), oy = pool_out(gy, k, s, p, ceil_mode), oz = pool_out(gz, k, s, p, ceil_mode);
   const bool small = (long long)n * gx * gy * gz * c < (1ll << 31);
-#define NRPN_POOL_BWD(T_, V_, I_) hipLaunchKernelGGL((maxpool_bwd_kernel<T_, V_, I_>), dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream), \
-                                                     (const T_ *)dy, argmax, (T_ *)dx, n, gx, gy, gz, ox, oy, oz, c, k, s, p)
-  if (small && (s == 1 || s == 2) && g_pool_fast.load(std::memory_order_relaxed)) {
-    const int v = (dtype == NRPN_BF16 && c % 8 == 0) ? 8 : 4;
-    const long long total = (long long)n * gx * gy * gz * (c / v);
-    const PoolDiv dv{make_fastdiv((unsigned)(c / v)), make_fastdiv((unsigned)gz), make_fastdiv((unsigned)gy), make_fastdiv((unsigned)gx)};
-#define NRPN_POOL_BWDF(T_, V_, S_, K_) hipLaunchKernelGGL((maxpool_bwd_fast_kernel<T_, V_, S_, K_>), dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream), \
-                                                          (const T_ *)dy, argmax, (T_ *)dx, (unsigned)total, ox, oy, oz, c, k, p, dv)
-    // stride 2: the two pools of the VGG / ResNet paths (3/2/1 and 2/2/0) with every load up front; everything else on the runtime loops
-#define NRPN_POOL_BWDK(T_, V_) do { if (s == 2 && k == 2) NRPN_POOL_BWDF(T_, V_, 2, 2); /* (k = 3 unrolled loads all 8 candidates where 3.4 exist on average: 49.5 vs 35.4 us) */ \
-                                    else if (s == 2) NRPN_POOL_BWDF(T_, V_, 2, 0); else NRPN_POOL_BWDF(T_, V_, 1, 0); } while (0)
-    if (v == 8) NRPN_POOL_BWDK(bf16s, 8); else { DISPATCH_T(dtype, NRPN_POOL_BWDK(T, 4)); }
-#undef NRPN_POOL_BWDK
-#undef NRPN_POOL_BWDF
-  } else if (dtype == NRPN_BF16 && c % 8 == 0) {
-    const long long total = (long long)n * gx * gy * gz * (c / 8);
-    if (small) NRPN_POOL_BWD(bf16s, 8, unsigned); else NRPN_POOL_BWD(bf16s, 8, long long);
-  } else {
-    const long long total = (long long)n * gx * gy * gz * (c / 4);
-    if (small) { DISPATCH_T(dtype, NRPN_POOL_BWD(T, 4, unsigned)); } else { DISPATCH_T(dtype, NRPN_POOL_BWD(T, 4, long long)); }
-  }
-#undef NRPN_POOL_BWD
+  const bool fast = small && (s == 1 || s == 2) && g_pool_fast.load(std::memory_order_relaxed);
+  const int v = cl_width(dtype, c);
+  const long long total = (long long)n * gx * gy * gz * (c / v);
+  const VoxelDiv dv = make_voxel_div(c / v, gx, gy, gz);
+  const dim3 grid(ew_blocks(total)), block(256);
+  hipStream_t st = as_stream(stream);
+  cl_dispatch(dtype, v, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    constexpr int V = decltype(tag)::V;
+    const T *gp = (const T *)dy;
+    T *dp = (T *)dx;
+    // stride 2: the two pools of the VGG / ResNet paths (3/2/1 and 2/2/0); 2/2/0 with every load up front, everything else on the runtime
+    // loops (k = 3 unrolled loads all 8 candidates where 3.4 exist on average: 49.5 vs 35.4 us)
+    if (fast && s == 2 && k == 2)
+      hipLaunchKernelGGL((maxpool_bwd_fast_kernel<T, V, 2, 2>), grid, block, 0, st, gp, argmax, dp, (unsigned)total, ox, oy, oz, c, k, p, dv);
+    else if (fast && s == 2)
+      hipLaunchKernelGGL((maxpool_bwd_fast_kernel<T, V, 2, 0>), grid, block, 0, st, gp, argmax, dp, (unsigned)total, ox, oy, oz, c, k, p, dv);
+    else if (fast)
+      hipLaunchKernelGGL((maxpool_bwd_fast_kernel<T, V, 1, 0>), grid, block, 0, st, gp, argmax, dp, (unsigned)total, ox, oy, oz, c, k, p, dv);
+    else if (small)
+      hipLaunchKernelGGL((maxpool_bwd_kernel<T, V, unsigned>), grid, block, 0, st, gp, argmax, dp, n, gx, gy, gz, ox, oy, oz, c, k, s, p);
+    else
+      hipLaunchKernelGGL((maxpool_bwd_kernel<T, V, long long>), grid, block, 0, st, gp, argmax, dp, n, gx, gy, gz, ox, oy, oz, c, k, s, p);
+  });
   NRPN_LAUNCH_CHECK("maxpool_bwd");
   return NRPN_OK;
 }
+
 
 // =====================================================================================================================
 // FPN top-down: fine += nearest(coarse), legacy index rule src = min(floor(dst * (in/out)), in-1) in fp32
@@ -865,15 +795,9 @@ __global__ void upsample_add_fwd_kernel(T *__restrict__ fine, const T *__restric
   const I ct = (I)(c / V);
   const I total = (I)n * fx * fy * fz * ct;
   for (I g = (I)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (I)gridDim.x * blockDim.x) {
-    const I vox = g / ct;
-    const int cg = (int)(g - vox * ct) * V;
-    I v = vox;
-    const int z = (int)(v % (I)fz); v /= (I)fz;
-    const int y = (int)(v % (I)fy); v /= (I)fy;
-    const int x = (int)(v % (I)fx);
-    const long long b = (long long)(v / (I)fx);
-    const long long src = (((b * cx + nearest_src(x, cx, fx)) * cy + nearest_src(y, cy, fy)) * cz + nearest_src(z, cz, fz)) * (long long)c + cg;
-    const long long dst = (long long)vox * c + cg;
+    const VoxelIdx v = voxel_index<V, I>(g, ct, fx, fy, fz);
+    const long long src = (((v.b * cx + nearest_src(v.x, cx, fx)) * cy + nearest_src(v.y, cy, fy)) * cz + nearest_src(v.z, cz, fz)) * (long long)c + v.cg;
+    const long long dst = v.vox * c + v.cg;
     float a[V], bq[V];
     vecv<T, V>::ld(fine + dst, a);
     vecv<T, V>::ld(coarse + src, bq);
@@ -889,13 +813,9 @@ __global__ void upsample_add_bwd_kernel(const T *__restrict__ dfine, T *__restri
   const I ct = (I)(c / V);
   const I total = (I)n * cx * cy * cz * ct;
   for (I g = (I)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (I)gridDim.x * blockDim.x) {
-    const I vox = g / ct;
-    const int cg = (int)(g - vox * ct) * V;
-    I v = vox;
-    const int z = (int)(v % (I)cz); v /= (I)cz;
-    const int y = (int)(v % (I)cy); v /= (I)cy;
-    const int x = (int)(v % (I)cx);
-    const long long b = (long long)(v / (I)cx);
+    const VoxelIdx v = voxel_index<V, I>(g, ct, cx, cy, cz);
+    const int x = v.x, y = v.y, z = v.z, cg = v.cg;
+    const long long b = v.b;
     // candidate fine indices around x * fx / cx
     const int x0 = max(0, (int)((long long)x * fx / cx) - 1), x1 = min(fx - 1, (int)((long long)(x + 1) * fx / cx) + 1);
     const int y0 = max(0, (int)((long long)y * fy / cy) - 1), y1 = min(fy - 1, (int)((long long)(y + 1) * fy / cy) + 1);
@@ -916,7 +836,7 @@ __global__ void upsample_add_bwd_kernel(const T *__restrict__ dfine, T *__restri
         }
       }
     }
-    const long long dst = (long long)vox * c + cg;
+    const long long dst = v.vox * c + cg;
     if (accumulate) {
       float old[V];
       vecv<T, V>::ld(dcoarse + dst, old);
@@ -927,7 +847,7 @@ __global__ void upsample_add_bwd_kernel(const T *__restrict__ dfine, T *__restri
   }
 }
 
-// Round 6 fast forms (tensors below 2^31 elements): multiply-shift voxel decomposition (PoolDiv) and the per-axis scale in / out computed once
+// Round 6 fast forms (tensors below 2^31 elements): multiply-shift voxel decomposition (VoxelDiv) and the per-axis scale in / out computed once
 // on the host (the same correctly rounded fp32 quotient the general kernel forms per lane); the backward of an exact 2x pyramid step (every
 // level pair of the three backbones on 160^3-class grids) sums the 8 children 2x + {0,1} directly -- the general kernel finds them by testing
 // ~35 candidate indices with nearest_src and six 64-bit divisions per lane.  Same bits: same children, same ascending (x, y, z) order.
@@ -938,14 +858,11 @@ __device__ __forceinline__ int nearest_src_s(int dst, int in, float scale) {
 
 template <typename T, int V>
 __global__ void __launch_bounds__(256) upsample_add_fwd_fast_kernel(T *__restrict__ fine, const T *__restrict__ coarse, unsigned total, int cx, int cy,
-                                                                    int cz, int c, float sx, float sy, float sz, PoolDiv dv) {
+                                                                    int cz, int c, float sx, float sy, float sz, VoxelDiv dv) {
   for (unsigned g = blockIdx.x * 256u + threadIdx.x; g < total; g += gridDim.x * 256u) {
-    const unsigned vox = fastdiv(g, dv.ct);
-    const int cg = (int)(g - vox * dv.ct.d) * V;
-    const unsigned t1 = fastdiv(vox, dv.z), t2 = fastdiv(t1, dv.y), b = fastdiv(t2, dv.x);
-    const int z = (int)(vox - t1 * dv.z.d), y = (int)(t1 - t2 * dv.y.d), x = (int)(t2 - b * dv.x.d);
-    const long long src = ((((long long)b * cx + nearest_src_s(x, cx, sx)) * cy + nearest_src_s(y, cy, sy)) * cz + nearest_src_s(z, cz, sz)) * (long long)c + cg;
-    const long long dst = (long long)vox * c + cg;
+    const VoxelIdx v = voxel_index<V>(g, dv);
+    const long long src = (((v.b * cx + nearest_src_s(v.x, cx, sx)) * cy + nearest_src_s(v.y, cy, sy)) * cz + nearest_src_s(v.z, cz, sz)) * (long long)c + v.cg;
+    const long long dst = v.vox * c + v.cg;
     float a[V], bq[V];
     vecv<T, V>::ld(fine + dst, a);
     vecv<T, V>::ld(coarse + src, bq);
@@ -957,23 +874,21 @@ __global__ void __launch_bounds__(256) upsample_add_fwd_fast_kernel(T *__restric
 
 template <typename T, int V>
 __global__ void __launch_bounds__(256) upsample_add_bwd_x2_kernel(const T *__restrict__ dfine, T *__restrict__ dcoarse, unsigned total, int fx, int fy,
-                                                                  int fz, int c, int accumulate, PoolDiv dv) {
+                                                                  int fz, int c, int accumulate, VoxelDiv dv) {
   for (unsigned g = blockIdx.x * 256u + threadIdx.x; g < total; g += gridDim.x * 256u) {
-    const unsigned vox = fastdiv(g, dv.ct);
-    const int cg = (int)(g - vox * dv.ct.d) * V;
-    const unsigned t1 = fastdiv(vox, dv.z), t2 = fastdiv(t1, dv.y), b = fastdiv(t2, dv.x);
-    const int z = (int)(vox - t1 * dv.z.d), y = (int)(t1 - t2 * dv.y.d), x = (int)(t2 - b * dv.x.d);
+    const VoxelIdx v = voxel_index<V>(g, dv);
+    const int cg = v.cg;
     float gv[8][V], acc[V];
 #pragma unroll
     for (int k = 0; k < 8; ++k)
-      vecv<T, V>::ld(dfine + ((((long long)b * fx + 2 * x + (k >> 2)) * fy + 2 * y + ((k >> 1) & 1)) * fz + 2 * z + (k & 1)) * (long long)c + cg, gv[k]);
+      vecv<T, V>::ld(dfine + (((v.b * fx + 2 * v.x + (k >> 2)) * fy + 2 * v.y + ((k >> 1) & 1)) * fz + 2 * v.z + (k & 1)) * (long long)c + cg, gv[k]);
 #pragma unroll
     for (int q = 0; q < V; ++q) acc[q] = 0.f;
 #pragma unroll
     for (int k = 0; k < 8; ++k)
 #pragma unroll
       for (int q = 0; q < V; ++q) acc[q] += gv[k][q];
-    const long long dst = (long long)vox * c + cg;
+    const long long dst = v.vox * c + cg;
     if (accumulate) {
       float old[V];
       vecv<T, V>::ld(dcoarse + dst, old);
@@ -988,26 +903,24 @@ extern "C" int nrpn_upsample_add_fwd(void *fine, const void *coarse, int n, int 
                                      nrpn_stream_t stream) {
   NRPN_REQUIRE(n > 0 && fx > 0 && fy > 0 && fz > 0 && cx > 0 && cy > 0 && cz > 0 && c % 4 == 0, "upsample_add_fwd: bad sizes");
   NRPN_REQUIRE(fine && coarse, "upsample_add_fwd: null pointer");
-  const bool small = (long long)n * fx * fy * fz * c < (1ll << 31);      // 32-bit index arithmetic; bf16 with C % 8 == 0: 16-byte accesses
-#define NRPN_UP_FWD(T_, V_, I_) hipLaunchKernelGGL((upsample_add_fwd_kernel<T_, V_, I_>), dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream), \
-                                                   (T_ *)fine, (const T_ *)coarse, n, fx, fy, fz, cx, cy, cz, c)
-  if (small && g_pool_fast.load(std::memory_order_relaxed)) {
-    const int v = (dtype == NRPN_BF16 && c % 8 == 0) ? 8 : 4;
-    const long long total = (long long)n * fx * fy * fz * (c / v);
-    const PoolDiv dv{make_fastdiv((unsigned)(c / v)), make_fastdiv((unsigned)fz), make_fastdiv((unsigned)fy), make_fastdiv((unsigned)fx)};
-    const float sx = (float)cx / (float)fx, sy = (float)cy / (float)fy, sz = (float)cz / (float)fz;
-#define NRPN_UP_FWDF(T_, V_) hipLaunchKernelGGL((upsample_add_fwd_fast_kernel<T_, V_>), dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream), \
-                                                (T_ *)fine, (const T_ *)coarse, (unsigned)total, cx, cy, cz, c, sx, sy, sz, dv)
-    if (v == 8) NRPN_UP_FWDF(bf16s, 8); else { DISPATCH_T(dtype, NRPN_UP_FWDF(T, 4)); }
-#undef NRPN_UP_FWDF
-  } else if (dtype == NRPN_BF16 && c % 8 == 0) {
-    const long long total = (long long)n * fx * fy * fz * (c / 8);
-    if (small) NRPN_UP_FWD(bf16s, 8, unsigned); else NRPN_UP_FWD(bf16s, 8, long long);
-  } else {
-    const long long total = (long long)n * fx * fy * fz * (c / 4);
-    if (small) { DISPATCH_T(dtype, NRPN_UP_FWD(T, 4, unsigned)); } else { DISPATCH_T(dtype, NRPN_UP_FWD(T, 4, long long)); }
-  }
-#undef NRPN_UP_FWD
+  const bool small = (long long)n * fx * fy * fz * c < (1ll << 31);      // 32-bit index arithmetic
+  const bool fast = small && g_pool_fast.load(std::memory_order_relaxed);
+  const int v = cl_width(dtype, c);
+  const long long total = (long long)n * fx * fy * fz * (c / v);
+  const VoxelDiv dv = make_voxel_div(c / v, fx, fy, fz);
+  const float sx = (float)cx / (float)fx, sy = (float)cy / (float)fy, sz = (float)cz / (float)fz;
+  const dim3 grid(ew_blocks(total)), block(256);
+  hipStream_t st = as_stream(stream);
+  cl_dispatch(dtype, v, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    constexpr int V = decltype(tag)::V;
+    if (fast)
+      hipLaunchKernelGGL((upsample_add_fwd_fast_kernel<T, V>), grid, block, 0, st, (T *)fine, (const T *)coarse, (unsigned)total, cx, cy, cz, c, sx, sy, sz, dv);
+    else if (small)
+      hipLaunchKernelGGL((upsample_add_fwd_kernel<T, V, unsigned>), grid, block, 0, st, (T *)fine, (const T *)coarse, n, fx, fy, fz, cx, cy, cz, c);
+    else
+      hipLaunchKernelGGL((upsample_add_fwd_kernel<T, V, long long>), grid, block, 0, st, (T *)fine, (const T *)coarse, n, fx, fy, fz, cx, cy, cz, c);
+  });
   NRPN_LAUNCH_CHECK("upsample_add_fwd");
   return NRPN_OK;
 }
@@ -1017,24 +930,22 @@ extern "C" int nrpn_upsample_add_bwd(const void *dfine, void *dcoarse, int n, in
   NRPN_REQUIRE(n > 0 && fx > 0 && fy > 0 && fz > 0 && cx > 0 && cy > 0 && cz > 0 && c % 4 == 0, "upsample_add_bwd: bad sizes");
   NRPN_REQUIRE(dfine && dcoarse, "upsample_add_bwd: null pointer");
   const bool small = (long long)n * fx * fy * fz * c < (1ll << 31);
-#define NRPN_UP_BWD(T_, V_, I_) hipLaunchKernelGGL((upsample_add_bwd_kernel<T_, V_, I_>), dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream), \
-                                                   (const T_ *)dfine, (T_ *)dcoarse, n, fx, fy, fz, cx, cy, cz, c, accumulate)
-  if (small && fx == 2 * cx && fy == 2 * cy && fz == 2 * cz && g_pool_fast.load(std::memory_order_relaxed)) {
-    const int v = (dtype == NRPN_BF16 && c % 8 == 0) ? 8 : 4;
-    const long long total = (long long)n * cx * cy * cz * (c / v);
-    const PoolDiv dv{make_fastdiv((unsigned)(c / v)), make_fastdiv((unsigned)cz), make_fastdiv((unsigned)cy), make_fastdiv((unsigned)cx)};
-#define NRPN_UP_BWDF(T_, V_) hipLaunchKernelGGL((upsample_add_bwd_x2_kernel<T_, V_>), dim3(ew_blocks(total)), dim3(256), 0, as_stream(stream), \
-                                                (const T_ *)dfine, (T_ *)dcoarse, (unsigned)total, fx, fy, fz, c, accumulate, dv)
-    if (v == 8) NRPN_UP_BWDF(bf16s, 8); else { DISPATCH_T(dtype, NRPN_UP_BWDF(T, 4)); }
-#undef NRPN_UP_BWDF
-  } else if (dtype == NRPN_BF16 && c % 8 == 0) {
-    const long long total = (long long)n * cx * cy * cz * (c / 8);
-    if (small) NRPN_UP_BWD(bf16s, 8, unsigned); else NRPN_UP_BWD(bf16s, 8, long long);
-  } else {
-    const long long total = (long long)n * cx * cy * cz * (c / 4);
-    if (small) { DISPATCH_T(dtype, NRPN_UP_BWD(T, 4, unsigned)); } else { DISPATCH_T(dtype, NRPN_UP_BWD(T, 4, long long)); }
-  }
-#undef NRPN_UP_BWD
+  const bool x2 = small && fx == 2 * cx && fy == 2 * cy && fz == 2 * cz && g_pool_fast.load(std::memory_order_relaxed);
+  const int v = cl_width(dtype, c);
+  const long long total = (long long)n * cx * cy * cz * (c / v);
+  const VoxelDiv dv = make_voxel_div(c / v, cx, cy, cz);
+  const dim3 grid(ew_blocks(total)), block(256);
+  hipStream_t st = as_stream(stream);
+  cl_dispatch(dtype, v, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    constexpr int V = decltype(tag)::V;
+    if (x2)
+      hipLaunchKernelGGL((upsample_add_bwd_x2_kernel<T, V>), grid, block, 0, st, (const T *)dfine, (T *)dcoarse, (unsigned)total, fx, fy, fz, c, accumulate, dv);
+    else if (small)
+      hipLaunchKernelGGL((upsample_add_bwd_kernel<T, V, unsigned>), grid, block, 0, st, (const T *)dfine, (T *)dcoarse, n, fx, fy, fz, cx, cy, cz, c, accumulate);
+    else
+      hipLaunchKernelGGL((upsample_add_bwd_kernel<T, V, long long>), grid, block, 0, st, (const T *)dfine, (T *)dcoarse, n, fx, fy, fz, cx, cy, cz, c, accumulate);
+  });
   NRPN_LAUNCH_CHECK("upsample_add_bwd");
   return NRPN_OK;
 }
@@ -1047,23 +958,15 @@ template <typename T, bool FWD>
 __global__ void subsample_kernel(const T *__restrict__ src, T *__restrict__ dst, int n, int gx, int gy, int gz, int ox, int oy, int oz,
                                  int c, int s) {
   // FWD: dst[n,ox,oy,oz,c] = src[n, x*s, y*s, z*s, c];  !FWD: dst[n,gx,gy,gz,c] = (x,y,z all multiples of s) ? src[..] : 0
-  const int ct = c / 4;
+  const long long ct = c / 4;
   const long long total = (long long)n * (FWD ? (long long)ox * oy * oz : (long long)gx * gy * gz) * ct;
   for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < total; g += (long long)gridDim.x * blockDim.x) {
-    const int cg = (int)(g % ct) * 4;
-    long long v = g / ct;
-    const int dz = FWD ? oz : gz, dy = FWD ? oy : gy, dx = FWD ? ox : gx;
-    const int z = (int)(v % dz); v /= dz;
-    const int y = (int)(v % dy); v /= dy;
-    const int x = (int)(v % dx);
-    const long long b = v / dx;
-    if (FWD) {
-      vec4<T>::st(dst + (g / ct) * (long long)c + cg, vec4<T>::ld(src + ((((b * gx + x * s) * gy + y * s) * gz + z * s) * (long long)c + cg)));
-    } else {
-      f4 val = {0, 0, 0, 0};
-      if (x % s == 0 && y % s == 0 && z % s == 0) val = vec4<T>::ld(src + ((((b * ox + x / s) * oy + y / s) * oz + z / s) * (long long)c + cg));
-      vec4<T>::st(dst + (g / ct) * (long long)c + cg, val);
-    }
+    const VoxelIdx v = FWD ? voxel_index<4, long long>(g, ct, ox, oy, oz) : voxel_index<4, long long>(g, ct, gx, gy, gz);
+    float val[4] = {0.f, 0.f, 0.f, 0.f};
+    if (FWD) vecv<T, 4>::ld(src + ((((v.b * gx + v.x * s) * gy + v.y * s) * gz + v.z * s) * (long long)c + v.cg), val);
+    else if (v.x % s == 0 && v.y % s == 0 && v.z % s == 0)
+      vecv<T, 4>::ld(src + ((((v.b * ox + v.x / s) * oy + v.y / s) * oz + v.z / s) * (long long)c + v.cg), val);
+    vecv<T, 4>::st(dst + v.vox * c + v.cg, val);
   }
 }
 
@@ -1083,11 +986,12 @@ extern "C" int nrpn_subsample3d(const void *src, void *dst, int n, int gx, int g
 template <typename T>
 __global__ void add_relu_kernel(const T *__restrict__ a, const T *__restrict__ b, T *__restrict__ y, long long groups, int relu) {
   for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += (long long)gridDim.x * blockDim.x) {
-    const f4 av = vec4<T>::ld(a + g * 4), bv = vec4<T>::ld(b + g * 4);
-    f4 o;
+    float av[4], bv[4], o[4];
+    vecv<T, 4>::ld(a + g * 4, av);
+    vecv<T, 4>::ld(b + g * 4, bv);
 #pragma unroll
     for (int k = 0; k < 4; ++k) { o[k] = av[k] + bv[k]; if (relu) o[k] = fmaxf(o[k], 0.f); }
-    vec4<T>::st(y + g * 4, o);
+    vecv<T, 4>::st(y + g * 4, o);
   }
 }
 
@@ -1137,8 +1041,8 @@ __global__ void planes4_to_cl_kernel(const float *__restrict__ src, T *__restric
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     const long long b = i / voxels, v = i - b * voxels;
     const float *s = src + b * 4 * voxels + v;
-    const f4 o = {s[0], s[voxels], s[2 * voxels], s[3 * voxels]};
-    vec4<T>::st(dst + i * 4, o);
+    const float o[4] = {s[0], s[voxels], s[2 * voxels], s[3 * voxels]};
+    vecv<T, 4>::st(dst + i * 4, o);
   }
 }
 
@@ -1292,13 +1196,14 @@ __global__ void __launch_bounds__(256) a2a_reduce_kernel(const bf16s *__restrict
                                                          long long chunk, bf16s *__restrict__ out) {
   for (long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < chunk; i += (long long)gridDim.x * blockDim.x * 4) {
     if (i + 4 <= chunk) {
-      f4 acc = {0.f, 0.f, 0.f, 0.f};
+      float acc[4] = {0.f, 0.f, 0.f, 0.f};
       for (int r = 0; r < world; ++r) {
-        const f4 v = (r == rank) ? *reinterpret_cast<const f4 *>(local + i) : vec4<bf16s>::ld(recv + (long long)r * chunk + i);
+        float v[4];
+        if (r == rank) vecv<float, 4>::ld(local + i, v); else vecv<bf16s, 4>::ld(recv + (long long)r * chunk + i, v);
 #pragma unroll
         for (int k = 0; k < 4; ++k) acc[k] += v[k];
       }
-      vec4<bf16s>::st(out + i, acc);
+      vecv<bf16s, 4>::st(out + i, acc);
     } else {
       for (long long e = i; e < chunk; ++e) {
         float acc = 0.f;
@@ -1615,8 +1520,7 @@ __global__ void ingest_kernel(const S *__restrict__ src, T *__restrict__ dst, lo
     for (int k = 0; k < 4; ++k) c[k] = sizeof(S) == 1 ? (float)src[v * 4 + k] * (1.0f / 255.0f) : (float)src[v * 4 + k];
     if (mode == 1) c[3] = fminf(fmaxf(1.0f - expf(-expf(c[3]) / 100.0f), 0.f), 1.f);                 // density_to_alpha
     else if (mode == 2) c[3] = fminf(fmaxf(1.0f - expf(-fmaxf(c[3], 0.f) / 100.0f), 0.f), 1.f);     // ScanNet variant (relu)
-    f4 o = {c[0], c[1], c[2], c[3]};
-    vec4<T>::st(dst + v * 4, o);
+    vecv<T, 4>::st(dst + v * 4, c);
   }
 }
 
@@ -1698,7 +1602,8 @@ __global__ void ingest_augment_kernel(const S *__restrict__ src, T *__restrict__
             }
           }
     }
-    vec4<T>::st(dst + v * 4, o);
+    const float ov[4] = {o[0], o[1], o[2], o[3]};
+    vecv<T, 4>::st(dst + v * 4, ov);
   }
 }
 

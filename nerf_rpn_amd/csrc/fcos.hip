@@ -7,40 +7,14 @@
 //     midpoint-offset OBB decode; inference.py:56-140, utils.py:12-62).
 // Locations are never materialised: (level, scene, voxel) -> (x, y, z) = idx * stride + stride / 2 is index arithmetic.
 // Compiled with -ffp-contract=off: the targets compare fp32 expressions against thresholds exactly as torch evaluates them.
-#include "common.h"
+#include "chanlast.cuh"
 #include <atomic>
 #include "geometry.cuh"
-
-typedef unsigned short bf16s;
-
-#define DISPATCH_T(dtype, ...)                                 \
-  if ((dtype) == NRPN_F32) { typedef float T; __VA_ARGS__; }   \
-  else { typedef bf16s T; __VA_ARGS__; }
-
-static inline int ew_blocks(long long work, int cap = 8192) { long long b = (work + 255) / 256; return (int)(b > cap ? cap : (b < 1 ? 1 : b)); }
 
 // =====================================================================================================================
 // GroupNorm
 // =====================================================================================================================
 // 4 consecutive channels per thread (8/16-byte accesses); C % 4 == 0
-template <typename T> struct gvec4;
-template <> struct gvec4<float> {
-  typedef __attribute__((ext_vector_type(4))) float f4;
-  static __device__ __forceinline__ void ld(const float *p, float *v) { const f4 t = *reinterpret_cast<const f4 *>(p); v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3]; }
-  static __device__ __forceinline__ void st(float *p, const float *v) { f4 t = {v[0], v[1], v[2], v[3]}; *reinterpret_cast<f4 *>(p) = t; }
-};
-template <> struct gvec4<bf16s> {
-  typedef __attribute__((ext_vector_type(4))) unsigned short us4;
-  static __device__ __forceinline__ void ld(const bf16s *p, float *v) {
-    const us4 t = *reinterpret_cast<const us4 *>(p);
-    v[0] = bf16_bits_to_f32(t[0]); v[1] = bf16_bits_to_f32(t[1]); v[2] = bf16_bits_to_f32(t[2]); v[3] = bf16_bits_to_f32(t[3]);
-  }
-  static __device__ __forceinline__ void st(bf16s *p, const float *v) {
-    us4 t = {f32_to_bf16_bits(v[0]), f32_to_bf16_bits(v[1]), f32_to_bf16_bits(v[2]), f32_to_bf16_bits(v[3])};
-    *reinterpret_cast<us4 *>(p) = t;
-  }
-};
-
 // per-(sample, channel) sums over the sample's rows: fwd (sum d, sum d^2) with d = x - K, K = x[n, row 0, first channel of the group]
 // (gn_finalize_fwd_kernel reads K back); bwd (sum g, sum g * (x - mean)) with g = dy * relu mask.  Both are shifted so that they do not
 // cancel when |mean| >> std: the unshifted sum x^2 - count * mean^2 in fp32 lost 1.6e-3 of rstd at mean / std = 100.
@@ -74,14 +48,14 @@ __global__ void __launch_bounds__(256) gn_partial_kernel(const T *__restrict__ x
     for (long long r = r0 + ty; r < r1; r += lanes) {
       const long long o = (base + r) * c + tx * 4;
       float xv[4];
-      gvec4<T>::ld(x + o, xv);
+      vecv<T, 4>::ld(x + o, xv);
       if (!BWD) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) { const float d = xv[k] - sh[k]; s0[k] += d; s1[k] += d * d; }
       } else {
         float g[4], yv[4] = {1.f, 1.f, 1.f, 1.f};
-        gvec4<T>::ld(dy + o, g);
-        if (relu) gvec4<T>::ld(y + o, yv);
+        vecv<T, 4>::ld(dy + o, g);
+        if (relu) vecv<T, 4>::ld(y + o, yv);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const float gk = (relu && !(yv[k] > 0.f)) ? 0.f : g[k];
@@ -150,14 +124,14 @@ __global__ void gn_apply_kernel(const T *__restrict__ x, T *__restrict__ y, cons
     const int ch = (int)(i % c);
     const long long n = i / c / rows;
     float v[4];
-    gvec4<T>::ld(x + i, v);
+    vecv<T, 4>::ld(x + i, v);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int sg = (int)n * groups + (ch + k) / cpg;
       v[k] = (v[k] - mean[sg]) * rstd[sg] * gamma[ch + k] + beta[ch + k];
       if (relu) v[k] = fmaxf(v[k], 0.f);
     }
-    gvec4<T>::st(y + i, v);
+    vecv<T, 4>::st(y + i, v);
   }
 }
 
@@ -166,18 +140,6 @@ __global__ void gn_apply_kernel(const T *__restrict__ x, T *__restrict__ y, cons
 // the block, blockIdx.y = sample) so gamma / beta / mean / rstd / coefficients leave the loop together with the 64-bit `i % c`, `i / c / rows` and the
 // per-element `(ch + k) / cpg` of the general kernels.  Needs C / groups % 8 == 0 (a lane's 8 channels share one group).  Same expressions, term
 // for term (this unit is compiled with -ffp-contract=off): same bits as the general kernels.
-typedef __attribute__((ext_vector_type(8))) unsigned short gn_us8;
-__device__ __forceinline__ void gn_ld8(const bf16s *p, float *v) {
-  const gn_us8 u = *reinterpret_cast<const gn_us8 *>(p);
-#pragma unroll
-  for (int q = 0; q < 8; ++q) v[q] = bf16_bits_to_f32(u[q]);
-}
-__device__ __forceinline__ void gn_st8(bf16s *p, const float *v) {
-  gn_us8 u;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) u[q] = f32_to_bf16_bits(v[q]);
-  *reinterpret_cast<gn_us8 *>(p) = u;
-}
 static std::atomic<int> g_gn_fast{1};      // tools-only A/B switch (nerfrpn_tools.h)
 extern "C" int nrpn_set_gn_fast(int on) { g_gn_fast = on ? 1 : 0; return NRPN_OK; }
 static inline bool gn_fast_ok(int c, int groups, int dtype) {
@@ -199,13 +161,13 @@ __global__ void __launch_bounds__(256) gn_apply_fast_kernel(const bf16s *__restr
 #pragma unroll 2
   for (long long r = (long long)blockIdx.x * lanes + rl; r < rows; r += (long long)gridDim.x * lanes) {
     float v[8];
-    gn_ld8(x + (base + r) * c + cg, v);
+    vecv<bf16s, 8>::ld(x + (base + r) * c + cg, v);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       v[k] = (v[k] - m) * rs * ga[k] + be[k];
       if (relu) v[k] = fmaxf(v[k], 0.f);
     }
-    gn_st8(y + (base + r) * c + cg, v);
+    vecv<bf16s, 8>::st(y + (base + r) * c + cg, v);
   }
 }
 
@@ -225,16 +187,16 @@ __global__ void __launch_bounds__(256) gn_bwd_apply_fast_kernel(const bf16s *__r
   for (long long r = (long long)blockIdx.x * lanes + rl; r < rows; r += (long long)gridDim.x * lanes) {
     const long long o = (base + r) * c + cg;
     float xv[8], gv[8], yv[8], ov[8];
-    gn_ld8(x + o, xv);
-    gn_ld8(dy + o, gv);
-    if (relu) gn_ld8(y + o, yv);
+    vecv<bf16s, 8>::ld(x + o, xv);
+    vecv<bf16s, 8>::ld(dy + o, gv);
+    if (relu) vecv<bf16s, 8>::ld(y + o, yv);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const float g = (relu && !(yv[k] > 0.f)) ? 0.f : gv[k];
       const float xh = (xv[k] - m) * rs;
       ov[k] = rs * (g * ga[k] - cB - xh * cA);
     }
-    gn_st8(dx + o, ov);
+    vecv<bf16s, 8>::st(dx + o, ov);
   }
 }
 static inline int gn_fast_blocks(long long rows, int c) {
@@ -284,9 +246,9 @@ __global__ void gn_bwd_apply_kernel(const T *__restrict__ x, const T *__restrict
     const int ch = (int)(i % c);
     const long long n = i / c / rows;
     float xv[4], gv[4], yv[4] = {1.f, 1.f, 1.f, 1.f}, o[4];
-    gvec4<T>::ld(x + i, xv);
-    gvec4<T>::ld(dy + i, gv);
-    if (relu) gvec4<T>::ld(y + i, yv);
+    vecv<T, 4>::ld(x + i, xv);
+    vecv<T, 4>::ld(dy + i, gv);
+    if (relu) vecv<T, 4>::ld(y + i, yv);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int sg = (int)n * groups + (ch + k) / cpg;
@@ -294,7 +256,7 @@ __global__ void gn_bwd_apply_kernel(const T *__restrict__ x, const T *__restrict
       const float xh = (xv[k] - mean[sg]) * rstd[sg];
       o[k] = rstd[sg] * (g * gamma[ch + k] - coef[sg * 2 + 1] - xh * coef[sg * 2]);
     }
-    gvec4<T>::st(dx + i, o);
+    vecv<T, 4>::st(dx + i, o);
   }
 }
 

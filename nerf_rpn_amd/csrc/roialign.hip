@@ -12,28 +12,9 @@
 // reference's fp32 atomicAdd (:329-336) -- and needs no RoI sorting.
 // Address of feature element (x, y, z) is ((x*Y + y)*Z + z)*C + c for every shape (the reference's index expression is only that
 // element on cubic maps -- DESIGN.md, oracle/roialign.c).
-#include "common.h"
+#include "chanlast.cuh"
 
 namespace {
-typedef unsigned short bf16s;
-typedef __attribute__((ext_vector_type(4))) float f4;
-typedef __attribute__((ext_vector_type(4))) unsigned short us4;
-
-template <typename T> struct v4;
-template <> struct v4<float> {
-  static __device__ __forceinline__ f4 ld(const float *p) { return *reinterpret_cast<const f4 *>(p); }
-  static __device__ __forceinline__ void st(float *p, f4 v) { *reinterpret_cast<f4 *>(p) = v; }
-};
-template <> struct v4<bf16s> {
-  static __device__ __forceinline__ f4 ld(const bf16s *p) {
-    const us4 u = *reinterpret_cast<const us4 *>(p);
-    return f4{bf16_bits_to_f32(u[0]), bf16_bits_to_f32(u[1]), bf16_bits_to_f32(u[2]), bf16_bits_to_f32(u[3])};
-  }
-  static __device__ __forceinline__ void st(bf16s *p, f4 v) {
-    *reinterpret_cast<us4 *>(p) = us4{f32_to_bf16_bits(v[0]), f32_to_bf16_bits(v[1]), f32_to_bf16_bits(v[2]), f32_to_bf16_bits(v[3])};
-  }
-};
-
 struct Roi {
   int batch, gw, gl, gh;
   float cw, cl, ch, bin_w, bin_l, bin_h, start_w, start_l, start_h, cosT, sinT, count;
@@ -118,15 +99,15 @@ __global__ void __launch_bounds__(64) roi_align_kernel(const T *__restrict__ fea
   const long long base = (long long)o.batch * width * length * height;
   if (o.batch < 0 || o.batch >= nbatch) {      // a bad batch index would read / atomically write out of bounds: the RoI pools to zeros
     if (MODE == 0) {
-      const f4 z = {0.f, 0.f, 0.f, 0.f};
-      for (int cg = threadIdx.x * 4; cg < channels; cg += 256) v4<T>::st(out + ((long long)n * bins + bin) * channels + cg, z);
+      const float z[4] = {0.f, 0.f, 0.f, 0.f};
+      for (int cg = threadIdx.x * 4; cg < channels; cg += 256) vecv<T, 4>::st(out + ((long long)n * bins + bin) * channels + cg, z);
     }
     return;
   }
   for (int cg = threadIdx.x * 4; cg < channels; cg += 256) {
-    f4 acc = {0.f, 0.f, 0.f, 0.f};
-    f4 top = {0.f, 0.f, 0.f, 0.f};
-    if (MODE == 1) top = v4<T>::ld(grad_out + ((long long)n * bins + bin) * channels + cg);
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    float top[4] = {0.f, 0.f, 0.f, 0.f};
+    if (MODE == 1) vecv<T, 4>::ld(grad_out + ((long long)n * bins + bin) * channels + cg, top);
     for (int iz = 0; iz < o.gh; ++iz)
       for (int iy = 0; iy < o.gl; ++iy)
         for (int ix = 0; ix < o.gw; ++ix) {
@@ -135,10 +116,11 @@ __global__ void __launch_bounds__(64) roi_align_kernel(const T *__restrict__ fea
           const Taps t = taps(width, length, height, x, y, z);
           if (!t.valid) continue;
           if (MODE == 0) {
-            f4 val = {0.f, 0.f, 0.f, 0.f};
+            float val[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
-              const f4 v = v4<T>::ld(feat + (base + tap_voxel(t, k, length, height)) * channels + cg);
+              float v[4];
+              vecv<T, 4>::ld(feat + (base + tap_voxel(t, k, length, height)) * channels + cg, v);
 #pragma unroll
               for (int q = 0; q < 4; ++q) val[q] += t.w[k] * v[q];
             }
@@ -161,7 +143,7 @@ __global__ void __launch_bounds__(64) roi_align_kernel(const T *__restrict__ fea
     if (MODE == 0) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) acc[q] = acc[q] / o.count;
-      v4<T>::st(out + ((long long)n * bins + bin) * channels + cg, acc);
+      vecv<T, 4>::st(out + ((long long)n * bins + bin) * channels + cg, acc);
     }
   }
 }

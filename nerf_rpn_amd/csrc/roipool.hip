@@ -13,10 +13,9 @@
 // they lie), as torch's max_pool3d does.  Backward scatters through 64-bit fixed-point integer atomics (2^44, as csrc/roialign.hip): integer
 // addition is associative, so the gradient is bit-identical from run to run.
 // Compiled with -ffp-contract=off: floor / ceil of the rotated sample positions decide which voxels are read.
-#include "common.h"
+#include "chanlast.cuh"
 
 namespace {
-typedef unsigned short bf16s;
 constexpr double kFix = 17592186044416.0;     // 2^44
 constexpr float kFixClamp = 262144.f;         // 2^18
 

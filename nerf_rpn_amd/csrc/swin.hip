@@ -7,17 +7,8 @@
 // inverses are pure index arithmetic inside the attention kernels -- nothing is rolled, padded or permuted in memory.
 // The attention matmuls are 64x32x64 per (window, head) ("attention GEMMs are tiny"): one wavefront per
 // (window, head), one lane per query token, K/V staged in LDS and broadcast-read, softmax in registers.
-#include "common.h"
+#include "chanlast.cuh"
 
-typedef unsigned short bf16s;
-typedef __attribute__((ext_vector_type(4))) float f4;
-typedef __attribute__((ext_vector_type(4))) unsigned short us4;
-
-#define DISPATCH_T(dtype, ...)                                 \
-  if ((dtype) == NRPN_F32) { typedef float T; __VA_ARGS__; }   \
-  else { typedef bf16s T; __VA_ARGS__; }
-
-static inline int ew_blocks(long long work) { long long b = (work + 255) / 256; return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b)); }
 
 // =====================================================================================================================
 // patch embedding gather: [N,X,Y,Z,4] -> [N,X/p,Y/p,Z/p, 4*p^3] with inner order (c, dx, dy, dz) = the flattened
@@ -205,35 +196,19 @@ extern "C" int nrpn_layernorm_bwd(const void *x, const void *dy, void *dx, const
 // =====================================================================================================================
 // exact GELU (nn.GELU default) and the residual join y = a + s[n] * b (s = stochastic-depth row scale, or 1)
 // =====================================================================================================================
-// 4 elements per thread (8/16-byte accesses) when the count allows it
-template <typename T> struct ev4;
-template <> struct ev4<float> {
-  static __device__ __forceinline__ void ld(const float *p, float *v) { const f4 t = *reinterpret_cast<const f4 *>(p); v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3]; }
-  static __device__ __forceinline__ void st(float *p, const float *v) { f4 t = {v[0], v[1], v[2], v[3]}; *reinterpret_cast<f4 *>(p) = t; }
-};
-template <> struct ev4<bf16s> {
-  static __device__ __forceinline__ void ld(const bf16s *p, float *v) {
-    const us4 t = *reinterpret_cast<const us4 *>(p);
-    v[0] = bf16_bits_to_f32(t[0]); v[1] = bf16_bits_to_f32(t[1]); v[2] = bf16_bits_to_f32(t[2]); v[3] = bf16_bits_to_f32(t[3]);
-  }
-  static __device__ __forceinline__ void st(bf16s *p, const float *v) {
-    us4 t = {f32_to_bf16_bits(v[0]), f32_to_bf16_bits(v[1]), f32_to_bf16_bits(v[2]), f32_to_bf16_bits(v[3])};
-    *reinterpret_cast<us4 *>(p) = t;
-  }
-};
-
+// 4 elements per thread (8/16-byte accesses): the count is a multiple of 4
 template <typename T, bool BWD>
 __global__ void gelu_kernel(const T *__restrict__ x, const T *__restrict__ dy, T *__restrict__ out, long long groups) {
   for (long long gi = (long long)blockIdx.x * blockDim.x + threadIdx.x; gi < groups; gi += (long long)gridDim.x * blockDim.x) {
     float v[4], d[4] = {0.f, 0.f, 0.f, 0.f}, o[4];
-    ev4<T>::ld(x + gi * 4, v);
-    if (BWD) ev4<T>::ld(dy + gi * 4, d);
+    vecv<T, 4>::ld(x + gi * 4, v);
+    if (BWD) vecv<T, 4>::ld(dy + gi * 4, d);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const float cdf = 0.5f * (1.0f + erff(v[k] * 0.70710678118654752f));
       o[k] = BWD ? d[k] * (cdf + v[k] * 0.39894228040143268f * expf(-0.5f * v[k] * v[k])) : v[k] * cdf;
     }
-    ev4<T>::st(out + gi * 4, o);
+    vecv<T, 4>::st(out + gi * 4, o);
   }
 }
 
@@ -254,11 +229,11 @@ __global__ void scale_add_kernel(const T *__restrict__ a, const T *__restrict__ 
   for (long long gi = (long long)blockIdx.x * blockDim.x + threadIdx.x; gi < groups; gi += (long long)gridDim.x * blockDim.x) {
     const float s = scale ? scale[gi * 4 / per_sample] : 1.0f;
     float av[4] = {0.f, 0.f, 0.f, 0.f}, bv[4], o[4];
-    if (a) ev4<T>::ld(a + gi * 4, av);
-    ev4<T>::ld(b + gi * 4, bv);
+    if (a) vecv<T, 4>::ld(a + gi * 4, av);
+    vecv<T, 4>::ld(b + gi * 4, bv);
 #pragma unroll
     for (int k = 0; k < 4; ++k) o[k] = av[k] + s * bv[k];
-    ev4<T>::st(y + gi * 4, o);
+    vecv<T, 4>::st(y + gi * 4, o);
   }
 }
 

@@ -58,6 +58,29 @@ def test_argument_errors_are_reported_not_fatal():
         lib.call("conv3d_fwd", 1, 1, 0, 1, 1, 4, 4, 4, 64, 64, 64, 5, 0, 0, 0, 0, 0)
 
 
+def test_chanlast_divisors_and_width_rule_on_the_host(tmp_path):
+    """csrc/chanlast.cuh, host side: make_fastdiv / make_voxel_div evaluated as the device evaluates them equal plain division over a sweep
+    of divisors and indices up to 2^31 - 1, the width rule and the (dtype, width) dispatch -- a stand-alone program under ASan + UBSan."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    exe = str(tmp_path / "chanlast_invariants")
+    cc = subprocess.run(["hipcc", "--cuda-host-only", "-std=c++17", "-O1", "-Xarch_host", "-fsanitize=address,undefined",
+                         os.path.join(here, "chanlast_invariants.hip"), "-o", exe], capture_output=True, text=True)
+    assert cc.returncode == 0, cc.stderr[-4000:]
+    run = subprocess.run([exe], capture_output=True, text=True, env={**os.environ, "ASAN_OPTIONS": "detect_leaks=0"})
+    assert run.returncode == 0 and "runtime error" not in run.stderr, (run.stdout[-4000:], run.stderr[-4000:])
+    assert int(run.stdout.split()[0]) > 2_000_000 and run.stdout.split()[2] == "0", run.stdout
+
+
+def test_maxpool_padding_beyond_half_the_window_is_refused():
+    """torch's rule 2 * p <= k: beyond it a window can lie wholly in the padding, which the fast forward's clamped loads do not cover.
+    The check returns before any pointer is looked at or any kernel launched."""
+    for name in ("maxpool3d_fwd", "maxpool3d_bwd"):
+        with pytest.raises(lib.NrpnError, match=r"2 \* p <= k"):
+            lib.call(name, 0, 0, 0, 1, 8, 8, 8, 4, 3, 2, 2, 0, lib.F32, 0)      # k = 3, s = 2, p = 2
+        with pytest.raises(lib.NrpnError, match="null pointer"):
+            lib.call(name, 0, 0, 0, 1, 8, 8, 8, 4, 3, 2, 1, 0, lib.F32, 0)      # p = 1 passes the size checks
+
+
 def test_product_path_has_no_cpu_fallback():
     from nerf_rpn_amd import ops
     with pytest.raises(lib.NrpnError, match="non-CUDA"):
