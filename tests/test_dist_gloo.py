@@ -1,6 +1,7 @@
 """CPU, world sizes 2 / 3 / 4 / 8 (gloo): the data-parallel gradient exchange of nerf_rpn_amd.engine.FlatTrainer -- rank-0 weight
 broadcast, bucketed SUM all-reduce launched from post-accumulate hooks, unused-parameter buckets, 1/world folding.
-(The optimiser kernels themselves are GPU-only and are covered by tests/test_gpu_conv.py::test_layout_roundtrip_and_adamw.)"""
+(The optimiser kernels themselves are GPU-only and are covered by tests/test_gpu_optim_kernels.py, against the float64
+references of tests/optim_ref.py.)"""
 import os
 import socket
 

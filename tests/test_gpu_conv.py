@@ -236,7 +236,10 @@ def test_upsample_add(sizes, dev):
     assert torch.allclose(cf(ch.grad.cpu()), cr.grad, atol=1e-5) and torch.allclose(cf(fh.grad.cpu()), fr.grad, atol=1e-6)
 
 
-def test_layout_roundtrip_and_adamw(dev):
+def test_layout_roundtrip_and_adamw_smoke(dev):
+    """The channels-last round trip, and a three-step smoke check of grad_sumsq + adamw_step against torch.optim.AdamW with
+    clip_grad_norm_ (10007 elements: the remainder loop and the scalar tail only; no shadow, no zero_grad, grad_scale 1).  What holds the
+    optimiser kernels element by element, at every loop and configuration, is tests/test_gpu_optim_kernels.py."""
     from nerf_rpn_amd import ops
     torch.manual_seed(0)
     x = torch.randn(2, 5, 7, 6, 3)

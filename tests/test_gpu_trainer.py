@@ -163,8 +163,8 @@ def test_flat_trainer_trains_like_torch_adamw(dtype, golden, dev):
         # diag_trainer_cone.py: step 2, rpn.head.conv.0 + fpn_convs.1 only) and Adam turns that into a fraction of an lr-sized step.
         # Required: 99.9 % of the significant entries within 5 % of the total step budget, none further off than ONE reversed Adam step
         # (an entry whose gradient changed sign on one of the steps travels +lr instead of -lr: 2 lr; measured worst 1.25 lr), and the
-        # update as a whole the same vector (cosine > 0.9999, norm within 0.1 %).  The AdamW kernel itself is held to torch.optim.AdamW on
-        # IDENTICAL gradients in test_gpu_conv.py::test_layout_roundtrip_and_adamw (1e-6).
+        # update as a whole the same vector (cosine > 0.9999, norm within 0.1 %).  The AdamW kernel itself is held to a float64 AdamW on
+        # IDENTICAL inputs, element by element inside derived bounds, in test_gpu_optim_kernels.py (reference: optim_ref.py).
         d = (tr.flat_params() - after_ref)[sig].abs()
         assert (d < 0.05 * lr * steps).float().mean().item() > 0.999, (d < 0.05 * lr * steps).float().mean().item()
         # an entry further off than 0.3 lr x steps must BELONG to a tensor whose gradient the detector above saw change by
