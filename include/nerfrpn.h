@@ -906,6 +906,40 @@ int nrpn_nerfraylosses_backward(const float *rgb_map, const float *target_s, con
                                 const float *weights, const float *target_d, const uint8_t *target_vd, int64_t num_rays,
                                 int num_samples, const float *g_losses, float *g_rgb, float *g_depth, float *g_w, nrpn_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The front end of a NeRF training step, ops.nerf_train_batch and ops.nerf_train_samples (nerf_train.py).  [f11]  DESIGN.md 3.22.
+ * One launch each; no atomics, no allocation, no host synchronisation; a ray's result depends on nothing but the ray.
+ * nrpn_nerftrain_work_bytes(num_rays, num_samples): bytes of nrpn_nerftrain_samples' scratch (a ray's cdf, num_samples doubles);
+ *   -1 outside the supported range (2 <= num_samples <= 65536, num_rays * num_samples < 2^31 - 64).
+ * nrpn_nerftrain_batch replaces get_ray_batch_from_one_image (data/scannet/run_nerf.py:650-670) after the pixel draw, with
+ *   precompute_depth_sampling (:159-162), the view directions of render (:127-132) and perturb_z_vals (:480-495).  camera f32 [16] and
+ *   the ray of a pixel as nrpn_nerfrender_frame has them, bit for bit; pix i32 [num_rays]: row-major pixel indices v * width + u in
+ *   any order, repeats allowed (an index outside the image is clamped into it, not reported: that would synchronise); image f32
+ *   [height][width][3]; depth f32 [height][width][2] (depth, std) and valid u8 [height][width], both or neither; z f32
+ *   [num_samples] and t_rand f32 [num_rays][num_samples], both or neither (num_samples is not read without them) -> rays f32
+ *   [num_rays][6] (o, d), viewdirs f32 [num_rays][3] = d / |d|, target_s f32 [num_rays][3]; with depth: target_d f32 [num_rays][2],
+ *   target_vd u8 [num_rays], depth_range f32 [num_rays][3] = (d, d - 3 s, d + 3 s); with t_rand: z1 f32 [num_rays][num_samples] =
+ *   lower + (upper - lower) * t_rand over the midpoints of z.  float32 in the reference's operation order, no contraction.
+ * nrpn_nerftrain_samples replaces the second sample list of render_rays at train time (:588-592): compute_samples_around_depth
+ *   (:497-502; raw2depth :431-435) for the rays without a depth, sample_3sigma (:471-478) of the given range for those with one, and
+ *   the stochastic sample_pdf.  raw1 f32 [num_rays][num_samples][4] at z1 f32 [num_samples] (z1_stride 0) or
+ *   [num_rays][num_samples] (z1_stride num_samples); rays f32 [num_rays][6]; depth_range f32 [num_rays][3] or null: a ray with
+ *   depth_range[r][0] >= near takes its bins from depth_range[r][1] .. [r][2], every other ray (all of them with null) from the depth
+ *   and std of its first list, the std clamped below at lower_bound; edges clamped to [near, far]; u f32 [num_rays][num_samples] in
+ *   any order, or null for u_j = j / (num_samples - 1) -> z2 f32 [num_rays][num_samples], the inverse cdf at u (searchsorted from the
+ *   right, denominators below 1e-5 replaced by 1) in u's order, not sorted.  Float64 after the float32 inputs; the cdf is a serial sum
+ *   in bin order.  With u and depth_range null and a shared z1 whose lower_bound is z1[-1] - z1[-2], the bits of
+ *   nrpn_nerfrender_samples.  work: nrpn_nerftrain_work_bytes bytes, 8-byte aligned.
+ * ---------------------------------------------------------------------------------------------- */
+int64_t nrpn_nerftrain_work_bytes(int64_t num_rays, int num_samples);
+int nrpn_nerftrain_batch(const float *camera, int height, int width, const int *pix, int64_t num_rays, const float *image,
+                         const float *depth, const uint8_t *valid, const float *z, const float *t_rand, int num_samples, float *rays,
+                         float *viewdirs, float *target_s, float *target_d, uint8_t *target_vd, float *depth_range, float *z1,
+                         nrpn_stream_t stream);
+int nrpn_nerftrain_samples(const float *raw1, const float *z1, int z1_stride, const float *rays, const float *depth_range,
+                           const float *u, int num_samples, float lower_bound, float near, float far, int64_t num_rays, void *work,
+                           int64_t work_bytes, float *z2, nrpn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 // The per-ray float64 arithmetic of compute_weights and raw2outputs (data/scannet/run_nerf.py:419-469) over the merge of a ray's
 // two non-decreasing sample lists (forward_with_additonal_samples :504-512), shared by nerfrender.hip (views, the camera-embedding
-// objective) and nerfcomposite.hip (the differentiable ray stage): one definition, so the two give the same bits.
+// objective) and nerfcomposite.hip (the differentiable ray stage): one definition, so the two give the same bits.  Likewise the ray
+// of a pixel, raw2depth's walk and sample_3sigma's bins with the inverse-cdf expression, shared by nerfrender.hip and nerftrain.hip.
 #pragma once
 #include "common.h"
 
@@ -109,5 +110,75 @@ struct RaySums {
     return 1.0 / (q < 1e-10 ? 1e-10 : q);
   }
 };
+
+// The ray of pixel p = v W + u (get_rays as render :108-110 uses it): o = t, d = R [(u - cx) / fx, -(v - cy) / fy, -1],
+// float32 in the reference's order.  camera: fx, fy, cx, cy, then c2w[:3, :4] row-major; ray[6] = o, d
+__device__ __forceinline__ void pixel_ray(const float *__restrict__ camera, int W, int64_t p, float *__restrict__ ray) {
+  const float u = (float)(p % W), v = (float)(p / W);
+  const float fx = camera[0], fy = camera[1], cx = camera[2], cy = camera[3];
+  const float *m = camera + 4;
+  const float a = __fdiv_rn(__fsub_rn(u, cx), fx), b = -__fdiv_rn(__fsub_rn(v, cy), fy), c = -1.0f;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    ray[k] = m[4 * k + 3];
+    ray[3 + k] = __fadd_rn(__fadd_rn(__fmul_rn(a, m[4 * k]), __fmul_rn(b, m[4 * k + 1])), __fmul_rn(c, m[4 * k + 2]));
+  }
+}
+
+// raw2depth (:431-435) of one list: sg its sigma, 4 floats apart.  Two walks: the depth, then the variance about it
+__device__ __forceinline__ void depth_and_var(const float *z, const float *sg, int S, double nd, double &depth, double &var) {
+  depth = 0.0, var = 0.0;
+  merged_walk(z, sg, S, nullptr, nullptr, 0, nd, [&](bool, int, float zv, double w) { depth += w * (double)zv; });
+  const double d = depth;
+  double v = 0.0;
+  merged_walk(z, sg, S, nullptr, nullptr, 0, nd, [&](bool, int, float zv, double w) {
+    const double dz = (double)zv - d;
+    v += dz * dz * w;
+  });
+  var = v;
+}
+
+struct Bins {           // sample_3sigma (:471-478): edges and weights of the N - 1 bins between lo and hi, clamped to [near, far]
+  double lo, hi, step, near, far;
+  int N;
+  __device__ __forceinline__ Bins(double lo_, double hi_, int n, double near_, double far_)
+      : lo(lo_), hi(hi_), step((hi_ - lo_) / (double)(n - 1)), near(near_), far(far_), N(n) {}
+  __device__ __forceinline__ double edge(int i) const {
+    const double t = (double)i / (double)(N - 1);
+    const double e = lo * (1.0 - t) + hi * t;
+    return fmin(fmax(e, near), far);
+  }
+  __device__ __forceinline__ double weight(int i) const {       // factor * N(x_i) + the 1e-5 of sample_pdf
+    const double x = N > 2 ? -3.0 + 6.0 * (double)i / (double)(N - 2) : -3.0;
+    const double factor = (edge(i + 1) - edge(i)) / step;
+    return factor * (0.3989422804014327 * exp(-0.5 * x * x)) + 1e-5;
+  }
+  __device__ __forceinline__ double total() const {
+    double t = 0.0;
+    for (int i = 0; i < N - 1; ++i) t += weight(i);
+    return t;
+  }
+  // sample_pdf's sample at u between cdf entries below (value cb) and above (value ca)
+  __device__ __forceinline__ float sample(double u, int below, double cb, int above, double ca) const {
+    double denom = ca - cb;
+    if (denom < 1e-5) denom = 1.0;
+    const double tt = (u - cb) / denom;
+    const double eb = edge(below);
+    return (float)(eb + tt * (edge(above) - eb));
+  }
+};
+
+// compute_samples_around_depth's range (:497-502) from raw2depth's moments, the std clamped below at lower_bound
+__device__ __forceinline__ void range_around_depth(double depth, double var, double lower_bound, double &lo, double &hi) {
+  const double std = fmax(sqrt(var), lower_bound);
+  lo = depth - 3.0 * std, hi = depth + 3.0 * std;
+}
+
+// ... and its bins
+__device__ __forceinline__ Bins bins_around_depth(double depth, double var, double lower_bound, int N, double near, double far) {
+  double lo, hi;
+  range_around_depth(depth, var, lower_bound, lo, hi);
+  return Bins(lo, hi, N, near, far);
+}
 
 }  // namespace nerfray

@@ -38,17 +38,7 @@ struct RayPoints {
 __global__ void nerfrender_rays_kernel(const float *__restrict__ camera, int W, int64_t ray0, int count, float *__restrict__ rays) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
-  const int64_t r = ray0 + i;
-  const float u = (float)(r % W), v = (float)(r / W);
-  const float fx = camera[0], fy = camera[1], cx = camera[2], cy = camera[3];
-  const float *m = camera + 4;
-  const float a = __fdiv_rn(__fsub_rn(u, cx), fx), b = -__fdiv_rn(__fsub_rn(v, cy), fy), c = -1.0f;
-  float *o = rays + (int64_t)i * 6;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    o[k] = m[4 * k + 3];
-    o[3 + k] = __fadd_rn(__fadd_rn(__fmul_rn(a, m[4 * k]), __fmul_rn(b, m[4 * k + 1])), __fmul_rn(c, m[4 * k + 2]));
-  }
+  pixel_ray(camera, W, ray0 + i, rays + (int64_t)i * 6);
 }
 
 // ---- trunk -----------------------------------------------------------------------------------------------------------------------
@@ -172,40 +162,17 @@ __global__ __launch_bounds__(kTile) void nerfrender_head_kernel(RayPoints rp, co
 }
 
 // ---- per-ray reductions, float64 ---------------------------------------------------------------------------------------------
-struct Bins {           // sample_3sigma (:471-478): edges and weights of the N - 1 bins between depth -+ 3 std, clamped to [near, far]
-  double lo, hi, step, near, far;
-  int N;
-  __device__ __forceinline__ double edge(int i) const {
-    const double t = (double)i / (double)(N - 1);
-    const double e = lo * (1.0 - t) + hi * t;
-    return fmin(fmax(e, near), far);
-  }
-  __device__ __forceinline__ double weight(int i) const {       // factor * N(x_i) + the 1e-5 of sample_pdf
-    const double x = N > 2 ? -3.0 + 6.0 * (double)i / (double)(N - 2) : -3.0;
-    const double factor = (edge(i + 1) - edge(i)) / step;
-    return factor * (0.3989422804014327 * exp(-0.5 * x * x)) + 1e-5;
-  }
-};
-
-// raw [rays][S][4], z [S] shared, rays [rays][6] -> z2 [rays][S]
+// raw [rays][S][4], z [S] shared, rays [rays][6] -> z2 [rays][S]; Bins and the depth / variance walk are nerf_ray.cuh's
 __global__ void nerfrender_sample_kernel(const float *__restrict__ raw, const float *__restrict__ rays, const float *__restrict__ z, int S,
                                          float near, float far, int num_rays, float *__restrict__ z2) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= num_rays) return;
   const double nd = ray_norm(rays + (int64_t)r * 6 + 3);
   const float *sg = raw + (int64_t)r * S * 4 + 3;
-  double depth = 0.0, var = 0.0;         // two walks of the one list: the depth, then the variance about it
-  merged_walk(z, sg, S, nullptr, nullptr, 0, nd, [&](bool, int, float zv, double w) { depth += w * (double)zv; });
-  merged_walk(z, sg, S, nullptr, nullptr, 0, nd, [&](bool, int, float zv, double w) {
-    const double dz = (double)zv - depth;
-    var += dz * dz * w;
-  });
-  const double std = fmax(sqrt(var), (double)z[S - 1] - (double)z[S - 2]);
-  Bins b;
-  b.lo = depth - 3.0 * std, b.hi = depth + 3.0 * std, b.N = S, b.near = near, b.far = far;
-  b.step = (b.hi - b.lo) / (double)(S - 1);
-  double total = 0.0;
-  for (int i = 0; i < S - 1; ++i) total += b.weight(i);
+  double depth, var;
+  depth_and_var(z, sg, S, nd, depth, var);
+  const Bins b = bins_around_depth(depth, var, (double)z[S - 1] - (double)z[S - 2], S, near, far);
+  const double total = b.total();
   // inverse CDF at u_j = j / (S - 1) (deterministic sample_pdf): k = number of cdf entries <= u (searchsorted, right), cb = cdf[k - 1],
   // ca = cdf[k]; both u and the cdf are non-decreasing, so k only moves forward
   int k = 1;
@@ -219,12 +186,7 @@ __global__ void nerfrender_sample_kernel(const float *__restrict__ raw, const fl
       if (k < S) ca = cb + b.weight(k - 1) / total;
     }
     const int below = k - 1, above = k < S ? k : S - 1;
-    const double c_above = k < S ? ca : cb;
-    double denom = c_above - cb;
-    if (denom < 1e-5) denom = 1.0;
-    const double tt = (u - cb) / denom;
-    const double eb = b.edge(below);
-    out[j] = (float)(eb + tt * (b.edge(above) - eb));
+    out[j] = b.sample(u, below, cb, above, k < S ? ca : cb);
   }
 }
 

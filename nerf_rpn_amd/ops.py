@@ -3131,3 +3131,117 @@ def nerf_ray_losses(rgb_map, target_s, depth_map=None, z_vals=None, weights=None
         raise lib.NrpnError(f"{who} expects target_vd [{R}], got {list(target_vd.shape)}")
     target_vd = (target_vd != 0).to(torch.uint8).contiguous()
     return NerfRayLossesFn.apply(rgb_map, depth_map, weights, target_s, z_vals, target_d, target_vd)
+
+
+# ======================================================================================================================
+# the front end of a NeRF training step (nerf_train.py)  [f11]
+# ======================================================================================================================
+def nerf_train_batch(intrinsic, c2w, H, W, pix, image, depth=None, valid=None, z=None, t_rand=None, check=False):
+    """get_ray_batch_from_one_image (run_nerf.py:650-670) after the pixel draw, in one launch.
+
+    intrinsic = (fx, fy, cx, cy) and c2w [>=3, 4] as nerf_render takes them; pix [R] integer row-major pixel indices v * W + u, in any
+    order, repeats allowed; image [H, W, 3]; depth [H, W, 2] (depth, std) with valid [H, W], both or neither; z [S], the base sample
+    list, with t_rand [R, S] in [0, 1), both or neither.  check=True verifies 0 <= pix < H W and raises NrpnError; it synchronises, so
+    it is off by default and an index outside the image is clamped into it.
+
+    Returns a dict of device tensors: rays [R, 6] (o, d; nerf_render's rays of those pixels, bit for bit), viewdirs [R, 3], target_s
+    [R, 3]; with depth: target_d [R, 2], target_vd [R] (bool), depth_range [R, 3] (precompute_depth_sampling :159-162); with t_rand:
+    z1 [R, S] (perturb_z_vals :480-495 of z, bit-equal to it for the same t_rand)."""
+    who = "nerf_train_batch"
+    if not torch.cuda.is_available():
+        raise lib.NrpnError(f"{who} needs a gfx950 device (the product path has no CPU fallback)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise lib.NrpnError(f"{who}: image {H} x {W}")
+    pose = torch.as_tensor(c2w, dtype=torch.float32)
+    if pose.dim() != 2 or pose.shape[0] < 3 or pose.shape[1] != 4:
+        raise lib.NrpnError(f"{who} expects c2w [>=3, 4], got {tuple(pose.shape)}")
+    intr = torch.as_tensor(intrinsic, dtype=torch.float32)
+    if intr.numel() != 4:
+        raise lib.NrpnError(f"{who} expects intrinsic (fx, fy, cx, cy), got {tuple(intr.shape)}")
+    camera = torch.cat([intr.reshape(4).to(dev), pose[:3].reshape(12).to(dev)]).contiguous()
+    pix = torch.as_tensor(pix)
+    if pix.dim() != 1 or pix.shape[0] < 1 or pix.dtype.is_floating_point or pix.dtype == torch.bool:
+        raise lib.NrpnError(f"{who} expects pix [R] of integers, got {tuple(pix.shape)} {pix.dtype}")
+    pix = pix.to(device=dev, dtype=torch.int32).contiguous()
+    R = int(pix.shape[0])
+    if check and not bool(((pix >= 0) & (pix < H * W)).all()):
+        raise lib.NrpnError(f"{who}: pix outside [0, {H * W})")
+    image = _f32_device(who, "image", image, dev, (H, W, 3))
+    if (depth is None) != (valid is None):
+        raise lib.NrpnError(f"{who}: depth and valid go together")
+    if (z is None) != (t_rand is None):
+        raise lib.NrpnError(f"{who}: z and t_rand go together")
+    S = 0
+    if z is not None:
+        z = torch.as_tensor(z, dtype=torch.float32)
+        if z.dim() != 1 or z.shape[0] < 1:
+            raise lib.NrpnError(f"{who} expects z [S], got {tuple(z.shape)}")
+        S = int(z.shape[0])
+        z = _f32_device(who, "z", z, dev, (S,))
+        t_rand = _f32_device(who, "t_rand", t_rand, dev, (R, S))
+
+    def new(*shape, dtype=torch.float32):
+        return torch.empty(shape, dtype=dtype, device=dev)
+    out = {"rays": new(R, 6), "viewdirs": new(R, 3), "target_s": new(R, 3)}
+    vd = None
+    if depth is not None:
+        depth = _f32_device(who, "depth", depth, dev, (H, W, 2))
+        valid = torch.as_tensor(valid).to(dev)
+        if tuple(valid.shape) != (H, W):
+            raise lib.NrpnError(f"{who} expects valid [{H}, {W}], got {list(valid.shape)}")
+        valid = (valid != 0).to(torch.uint8).contiguous()
+        out["target_d"], out["depth_range"], vd = new(R, 2), new(R, 3), new(R, dtype=torch.uint8)
+    if S:
+        out["z1"] = new(R, S)
+
+    def opt(t):
+        return None if t is None else _p(t)
+    call("nerftrain_batch", _p(camera), H, W, _p(pix), R, _p(image), opt(depth), opt(valid), opt(z), opt(t_rand), S, _p(out["rays"]),
+         _p(out["viewdirs"]), _p(out["target_s"]), opt(out.get("target_d")), opt(vd), opt(out.get("depth_range")), opt(out.get("z1")),
+         _s())
+    if vd is not None:
+        out["target_vd"] = vd.view(torch.bool)
+    return out
+
+
+def nerf_train_samples(raw1, z1, rays, near, far, lower_bound, depth_range=None, u=None):
+    """The second sample list of render_rays at train time (run_nerf.py:588-592) in one launch, with no host decision (DESIGN.md
+    3.22).
+
+    raw1 [R, S, 4] (detached: nothing here is differentiated) on the first list z1 [S] (every ray's) or [R, S]; rays [R, 6].  A ray
+    with depth_range[r, 0] >= near (depth_range [R, 3] of nerf_train_batch, or None) is sampled within depth_range[r, 1:]
+    (sample_3sigma :471-478); every other ray around the depth its first list predicts, with the std clamped below at lower_bound
+    (compute_samples_around_depth :497-502).  u [R, S]: the uniforms of sample_pdf, in any order; None selects the deterministic
+    u = linspace(0, 1, S) and then, with depth_range None and a shared z1, the result is nerf_render_samples', bit for bit.
+
+    Returns z2 [R, S] float32 in u's order -- not sorted: the inverse cdf is monotone in exact arithmetic only."""
+    who = "nerf_train_samples"
+    if not torch.cuda.is_available():
+        raise lib.NrpnError(f"{who} needs a gfx950 device (the product path has no CPU fallback)")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if not isinstance(raw1, torch.Tensor) or raw1.dim() != 3 or raw1.shape[2] != 4 or raw1.shape[0] < 1:
+        raise lib.NrpnError(f"{who} expects raw1 [R, S, 4], got {tuple(getattr(raw1, 'shape', ()))}")
+    if raw1.requires_grad:
+        raise NotImplementedError(f"{who}: raw1 requires grad; the reference samples on raw.detach() (:590)")
+    R, S = int(raw1.shape[0]), int(raw1.shape[1])
+    nbytes = lib.query("nerftrain_work_bytes", R, S)
+    if nbytes < 0:
+        raise lib.NrpnError(f"{who}: {R} rays with {S} samples are outside the supported range (S >= 2)")
+    raw1 = _f32_device(who, "raw1", raw1, dev, (R, S, 4))
+    z1 = torch.as_tensor(z1, dtype=torch.float32)
+    z1 = _f32_device(who, "z1", z1, dev, (S,) if z1.dim() == 1 else (R, S))
+    rays = _f32_device(who, "rays", rays, dev, (R, 6))
+    if depth_range is not None:
+        depth_range = _f32_device(who, "depth_range", depth_range, dev, (R, 3))
+    if u is not None:
+        u = _f32_device(who, "u", u, dev, (R, S))
+    near, far, lower_bound = float(near), float(far), float(lower_bound)
+    if not near <= far:
+        raise lib.NrpnError(f"{who}: near {near} above far {far}")
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    z2 = torch.empty((R, S), dtype=torch.float32, device=dev)
+    call("nerftrain_samples", _p(raw1), _p(z1), 0 if z1.dim() == 1 else S, _p(rays), None if depth_range is None else _p(depth_range),
+         None if u is None else _p(u), S, lower_bound, near, far, R, _p(work), nbytes, _p(z2), _s())
+    return z2
