@@ -712,7 +712,8 @@ int nrpn_scanbox_hull(int num_instances, int64_t num_members, int max_survivors,
  * view directions.  The trunk (encoding, pts_linears, feature_linear, alpha_linear and the feature columns W_f of views_linears.0)
  * runs once per point on the exact-fp32 MFMA; the poses loop over the head only.
  * nrpn_nerfgrid_work_bytes(what, num_points): what = 0 -> bytes of the packed weights; what = 1 -> bytes of the scratch a chunk of
- *   num_points points needs (128 floats per point, whole tiles of 64 points); -1 for anything else.
+ *   num_points points needs (128 floats per point, whole tiles of 64 points); what = 2 -> bytes of the bf16x3 planes (below); -1 for
+ *   anything else.
  * nrpn_nerfgrid_pack (the model create_nerf builds, run_nerf.py:344-358): raw f32, tensors in torch's [out][in] layout back to back:
  *   pts_linears.0 .. 7 weights ([256][input_ch], [256][256] x 4, [256][input_ch + 256], [256][256] x 2), feature_linear.weight
  *   [256][256], views_linears.0.weight[:, :256] as [128][256], then pts_linears.0 .. 7 biases, feature_linear.bias, alpha_linear.weight
@@ -730,6 +731,23 @@ int nrpn_nerfgrid_pack(const float *raw, int input_ch, float *packed, nrpn_strea
 int nrpn_nerfgrid_query(const float *xs, const float *ys, const float *zs, int res_x, int res_y, int res_z, float center_x,
                         float center_y, float center_z, float bb_scale, int multires, const float *packed, const float *ctab,
                         int num_poses, int layout, int64_t chunk, void *work, int64_t work_bytes, float *out, nrpn_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The bf16x3 arithmetic of the trunk, opt-in twins of the fp32 entries.  The ten matrix products of the trunk
+ * (pts_linears.0 .. 7, feature_linear, g = W_f f) carry each operand as hi = bf16(x), lo = bf16(x - hi) and add hi*hi + hi*lo + lo*hi
+ * on v_mfma_f32_32x32x16_bf16 in fp32 accumulators; encoding, biases, relu, alpha_linear, the heads and every backward product stay
+ * exact fp32.  Tensors stay float32.  A twin takes its fp32 entry's arguments plus ``split`` after ``packed``.
+ * nrpn_nerfgrid_work_bytes(2, 0): bytes of the planes.
+ * nrpn_nerfgrid_pack_bf16x3 (the model of create_nerf, run_nerf.py:344-358, as nrpn_nerfgrid_pack reads it): raw as for
+ *   nrpn_nerfgrid_pack -> planes: the hi plane of the ten matrices in the fragment order of the bf16 MFMA, then the lo plane; the zero
+ *   padding of the encoding columns is zero in both.  packed of nrpn_nerfgrid_pack is still needed by every twin.
+ * nrpn_nerfgrid_query_bf16x3 (extract_nerf, run_nerf.py:1166-1192; run_network :53-55): nrpn_nerfgrid_query in the arithmetic.
+ * ---------------------------------------------------------------------------------------------- */
+int nrpn_nerfgrid_pack_bf16x3(const float *raw, int input_ch, void *planes, nrpn_stream_t stream);
+int nrpn_nerfgrid_query_bf16x3(const float *xs, const float *ys, const float *zs, int res_x, int res_y, int res_z, float center_x,
+                               float center_y, float center_z, float bb_scale, int multires, const float *packed, const void *split,
+                               const float *ctab, int num_poses, int layout, int64_t chunk, void *work, int64_t work_bytes, float *out,
+                               nrpn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Views of a trained NeRF MLP, scripts/nerf_render.py.  [f6]  Replaces render / batchify_rays / render_rays of
@@ -769,6 +787,21 @@ int nrpn_nerfrender_frame(int height, int width, const float *camera, float near
                           const float *z2_in, int s2, int64_t chunk, void *work, int64_t work_bytes, float *rgb, float *depth, float *acc,
                           float *disp, float *depth_std, float *z_vals, float *weights, float *raw1_out, float *z2_out,
                           nrpn_stream_t stream);
+/* nrpn_nerfrender_rays_bf16x3 / nrpn_nerfrender_frame_bf16x3 (render :82-157, render_rays :514-614, as their fp32 twins): the trunk of
+ *   both passes in the bf16x3 arithmetic on split, the planes of nrpn_nerfgrid_pack_bf16x3; the head, the samples and the composite are
+ *   the fp32 entries'. */
+int nrpn_nerfrender_rays_bf16x3(const float *rays, int64_t num_rays, float near, float far, float center_x, float center_y,
+                                float center_z, float bb_scale, int multires, int multires_views, int input_ch_cam, const float *packed,
+                                const void *split, const float *w_view, const float *b_view, const float *embedded_cam, const float *z1,
+                                int s1, int z2_mode, const float *z2_in, int s2, int64_t chunk, void *work, int64_t work_bytes,
+                                float *rgb, float *depth, float *acc, float *disp, float *depth_std, float *z_vals, float *weights,
+                                float *raw1_out, float *z2_out, nrpn_stream_t stream);
+int nrpn_nerfrender_frame_bf16x3(int height, int width, const float *camera, float near, float far, float center_x, float center_y,
+                                 float center_z, float bb_scale, int multires, int multires_views, int input_ch_cam, const float *packed,
+                                 const void *split, const float *w_view, const float *b_view, const float *embedded_cam, const float *z1,
+                                 int s1, int z2_mode, const float *z2_in, int s2, int64_t chunk, void *work, int64_t work_bytes,
+                                 float *rgb, float *depth, float *acc, float *disp, float *depth_std, float *z_vals, float *weights,
+                                 float *raw1_out, float *z2_out, nrpn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Metrics of a rendered view against its ground truth, scripts/nerf_test.py.  [f7]  Replaces what render_images_with_metrics
@@ -863,6 +896,19 @@ int nrpn_nerfquery_backward(const float *pts, const float *viewdirs, int64_t num
                             float center_z, float bb_scale, int multires, int multires_views, int input_ch_cam, const float *packed,
                             const float *packed_t, const float *w_view, const float *b_view, const float *embedded_cam,
                             const float *draw, int64_t chunk, void *work, int64_t work_bytes, float *grads, nrpn_stream_t stream);
+/* nrpn_nerfquery_forward_bf16x3 (run_network :50-65) / nrpn_nerfquery_backward_bf16x3 (loss.backward() :848 below raw): their fp32
+ *   twins with the trunk in the bf16x3 arithmetic on split.  The backward re-runs that same forward, so the activations it keeps are
+ *   the forward's; dgrad, wgrad and the reductions then run in exact fp32 on them.  Sizes: nrpn_nerfquery_work_bytes, unchanged. */
+int nrpn_nerfquery_forward_bf16x3(const float *pts, const float *viewdirs, int64_t num_rays, int num_samples, float center_x,
+                                  float center_y, float center_z, float bb_scale, int multires, int multires_views, int input_ch_cam,
+                                  const float *packed, const void *split, const float *w_view, const float *b_view,
+                                  const float *embedded_cam, int64_t chunk, void *work, int64_t work_bytes, float *raw,
+                                  nrpn_stream_t stream);
+int nrpn_nerfquery_backward_bf16x3(const float *pts, const float *viewdirs, int64_t num_rays, int num_samples, float center_x,
+                                   float center_y, float center_z, float bb_scale, int multires, int multires_views, int input_ch_cam,
+                                   const float *packed, const void *split, const float *packed_t, const float *w_view,
+                                   const float *b_view, const float *embedded_cam, const float *draw, int64_t chunk, void *work,
+                                   int64_t work_bytes, float *grads, nrpn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The ray stage of NeRF training as differentiable operations, ops.nerf_composite and ops.nerf_ray_losses.  [f10]  Replaces

@@ -1,7 +1,8 @@
 // The 8 x 256 trunk of the NeRF MLP of DESIGN.md 3.16 on the exact-fp32 MFMA, shared by nerfgrid.hip (lattice points) and
 // nerfrender.hip (ray samples): packed-weight layout (nrpn_nerfgrid_pack), fragment loads, the k-ordered MFMA product and the body
 // of one workgroup.  A caller supplies where a tile's 64 points come from and where their sigma goes; g goes to a [column][point]
-// tile.  The arithmetic of a point does not depend on the caller, its tile or its neighbours.
+// tile.  The arithmetic of a point does not depend on the caller, its tile or its neighbours.  trunk_body<true> is the same body with
+// the matrix products in the bf16x3 arithmetic; the default, trunk_body<false>, is the exact-fp32 code unchanged.
 #pragma once
 #include "common.h"
 
@@ -33,7 +34,13 @@ constexpr int64_t kOffRgbW = kOffAlphaB + 4;                       // 3 x 128
 constexpr int64_t kOffRgbB = kOffRgbW + 3 * kHalf;                 // 3 (+1 pad)
 constexpr int64_t kPackedFloats = kOffRgbB + 4;
 
+// split planes of the bf16x3 arithmetic, in bf16 elements (include/nerfrpn.h: nrpn_nerfgrid_pack_bf16x3): the hi plane holds the ten
+// matrices at the offsets off_layer gives, the lo plane follows it.  Every offset is a multiple of 8: a fragment is one uint4.
+constexpr int64_t kSplitPlane = kOffBias;
+constexpr int64_t kSplitElems = 2 * kSplitPlane;
+
 using f32x16 = __attribute__((ext_vector_type(16))) float;
+using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 
 // acc[m][c] += act[32 m .. 32 m + 31][k0 .. k0 + K) * W[:, col0 + 32 c .. + 31]; one wave, NC column blocks.  K / 8 is even.  Two
 // register sets alternate, so the loads of k-group n + 1 are in flight during the 8 * NC MFMAs of group n without register copies.
@@ -87,6 +94,79 @@ __device__ __forceinline__ void gemm_tile(const float *act, int k0, int K, const
   }
 }
 
+// ---- bf16x3: x = hi + lo + O(2^-16 x) with hi = bf16(x), lo = bf16(x - hi), both rounded to nearest even; a product is
+// hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_bf16 into the same fp32 accumulators.  Lane l holds A[row l & 31][k = 8 (l >> 5) + j]
+// and B[k = 8 (l >> 5) + j][col l & 31], j = 0 .. 7; the accumulator layout is the fp32 instruction's.  The LDS image stays fp32: a lane
+// reads its eight floats of a row (two 16-byte reads) and splits them in registers; the weights come pre-split, one uint4 per plane.
+template <int NC>
+struct FragSplit {
+  float4 a[2][2];
+  uint4 bh[NC], bl[NC];
+};
+
+template <int NC>
+__device__ __forceinline__ void frag_load_split(FragSplit<NC> &f, const float *a_ptr, const uint4 *__restrict__ bh, const uint4 *__restrict__ bl,
+                                                int ks, int n_out) {
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {
+    f.a[m][0] = *reinterpret_cast<const float4 *>(a_ptr + 32 * m * kLd + ks * 16);
+    f.a[m][1] = *reinterpret_cast<const float4 *>(a_ptr + 32 * m * kLd + ks * 16 + 4);
+  }
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    f.bh[c] = bh[(int64_t)ks * n_out * 2 + c * 64];
+    f.bl[c] = bl[(int64_t)ks * n_out * 2 + c * 64];
+  }
+}
+
+__device__ __forceinline__ void split8(const float4 &x0, const float4 &x1, bf16x8 &hi, bf16x8 &lo) {
+  const float x[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const __bf16 hb = (__bf16)x[j];
+    hi[j] = hb;
+    lo[j] = (__bf16)(x[j] - (float)hb);      // the difference is exact in fp32
+  }
+}
+
+template <int NC>
+__device__ __forceinline__ void frag_mma_split(const FragSplit<NC> &f, f32x16 (&acc)[2][NC]) {
+  bf16x8 ah[2], al[2];
+#pragma unroll
+  for (int m = 0; m < 2; ++m) split8(f.a[m][0], f.a[m][1], ah[m], al[m]);
+  // product outermost: the 2 * NC accumulators are independent, so a product's MFMAs do not wait for one another
+#pragma unroll
+  for (int p = 0; p < 3; ++p)
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const bf16x8 b = __builtin_bit_cast(bf16x8, p == 1 ? f.bl[c] : f.bh[c]);
+#pragma unroll
+      for (int m = 0; m < 2; ++m) acc[m][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(p == 2 ? al[m] : ah[m], b, acc[m][c], 0, 0, 0);
+    }
+}
+
+// as gemm_tile, K a multiple of 16; hi / lo: the layer's planes, fragment (k-step ks, column o, half h) at (ks * n_out + o) * 2 + h
+template <int NC>
+__device__ __forceinline__ void gemm_tile_split(const float *act, int k0, int K, const uint4 *__restrict__ hi, const uint4 *__restrict__ lo,
+                                                int n_out, int col0, f32x16 (&acc)[2][NC]) {
+  const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+  const float *a_ptr = act + r * kLd + k0 + 8 * h;
+  const uint4 *bh = hi + ((int64_t)(col0 + r) * 2 + h), *bl = lo + ((int64_t)(col0 + r) * 2 + h);
+  const int steps = K >> 4;      // even: K is 64, 256 or 320
+  FragSplit<NC> f0, f1;
+  frag_load_split(f0, a_ptr, bh, bl, 0, n_out);
+  for (int ks = 0; ks < steps; ks += 2) {
+    frag_load_split(f1, a_ptr, bh, bl, ks + 1, n_out);
+    __builtin_amdgcn_sched_barrier(0);
+    frag_mma_split(f0, acc);
+    __builtin_amdgcn_sched_barrier(0);
+    frag_load_split(f0, a_ptr, bh, bl, ks + 2 < steps ? ks + 2 : ks, n_out);      // the last iteration reloads its own step: in bounds, unused
+    __builtin_amdgcn_sched_barrier(0);
+    frag_mma_split(f1, acc);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
 // A sink that declares ``static constexpr bool kKeeps = true`` also gets keep(layer, act) once the image holds a layer's output that
 // every wave may read: layer -1 the encoding in columns 0 .. 63, 0 .. 7 the post-relu h_i and 8 the feature f in columns 64 .. 319
 // (nerfquery.hip keeps them for the backward pass).  Every thread of the workgroup calls it; it may only read the image.
@@ -104,10 +184,11 @@ __device__ __forceinline__ int acc_row(int reg, int h) { return (reg & 3) + 8 * 
 
 // One workgroup of 256 threads, one tile of 64 points.  act: the kLdsBytes LDS image.  src.point(i, p) gives the normalised position
 // of tile point i (a partial tile repeats a valid point; nothing of it may be stored), sink.sigma(i, s) takes alpha_linear's output of
-// tile point i; g = W_f f goes to g_tile as [column][point], 128 x 64 floats, for every point of the tile.
-template <class Src, class Sink>
+// tile point i; g = W_f f goes to g_tile as [column][point], 128 x 64 floats, for every point of the tile.  kSplit: the ten matrix
+// products run in the bf16x3 arithmetic on the planes ``split``; everything else (encoding, bias, relu, alpha_linear) is the same fp32.
+template <bool kSplit = false, class Src, class Sink>
 __device__ __forceinline__ void trunk_body(float *act, const float *__restrict__ packed, int multires, int input_ch, const Src &src,
-                                           const Sink &sink, float *__restrict__ g_tile) {
+                                           const Sink &sink, float *__restrict__ g_tile, const uint4 *__restrict__ split = nullptr) {
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
 
   // encoding: thread = (point i, quarter q of the 3 L (frequency, axis) pairs)
@@ -146,7 +227,10 @@ __device__ __forceinline__ void trunk_body(float *act, const float *__restrict__
         for (int e = 0; e < 16; ++e) acc[m][c][e] = 0.f;
     const int k0 = (layer == 0 || layer == kSkipLayer) ? 0 : kEnc;
     const int K = layer == 0 ? kEnc : layer == kSkipLayer ? kEnc + kW : kW;
-    gemm_tile<2>(act, k0, K, wp + off_layer(layer) / 4, kW, col0, acc);
+    if constexpr (kSplit)
+      gemm_tile_split<2>(act, k0, K, split + off_layer(layer) / 8, split + (kSplitPlane + off_layer(layer)) / 8, kW, col0, acc);
+    else
+      gemm_tile<2>(act, k0, K, wp + off_layer(layer) / 4, kW, col0, acc);
     if (layer == kLayers && t < kTile) {
       // sigma = alpha_linear(h): h is still in the image; one thread per point, k in order
       const float4 *hrow = reinterpret_cast<const float4 *>(act + t * kLd + kEnc);
@@ -188,7 +272,10 @@ __device__ __forceinline__ void trunk_body(float *act, const float *__restrict__
     for (int m = 0; m < 2; ++m)
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[m][0][e] = 0.f;
-    gemm_tile<1>(act, kEnc, kW, wp + off_layer(9) / 4, kHalf, wave * 32, acc);
+    if constexpr (kSplit)
+      gemm_tile_split<1>(act, kEnc, kW, split + off_layer(9) / 8, split + (kSplitPlane + off_layer(9)) / 8, kHalf, wave * 32, acc);
+    else
+      gemm_tile<1>(act, kEnc, kW, wp + off_layer(9) / 4, kHalf, wave * 32, acc);
     float *gt = g_tile + (wave * 32 + r) * kTile;
 #pragma unroll
     for (int m = 0; m < 2; ++m)

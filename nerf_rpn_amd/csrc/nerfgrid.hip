@@ -49,6 +49,29 @@ __global__ void nerfgrid_pack_kernel(const float *__restrict__ raw, float *__res
   }
 }
 
+// The bf16x3 planes of the same ten matrices (segments with n_out > 0): k-step ks = 16 consecutive k of the k axis above; lane half h
+// takes k = 16 ks + 8 h + j in element j, so the eight bf16 of (ks, output column o, h) sit at ((ks * n_out + o) * 2 + h) * 8 of the hi
+// plane, and their residuals at the same place of the lo plane.  Padding is zero in both planes.
+__global__ void nerfgrid_pack_split_kernel(const float *__restrict__ raw, unsigned short *__restrict__ planes, PackPlan plan) {
+  const PackSeg s = plan.seg[blockIdx.y];
+  const int64_t total = (int64_t)(s.ka_pad + s.kb) * s.n_out;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int j = (int)(i & 7), h = (int)((i >> 3) & 1);
+    const int64_t q = i >> 4;
+    const int o = (int)(q % s.n_out), ks = (int)(q / s.n_out);
+    const int k = 16 * ks + 8 * h + j;
+    float v = 0.f;
+    if (k < s.ka_pad) {
+      if (k < s.ka) v = raw[s.src + (int64_t)o * s.ld + k];
+    } else {
+      v = raw[s.src + (int64_t)o * s.ld + s.ka + (k - s.ka_pad)];
+    }
+    const __bf16 hb = (__bf16)v;
+    planes[s.dst + i] = __builtin_bit_cast(unsigned short, hb);
+    planes[kSplitPlane + s.dst + i] = f32_to_bf16_bits(v - (float)hb);
+  }
+}
+
 // ---- trunk (body: nerf_mlp.cuh) --------------------------------------------------------------------------------------------------
 struct GridArgs {
   const float *xs, *ys, *zs;      // linspace values [rx], [ry], [rz]
@@ -100,6 +123,15 @@ __global__ __launch_bounds__(256) void nerfgrid_trunk_kernel(GridArgs ga, const 
              gbuf + (int64_t)blockIdx.x * (kTile * kHalf));
 }
 
+__global__ __launch_bounds__(256) void nerfgrid_trunk_bf16x3_kernel(GridArgs ga, const float *__restrict__ packed,
+                                                                    const uint4 *__restrict__ split, int64_t point0,
+                                                                    float *__restrict__ gbuf, float *__restrict__ out) {
+  extern __shared__ __align__(16) float act[];
+  const int64_t tile0 = point0 + (int64_t)blockIdx.x * kTile;
+  trunk_body<true>(act, packed, ga.multires, ga.input_ch, GridSrc{ga, tile0}, GridSink{ga, tile0, out},
+                   gbuf + (int64_t)blockIdx.x * (kTile * kHalf), split);
+}
+
 // ---- head ------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kTile) void nerfgrid_head_kernel(GridArgs ga, const float *__restrict__ packed, int64_t point0,
                                                               const float *__restrict__ gbuf, const float *__restrict__ ctab,
@@ -140,23 +172,12 @@ __global__ __launch_bounds__(kTile) void nerfgrid_head_kernel(GridArgs ga, const
   }
 }
 
-}  // namespace
-
-extern "C" {
-
-int64_t nrpn_nerfgrid_work_bytes(int what, int64_t num_points) {
-  if (what == 0) return kPackedFloats * 4;
-  if (what == 1 && num_points > 0) return cdiv64(num_points, kTile) * kTile * kHalf * 4;
-  return -1;
-}
-
-int nrpn_nerfgrid_pack(const float *raw, int input_ch, float *packed, nrpn_stream_t stream) {
-  NRPN_REQUIRE(raw && packed, "nerfgrid_pack: null pointer");
-  NRPN_REQUIRE(input_ch >= 3 && input_ch <= kEnc, "nerfgrid_pack: input_ch %d outside 3 .. %d", input_ch, kEnc);
-  PackPlan plan{};
+// the ten matrices of raw in the packed order: pts_linears 0 .. 7, feature_linear, W_f -> their segments; *src_end: where the small
+// tensors start
+int matrix_plan(int input_ch, PackPlan &plan, int64_t *src_end) {
   int n = 0;
   int64_t src = 0;
-  for (int i = 0; i <= 9; ++i) {      // the raw order is the packed order: pts_linears 0 .. 7, feature_linear, W_f
+  for (int i = 0; i <= 9; ++i) {
     PackSeg s{};
     s.dst = off_layer(i);
     s.src = src;
@@ -172,6 +193,67 @@ int nrpn_nerfgrid_pack(const float *raw, int input_ch, float *packed, nrpn_strea
     src += (int64_t)s.n_out * s.ld;
     plan.seg[n++] = s;
   }
+  *src_end = src;
+  return n;
+}
+
+// kSplit: the trunk in the bf16x3 arithmetic on the planes ``split``; the head is the same kernel either way
+template <bool kSplit>
+int grid_query(const float *xs, const float *ys, const float *zs, int res_x, int res_y, int res_z, float center_x, float center_y,
+               float center_z, float bb_scale, int multires, const float *packed, const void *split, const float *ctab, int num_poses,
+               int layout, int64_t chunk, void *work, int64_t work_bytes, float *out, nrpn_stream_t stream) {
+  NRPN_REQUIRE(xs && ys && zs && packed && ctab && work && out && (!kSplit || split), "nerfgrid_query: null pointer");
+  NRPN_REQUIRE(res_x >= 1 && res_y >= 1 && res_z >= 1, "nerfgrid_query: resolution %d x %d x %d", res_x, res_y, res_z);
+  NRPN_REQUIRE(multires >= 0 && 3 + 6 * multires <= kEnc, "nerfgrid_query: multires %d does not fit %d encoding columns", multires, kEnc);
+  NRPN_REQUIRE(num_poses >= 1, "nerfgrid_query: no poses");
+  NRPN_REQUIRE(layout == 0 || layout == 1, "nerfgrid_query: layout %d", layout);
+  const int64_t n = (int64_t)res_x * res_y * res_z;
+  NRPN_REQUIRE(n < ((int64_t)1 << 40), "nerfgrid_query: too many points");
+  NRPN_REQUIRE(chunk >= 1, "nerfgrid_query: chunk %lld", (long long)chunk);
+  const int64_t chunk_tiles = cdiv64(chunk < n ? chunk : n, kTile);
+  NRPN_REQUIRE(chunk_tiles <= 0x7fffffff, "nerfgrid_query: chunk too large");
+  NRPN_REQUIRE(work_bytes >= chunk_tiles * kTile * kHalf * 4, "nerfgrid_query: work buffer of %lld bytes is too small",
+               (long long)work_bytes);
+  if constexpr (kSplit) {
+    NRPN_LDS(nerfgrid_trunk_bf16x3_kernel, kLdsBytes);
+  } else {
+    NRPN_LDS(nerfgrid_trunk_kernel, kLdsBytes);
+  }
+  GridArgs ga{xs, ys, zs, res_x, res_y, res_z, center_x, center_y, center_z, bb_scale, multires, 3 + 6 * multires, n, layout};
+  float *gbuf = static_cast<float *>(work);
+  for (int64_t p0 = 0; p0 < n; p0 += chunk_tiles * kTile) {
+    const int64_t left = n - p0;
+    const int tiles = (int)(left < chunk_tiles * kTile ? cdiv64(left, kTile) : chunk_tiles);
+    if constexpr (kSplit) {
+      nerfgrid_trunk_bf16x3_kernel<<<tiles, 256, kLdsBytes, as_stream(stream)>>>(ga, packed, static_cast<const uint4 *>(split), p0, gbuf, out);
+      NRPN_LAUNCH_CHECK("nerfgrid_trunk_bf16x3_kernel");
+    } else {
+      nerfgrid_trunk_kernel<<<tiles, 256, kLdsBytes, as_stream(stream)>>>(ga, packed, p0, gbuf, out);
+      NRPN_LAUNCH_CHECK("nerfgrid_trunk_kernel");
+    }
+    nerfgrid_head_kernel<<<tiles, kTile, 0, as_stream(stream)>>>(ga, packed, p0, gbuf, ctab, num_poses, out);
+    NRPN_LAUNCH_CHECK("nerfgrid_head_kernel");
+  }
+  return NRPN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t nrpn_nerfgrid_work_bytes(int what, int64_t num_points) {
+  if (what == 0) return kPackedFloats * 4;
+  if (what == 2) return kSplitElems * 2;
+  if (what == 1 && num_points > 0) return cdiv64(num_points, kTile) * kTile * kHalf * 4;
+  return -1;
+}
+
+int nrpn_nerfgrid_pack(const float *raw, int input_ch, float *packed, nrpn_stream_t stream) {
+  NRPN_REQUIRE(raw && packed, "nerfgrid_pack: null pointer");
+  NRPN_REQUIRE(input_ch >= 3 && input_ch <= kEnc, "nerfgrid_pack: input_ch %d outside 3 .. %d", input_ch, kEnc);
+  PackPlan plan{};
+  int64_t src = 0;
+  int n = matrix_plan(input_ch, plan, &src);
   const int64_t small[5][2] = {{kOffBias, 9 * kW}, {kOffAlphaW, kW}, {kOffAlphaB, 1}, {kOffRgbW, 3 * kHalf}, {kOffRgbB, 3}};
   for (int i = 0; i < 5; ++i) {
     PackSeg s{};
@@ -187,33 +269,30 @@ int nrpn_nerfgrid_pack(const float *raw, int input_ch, float *packed, nrpn_strea
   return NRPN_OK;
 }
 
+int nrpn_nerfgrid_pack_bf16x3(const float *raw, int input_ch, void *planes, nrpn_stream_t stream) {
+  NRPN_REQUIRE(raw && planes, "nerfgrid_pack_bf16x3: null pointer");
+  NRPN_REQUIRE(input_ch >= 3 && input_ch <= kEnc, "nerfgrid_pack_bf16x3: input_ch %d outside 3 .. %d", input_ch, kEnc);
+  PackPlan plan{};
+  int64_t src = 0;
+  const int n = matrix_plan(input_ch, plan, &src);
+  nerfgrid_pack_split_kernel<<<dim3(64, n), 256, 0, as_stream(stream)>>>(raw, static_cast<unsigned short *>(planes), plan);
+  NRPN_LAUNCH_CHECK("nerfgrid_pack_split_kernel");
+  return NRPN_OK;
+}
+
 int nrpn_nerfgrid_query(const float *xs, const float *ys, const float *zs, int res_x, int res_y, int res_z, float center_x,
                         float center_y, float center_z, float bb_scale, int multires, const float *packed, const float *ctab,
                         int num_poses, int layout, int64_t chunk, void *work, int64_t work_bytes, float *out, nrpn_stream_t stream) {
-  NRPN_REQUIRE(xs && ys && zs && packed && ctab && work && out, "nerfgrid_query: null pointer");
-  NRPN_REQUIRE(res_x >= 1 && res_y >= 1 && res_z >= 1, "nerfgrid_query: resolution %d x %d x %d", res_x, res_y, res_z);
-  NRPN_REQUIRE(multires >= 0 && 3 + 6 * multires <= kEnc, "nerfgrid_query: multires %d does not fit %d encoding columns", multires, kEnc);
-  NRPN_REQUIRE(num_poses >= 1, "nerfgrid_query: no poses");
-  NRPN_REQUIRE(layout == 0 || layout == 1, "nerfgrid_query: layout %d", layout);
-  const int64_t n = (int64_t)res_x * res_y * res_z;
-  NRPN_REQUIRE(n < ((int64_t)1 << 40), "nerfgrid_query: too many points");
-  NRPN_REQUIRE(chunk >= 1, "nerfgrid_query: chunk %lld", (long long)chunk);
-  const int64_t chunk_tiles = cdiv64(chunk < n ? chunk : n, kTile);
-  NRPN_REQUIRE(chunk_tiles <= 0x7fffffff, "nerfgrid_query: chunk too large");
-  NRPN_REQUIRE(work_bytes >= chunk_tiles * kTile * kHalf * 4, "nerfgrid_query: work buffer of %lld bytes is too small",
-               (long long)work_bytes);
-  NRPN_LDS(nerfgrid_trunk_kernel, kLdsBytes);
-  GridArgs ga{xs, ys, zs, res_x, res_y, res_z, center_x, center_y, center_z, bb_scale, multires, 3 + 6 * multires, n, layout};
-  float *gbuf = static_cast<float *>(work);
-  for (int64_t p0 = 0; p0 < n; p0 += chunk_tiles * kTile) {
-    const int64_t left = n - p0;
-    const int tiles = (int)(left < chunk_tiles * kTile ? cdiv64(left, kTile) : chunk_tiles);
-    nerfgrid_trunk_kernel<<<tiles, 256, kLdsBytes, as_stream(stream)>>>(ga, packed, p0, gbuf, out);
-    NRPN_LAUNCH_CHECK("nerfgrid_trunk_kernel");
-    nerfgrid_head_kernel<<<tiles, kTile, 0, as_stream(stream)>>>(ga, packed, p0, gbuf, ctab, num_poses, out);
-    NRPN_LAUNCH_CHECK("nerfgrid_head_kernel");
-  }
-  return NRPN_OK;
+  return grid_query<false>(xs, ys, zs, res_x, res_y, res_z, center_x, center_y, center_z, bb_scale, multires, packed, nullptr, ctab,
+                           num_poses, layout, chunk, work, work_bytes, out, stream);
+}
+
+int nrpn_nerfgrid_query_bf16x3(const float *xs, const float *ys, const float *zs, int res_x, int res_y, int res_z, float center_x,
+                               float center_y, float center_z, float bb_scale, int multires, const float *packed, const void *split,
+                               const float *ctab, int num_poses, int layout, int64_t chunk, void *work, int64_t work_bytes, float *out,
+                               nrpn_stream_t stream) {
+  return grid_query<true>(xs, ys, zs, res_x, res_y, res_z, center_x, center_y, center_z, bb_scale, multires, packed, split, ctab,
+                          num_poses, layout, chunk, work, work_bytes, out, stream);
 }
 
 }  // extern "C"

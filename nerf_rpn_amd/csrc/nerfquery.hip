@@ -171,6 +171,25 @@ __global__ __launch_bounds__(256) void nerfquery_trunk_keep_kernel(Points pp, in
              gbuf + (int64_t)blockIdx.x * (kTile * kHalf));
 }
 
+// the same two in the bf16x3 arithmetic: the backward keeps what this forward computed
+__global__ __launch_bounds__(256) void nerfquery_trunk_bf16x3_kernel(Points pp, int multires, const float *__restrict__ packed,
+                                                                     const uint4 *__restrict__ split, int64_t point0,
+                                                                     float *__restrict__ gbuf, float *__restrict__ raw) {
+  extern __shared__ __align__(16) float act[];
+  const int64_t tile0 = point0 + (int64_t)blockIdx.x * kTile;
+  trunk_body<true>(act, packed, multires, 3 + 6 * multires, PointSrc{pp, tile0}, RawSink{tile0, pp.num_points, raw},
+                   gbuf + (int64_t)blockIdx.x * (kTile * kHalf), split);
+}
+
+__global__ __launch_bounds__(256) void nerfquery_trunk_keep_bf16x3_kernel(Points pp, int multires, const float *__restrict__ packed,
+                                                                          const uint4 *__restrict__ split, int64_t point0,
+                                                                          float *__restrict__ gbuf, Kept kept) {
+  extern __shared__ __align__(16) float act[];
+  const int64_t tile0 = point0 + (int64_t)blockIdx.x * kTile;
+  trunk_body<true>(act, packed, multires, 3 + 6 * multires, PointSrc{pp, tile0}, KeepSink{kept, (int64_t)blockIdx.x * kTile},
+                   gbuf + (int64_t)blockIdx.x * (kTile * kHalf), split);
+}
+
 // ---- head ------------------------------------------------------------------------------------------------------------------------
 // One workgroup of 64 threads, one tile; rgb_linear over v = relu(g + c_ray) as 128-term fmaf chains in j order
 __global__ __launch_bounds__(kTile) void nerfquery_head_kernel(Points pp, const float *__restrict__ packed, const float *__restrict__ ctab,
@@ -436,6 +455,7 @@ struct QueryCall {
   void *work;
   int64_t work_bytes;
   hipStream_t stream;
+  const uint4 *split;       // the bf16x3 planes of packed (kSplit launchers only)
   int64_t chunk_tiles() const { return cdiv64(chunk < pp.num_points ? chunk : pp.num_points, kTile); }
 };
 
@@ -496,10 +516,16 @@ int launch_rays(const QueryCall &c, const Layout &l, bool with_xv) {
   return NRPN_OK;
 }
 
+// kSplit (here and in backward): the trunk runs in the bf16x3 arithmetic on c.split; everything after it is the same
+template <bool kSplit>
 int forward(const QueryCall &c, float *raw) {
   if (int rc = check("nerfquery_forward", c, false)) return rc;
-  NRPN_REQUIRE(raw, "nerfquery_forward: null output");
-  NRPN_LDS(nerfquery_trunk_kernel, kLdsBytes);
+  NRPN_REQUIRE(raw && (!kSplit || c.split), "nerfquery_forward: null output or planes");
+  if constexpr (kSplit) {
+    NRPN_LDS(nerfquery_trunk_bf16x3_kernel, kLdsBytes);
+  } else {
+    NRPN_LDS(nerfquery_trunk_kernel, kLdsBytes);
+  }
   const Layout l = layout(c.m, c.num_rays, c.chunk_tiles());
   char *wk = static_cast<char *>(c.work);
   const float *ctab = reinterpret_cast<float *>(wk + l.ctab);
@@ -508,8 +534,13 @@ int forward(const QueryCall &c, float *raw) {
   for (int64_t p0 = 0; p0 < c.pp.num_points; p0 += l.rows) {
     const int64_t left = c.pp.num_points - p0;
     const int tiles = (int)cdiv64(left < l.rows ? left : l.rows, kTile);
-    nerfquery_trunk_kernel<<<tiles, 256, kLdsBytes, c.stream>>>(c.pp, c.m.multires, c.packed, p0, gbuf, raw);
-    NRPN_LAUNCH_CHECK("nerfquery_trunk_kernel");
+    if constexpr (kSplit) {
+      nerfquery_trunk_bf16x3_kernel<<<tiles, 256, kLdsBytes, c.stream>>>(c.pp, c.m.multires, c.packed, c.split, p0, gbuf, raw);
+      NRPN_LAUNCH_CHECK("nerfquery_trunk_bf16x3_kernel");
+    } else {
+      nerfquery_trunk_kernel<<<tiles, 256, kLdsBytes, c.stream>>>(c.pp, c.m.multires, c.packed, p0, gbuf, raw);
+      NRPN_LAUNCH_CHECK("nerfquery_trunk_kernel");
+    }
     nerfquery_head_kernel<<<tiles, kTile, 0, c.stream>>>(c.pp, c.packed, ctab, p0, gbuf, raw);
     NRPN_LAUNCH_CHECK("nerfquery_head_kernel");
   }
@@ -527,10 +558,15 @@ struct Wgrad {            // one product of the backward and where its rows and 
   int64_t bias_dst;       // of column sum row_lo, or -1
 };
 
+template <bool kSplit>
 int backward(const QueryCall &c, const float *packed_t, const float *draw, float *grads) {
   if (int rc = check("nerfquery_backward", c, true)) return rc;
-  NRPN_REQUIRE(packed_t && draw && grads, "nerfquery_backward: null pointer");
-  NRPN_LDS(nerfquery_trunk_keep_kernel, kLdsBytes);
+  NRPN_REQUIRE(packed_t && draw && grads && (!kSplit || c.split), "nerfquery_backward: null pointer");
+  if constexpr (kSplit) {
+    NRPN_LDS(nerfquery_trunk_keep_bf16x3_kernel, kLdsBytes);
+  } else {
+    NRPN_LDS(nerfquery_trunk_keep_kernel, kLdsBytes);
+  }
   NRPN_LDS(nerfquery_dgrad_kernel, kLdsBytes);
   const Model &m = c.m;
   const Layout l = layout(m, c.num_rays, c.chunk_tiles());
@@ -577,8 +613,13 @@ int backward(const QueryCall &c, const float *packed_t, const float *draw, float
     };
     auto hl = [&](int i) { return kept.h + (int64_t)i * l.rows * kW; };
 
-    nerfquery_trunk_keep_kernel<<<tiles, 256, kLdsBytes, c.stream>>>(c.pp, m.multires, c.packed, p0, gbuf, kept);
-    NRPN_LAUNCH_CHECK("nerfquery_trunk_keep_kernel");
+    if constexpr (kSplit) {
+      nerfquery_trunk_keep_bf16x3_kernel<<<tiles, 256, kLdsBytes, c.stream>>>(c.pp, m.multires, c.packed, c.split, p0, gbuf, kept);
+      NRPN_LAUNCH_CHECK("nerfquery_trunk_keep_bf16x3_kernel");
+    } else {
+      nerfquery_trunk_keep_kernel<<<tiles, 256, kLdsBytes, c.stream>>>(c.pp, m.multires, c.packed, p0, gbuf, kept);
+      NRPN_LAUNCH_CHECK("nerfquery_trunk_keep_kernel");
+    }
     nerfquery_headbwd_kernel<<<tiles, kTile, 0, c.stream>>>(c.pp, c.packed, ctab, xv, kv, p0, gbuf, draw, ho);
     NRPN_LAUNCH_CHECK("nerfquery_headbwd_kernel");
     // rgb_linear and alpha_linear: rows 0 .. 2 and row 3 of the head's cotangent
@@ -644,8 +685,19 @@ int nrpn_nerfquery_forward(const float *pts, const float *viewdirs, int64_t num_
                            int64_t work_bytes, float *raw, nrpn_stream_t stream) {
   QueryCall c{Points{pts, num_rays * num_samples, num_samples, center_x, center_y, center_z, bb_scale},
               Model{multires, multires_views, input_ch_cam}, viewdirs, packed, w_view, b_view, embedded_cam, num_rays, chunk, work,
-              work_bytes, as_stream(stream)};
-  return forward(c, raw);
+              work_bytes, as_stream(stream), nullptr};
+  return forward<false>(c, raw);
+}
+
+int nrpn_nerfquery_forward_bf16x3(const float *pts, const float *viewdirs, int64_t num_rays, int num_samples, float center_x,
+                                  float center_y, float center_z, float bb_scale, int multires, int multires_views, int input_ch_cam,
+                                  const float *packed, const void *split, const float *w_view, const float *b_view,
+                                  const float *embedded_cam, int64_t chunk, void *work, int64_t work_bytes, float *raw,
+                                  nrpn_stream_t stream) {
+  QueryCall c{Points{pts, num_rays * num_samples, num_samples, center_x, center_y, center_z, bb_scale},
+              Model{multires, multires_views, input_ch_cam}, viewdirs, packed, w_view, b_view, embedded_cam, num_rays, chunk, work,
+              work_bytes, as_stream(stream), static_cast<const uint4 *>(split)};
+  return forward<true>(c, raw);
 }
 
 int nrpn_nerfquery_backward(const float *pts, const float *viewdirs, int64_t num_rays, int num_samples, float center_x, float center_y,
@@ -654,8 +706,19 @@ int nrpn_nerfquery_backward(const float *pts, const float *viewdirs, int64_t num
                             const float *draw, int64_t chunk, void *work, int64_t work_bytes, float *grads, nrpn_stream_t stream) {
   QueryCall c{Points{pts, num_rays * num_samples, num_samples, center_x, center_y, center_z, bb_scale},
               Model{multires, multires_views, input_ch_cam}, viewdirs, packed, w_view, b_view, embedded_cam, num_rays, chunk, work,
-              work_bytes, as_stream(stream)};
-  return backward(c, packed_t, draw, grads);
+              work_bytes, as_stream(stream), nullptr};
+  return backward<false>(c, packed_t, draw, grads);
+}
+
+int nrpn_nerfquery_backward_bf16x3(const float *pts, const float *viewdirs, int64_t num_rays, int num_samples, float center_x,
+                                   float center_y, float center_z, float bb_scale, int multires, int multires_views, int input_ch_cam,
+                                   const float *packed, const void *split, const float *packed_t, const float *w_view,
+                                   const float *b_view, const float *embedded_cam, const float *draw, int64_t chunk, void *work,
+                                   int64_t work_bytes, float *grads, nrpn_stream_t stream) {
+  QueryCall c{Points{pts, num_rays * num_samples, num_samples, center_x, center_y, center_z, bb_scale},
+              Model{multires, multires_views, input_ch_cam}, viewdirs, packed, w_view, b_view, embedded_cam, num_rays, chunk, work,
+              work_bytes, as_stream(stream), static_cast<const uint4 *>(split)};
+  return backward<true>(c, packed_t, draw, grads);
 }
 
 }  // extern "C"

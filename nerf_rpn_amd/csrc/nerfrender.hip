@@ -74,6 +74,15 @@ __global__ __launch_bounds__(256) void nerfrender_trunk_kernel(RayPoints rp, int
              gbuf + (int64_t)blockIdx.x * (kTile * kHalf));
 }
 
+__global__ __launch_bounds__(256) void nerfrender_trunk_bf16x3_kernel(RayPoints rp, int multires, const float *__restrict__ packed,
+                                                                      const uint4 *__restrict__ split, float *__restrict__ gbuf,
+                                                                      float *__restrict__ raw) {
+  extern __shared__ __align__(16) float act[];
+  const int64_t tile0 = (int64_t)blockIdx.x * kTile;
+  trunk_body<true>(act, packed, multires, 3 + 6 * multires, RaySrc{rp, tile0}, RaySink{tile0, rp.num_points, raw},
+                   gbuf + (int64_t)blockIdx.x * (kTile * kHalf), split);
+}
+
 // ---- head ------------------------------------------------------------------------------------------------------------------------
 // rgb_linear over v = relu(g + c) for one point: g the point's 128 trunk outputs in registers, c[j] the view part of its ray.
 // 128-term fmaf chains in j order; W_rgb is wave-uniform and comes through the scalar cache.  kMask: bit j of m is g[j] + c[j] > 0,
@@ -251,6 +260,7 @@ struct RayCall {          // what a render and the camera-embedding objective sh
   void *work;
   int64_t work_bytes;
   hipStream_t stream;
+  const uint4 *split = nullptr;       // the bf16x3 planes of packed: the trunk then runs in that arithmetic (renders only)
   int64_t chunk_rays() const { return chunk < num_rays ? chunk : num_rays; }
   int64_t chunks() const { return cdiv64(num_rays, chunk_rays()); }
 };
@@ -266,6 +276,7 @@ int check_call(const char *who, const RayCall &c, int64_t max_rays) {
 int check_work(const char *who, const RayCall &c, int64_t need) {
   NRPN_REQUIRE(c.work_bytes >= need, "%s: work buffer of %lld bytes is too small", who, (long long)c.work_bytes);
   NRPN_LDS(nerfrender_trunk_kernel, kLdsBytes);
+  if (c.split) NRPN_LDS(nerfrender_trunk_bf16x3_kernel, kLdsBytes);
   return NRPN_OK;
 }
 
@@ -311,6 +322,12 @@ Chunk chunk_at(const RayCall &c, int64_t ci, const float *rays, bool rays_whole,
 }
 
 int launch_trunk(const RayCall &c, const RayPoints &rp, float *gbuf, float *raw) {
+  if (c.split) {
+    nerfrender_trunk_bf16x3_kernel<<<(int)cdiv64(rp.num_points, kTile), 256, kLdsBytes, c.stream>>>(rp, c.multires, c.packed, c.split, gbuf,
+                                                                                                  raw);
+    NRPN_LAUNCH_CHECK("nerfrender_trunk_bf16x3_kernel");
+    return NRPN_OK;
+  }
   nerfrender_trunk_kernel<<<(int)cdiv64(rp.num_points, kTile), 256, kLdsBytes, c.stream>>>(rp, c.multires, c.packed, gbuf, raw);
   NRPN_LAUNCH_CHECK("nerfrender_trunk_kernel");
   return NRPN_OK;
@@ -370,6 +387,36 @@ int render(const RenderCall &c) {
     NRPN_LAUNCH_CHECK("nerfrender_composite_kernel");
   }
   return NRPN_OK;
+}
+
+// the two entries of a render; kSplit: the planes are required and the trunk runs in the bf16x3 arithmetic
+template <bool kSplit>
+int render_rays(const float *rays, int64_t num_rays, float near, float far, float center_x, float center_y, float center_z, float bb_scale,
+                int multires, int multires_views, int input_ch_cam, const float *packed, const void *split, const float *w_view,
+                const float *b_view, const float *embedded_cam, const float *z1, int s1, int z2_mode, const float *z2_in, int s2,
+                int64_t chunk, void *work, int64_t work_bytes, const CompositeOut &out, float *raw1_out, float *z2_out,
+                nrpn_stream_t stream) {
+  NRPN_REQUIRE(rays, "nerfrender_rays: null rays");
+  NRPN_REQUIRE(!kSplit || split, "nerfrender_rays: null planes");
+  RenderCall c{{num_rays, center_x, center_y, center_z, bb_scale, multires, packed, z1, s1, s2, chunk, work, work_bytes, as_stream(stream),
+                kSplit ? static_cast<const uint4 *>(split) : nullptr},
+               rays, nullptr, 0, near, far, multires_views, input_ch_cam, w_view, b_view, embedded_cam, z2_mode, z2_in, out, raw1_out, z2_out};
+  return render(c);
+}
+
+template <bool kSplit>
+int render_frame(int height, int width, const float *camera, float near, float far, float center_x, float center_y, float center_z,
+                 float bb_scale, int multires, int multires_views, int input_ch_cam, const float *packed, const void *split,
+                 const float *w_view, const float *b_view, const float *embedded_cam, const float *z1, int s1, int z2_mode,
+                 const float *z2_in, int s2, int64_t chunk, void *work, int64_t work_bytes, const CompositeOut &out, float *raw1_out,
+                 float *z2_out, nrpn_stream_t stream) {
+  NRPN_REQUIRE(camera && height >= 1 && width >= 1, "nerfrender_frame: camera / %d x %d", height, width);
+  NRPN_REQUIRE(!kSplit || split, "nerfrender_frame: null planes");
+  RenderCall c{{(int64_t)height * width, center_x, center_y, center_z, bb_scale, multires, packed, z1, s1, s2, chunk, work, work_bytes,
+                as_stream(stream), kSplit ? static_cast<const uint4 *>(split) : nullptr},
+               nullptr, camera, width, near, far, multires_views, input_ch_cam, w_view, b_view, embedded_cam, z2_mode, z2_in, out, raw1_out,
+               z2_out};
+  return render(c);
 }
 
 // ---- camera-embedding objective (scripts/nerf_test.py --task test_opt; run_nerf.py optimize_camera_embedding :193-229) ---------
@@ -670,11 +717,20 @@ int nrpn_nerfrender_rays(const float *rays, int64_t num_rays, float near, float 
                          const float *b_view, const float *embedded_cam, const float *z1, int s1, int z2_mode, const float *z2_in, int s2,
                          int64_t chunk, void *work, int64_t work_bytes, float *rgb, float *depth, float *acc, float *disp,
                          float *depth_std, float *z_vals, float *weights, float *raw1_out, float *z2_out, nrpn_stream_t stream) {
-  NRPN_REQUIRE(rays, "nerfrender_rays: null rays");
-  RenderCall c{{num_rays, center_x, center_y, center_z, bb_scale, multires, packed, z1, s1, s2, chunk, work, work_bytes, as_stream(stream)},
-               rays, nullptr, 0, near, far, multires_views, input_ch_cam, w_view, b_view, embedded_cam, z2_mode, z2_in,
-               CompositeOut{rgb, depth, acc, disp, depth_std, z_vals, weights}, raw1_out, z2_out};
-  return render(c);
+  return render_rays<false>(rays, num_rays, near, far, center_x, center_y, center_z, bb_scale, multires, multires_views, input_ch_cam,
+                            packed, nullptr, w_view, b_view, embedded_cam, z1, s1, z2_mode, z2_in, s2, chunk, work, work_bytes,
+                            CompositeOut{rgb, depth, acc, disp, depth_std, z_vals, weights}, raw1_out, z2_out, stream);
+}
+
+int nrpn_nerfrender_rays_bf16x3(const float *rays, int64_t num_rays, float near, float far, float center_x, float center_y,
+                                float center_z, float bb_scale, int multires, int multires_views, int input_ch_cam, const float *packed,
+                                const void *split, const float *w_view, const float *b_view, const float *embedded_cam, const float *z1,
+                                int s1, int z2_mode, const float *z2_in, int s2, int64_t chunk, void *work, int64_t work_bytes,
+                                float *rgb, float *depth, float *acc, float *disp, float *depth_std, float *z_vals, float *weights,
+                                float *raw1_out, float *z2_out, nrpn_stream_t stream) {
+  return render_rays<true>(rays, num_rays, near, far, center_x, center_y, center_z, bb_scale, multires, multires_views, input_ch_cam,
+                           packed, split, w_view, b_view, embedded_cam, z1, s1, z2_mode, z2_in, s2, chunk, work, work_bytes,
+                           CompositeOut{rgb, depth, acc, disp, depth_std, z_vals, weights}, raw1_out, z2_out, stream);
 }
 
 int nrpn_nerfrender_frame(int height, int width, const float *camera, float near, float far, float center_x, float center_y,
@@ -683,12 +739,20 @@ int nrpn_nerfrender_frame(int height, int width, const float *camera, float near
                           const float *z2_in, int s2, int64_t chunk, void *work, int64_t work_bytes, float *rgb, float *depth, float *acc,
                           float *disp, float *depth_std, float *z_vals, float *weights, float *raw1_out, float *z2_out,
                           nrpn_stream_t stream) {
-  NRPN_REQUIRE(camera && height >= 1 && width >= 1, "nerfrender_frame: camera / %d x %d", height, width);
-  RenderCall c{{(int64_t)height * width, center_x, center_y, center_z, bb_scale, multires, packed, z1, s1, s2, chunk, work, work_bytes,
-                as_stream(stream)},
-               nullptr, camera, width, near, far, multires_views, input_ch_cam, w_view, b_view, embedded_cam, z2_mode, z2_in,
-               CompositeOut{rgb, depth, acc, disp, depth_std, z_vals, weights}, raw1_out, z2_out};
-  return render(c);
+  return render_frame<false>(height, width, camera, near, far, center_x, center_y, center_z, bb_scale, multires, multires_views,
+                             input_ch_cam, packed, nullptr, w_view, b_view, embedded_cam, z1, s1, z2_mode, z2_in, s2, chunk, work,
+                             work_bytes, CompositeOut{rgb, depth, acc, disp, depth_std, z_vals, weights}, raw1_out, z2_out, stream);
+}
+
+int nrpn_nerfrender_frame_bf16x3(int height, int width, const float *camera, float near, float far, float center_x, float center_y,
+                                 float center_z, float bb_scale, int multires, int multires_views, int input_ch_cam, const float *packed,
+                                 const void *split, const float *w_view, const float *b_view, const float *embedded_cam, const float *z1,
+                                 int s1, int z2_mode, const float *z2_in, int s2, int64_t chunk, void *work, int64_t work_bytes,
+                                 float *rgb, float *depth, float *acc, float *disp, float *depth_std, float *z_vals, float *weights,
+                                 float *raw1_out, float *z2_out, nrpn_stream_t stream) {
+  return render_frame<true>(height, width, camera, near, far, center_x, center_y, center_z, bb_scale, multires, multires_views,
+                            input_ch_cam, packed, split, w_view, b_view, embedded_cam, z1, s1, z2_mode, z2_in, s2, chunk, work,
+                            work_bytes, CompositeOut{rgb, depth, acc, disp, depth_std, z_vals, weights}, raw1_out, z2_out, stream);
 }
 
 int64_t nrpn_nerfcamopt_work_bytes(int what, int64_t num_rays, int64_t chunk_rays, int s1, int s2) {

@@ -8,10 +8,13 @@ from . import ops
 class NeRF(nn.Module):
     """The 24 parameters of the network under the names and shapes of a checkpoint's network_fn_state_dict (D = 8, W = 256, skips =
     [4], multires 9, view directions), initialised as torch initialises nn.Linear.  ``cfg`` is a training run's args.json (a dict or a
-    namespace) and goes through ops.nerf_grid_config, which raises NotImplementedError for an unsupported option."""
+    namespace) and goes through ops.nerf_grid_config, which raises NotImplementedError for an unsupported option.  ``dtype`` is the
+    arithmetic of the trunk's matrix products in query, forward and backward: "fp32" (exact, the default) or "bf16x3" (DESIGN.md 3.23);
+    the parameters and gradients are float32 either way."""
 
-    def __init__(self, cfg=None):
+    def __init__(self, cfg=None, dtype="fp32"):
         super().__init__()
+        self.set_compute_dtype(dtype)
         self.cfg = dict(cfg) if isinstance(cfg, dict) else ({} if cfg is None else cfg)
         c = ops.nerf_grid_config(self.cfg)
         W, input_ch, views_ch = 256, 3 + 6 * c["multires"], 3 + 6 * c["multires_views"]
@@ -22,9 +25,15 @@ class NeRF(nn.Module):
         self.alpha_linear = nn.Linear(W, 1)
         self.rgb_linear = nn.Linear(W // 2, 3)
 
+    def set_compute_dtype(self, dtype):
+        """"fp32" or "bf16x3"; anything else raises ValueError."""
+        self.compute_dtype = ops.nerf_check_dtype(dtype)
+        return self
+
     def query(self, pts, viewdirs, embedded_cam=None, bb_center=(0., 0., 0.), bb_scale=1., chunk=None):
         """network_query_fn(pts, viewdirs, embedded_cam, self): raw [R, S, 4], differentiable in the parameters and embedded_cam."""
-        return ops.nerf_query(dict(self.named_parameters()), self.cfg, pts, viewdirs, embedded_cam, bb_center, bb_scale, chunk)
+        return ops.nerf_query(dict(self.named_parameters()), self.cfg, pts, viewdirs, embedded_cam, bb_center, bb_scale, chunk,
+                              self.compute_dtype)
 
     def forward(self, pts, viewdirs, embedded_cam=None, bb_center=(0., 0., 0.), bb_scale=1., chunk=None):
         return self.query(pts, viewdirs, embedded_cam, bb_center, bb_scale, chunk)

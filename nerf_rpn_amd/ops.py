@@ -2440,6 +2440,14 @@ def scannet_instance_boxes(vertices, seg_of_vertex, instance_segments):
 # ======================================================================================================================
 NERF_GRID_DEFAULT_CHUNK = 1 << 20      # points per trunk / head launch pair: 512 MiB of scratch (128 floats per point)
 _NERF_LAYOUTS = {"flat": 0, "wlh": 1}
+NERF_DTYPES = ("fp32", "bf16x3")       # arithmetic of the trunk's matrix products; tensors are float32 either way
+
+
+def nerf_check_dtype(dtype):
+    """``dtype`` if it names an arithmetic of the NeRF trunk; ValueError otherwise."""
+    if dtype not in NERF_DTYPES:
+        raise ValueError(f"dtype {dtype!r}: expected 'fp32' or 'bf16x3'")
+    return dtype
 
 
 def nerf_grid_config(cfg):
@@ -2464,10 +2472,19 @@ def nerf_grid_config(cfg):
 class NerfGridWeights:
     """The device-side weights of one NeRF MLP for nerf_grid_query: the packed trunk and rgb_linear (nrpn_nerfgrid_pack), the view
     columns W_d and the bias of views_linears.0 for the c_p table, and the options they were built for."""
-    def __init__(self, packed, w_dirs, b_views, config, w_view=None, raw=None):
+    def __init__(self, packed, w_dirs, b_views, config, w_view=None, raw=None, dtype="fp32", split=None):
         self.packed, self.w_dirs, self.b_views, self.config = packed, w_dirs, b_views, config
         self.w_view = w_view        # the view and camera columns together, [128][views_ch + input_ch_cam]: nerf_render's head
         self.raw = raw              # what nrpn_nerfgrid_pack read: nerf_query's backward packs the transposes from it
+        self.dtype = dtype          # "fp32", or "bf16x3" with split: the hi and lo bf16 planes of the trunk's matrices
+        self.split = split
+
+    def entry(self, name, *before_split):
+        """(C entry, arguments up to and including the weights) of ``name`` in this object's arithmetic: the bf16x3 twins take the
+        planes right after ``packed``, which ends ``before_split``."""
+        if self.dtype == "fp32":
+            return name, before_split
+        return name + "_bf16x3", (*before_split, _p(self.split))
 
 
 def _nerf_raw(t):
@@ -2479,9 +2496,11 @@ def _nerf_raw(t):
                         t["rgb_linear.weight"].reshape(-1), t["rgb_linear.bias"]]).contiguous()
 
 
-def nerf_grid_pack(state_dict, cfg):
+def nerf_grid_pack(state_dict, cfg, dtype="fp32"):
     """Upload and pack a checkpoint's network_fn_state_dict once (keys with or without DataParallel's ``module.``) -> NerfGridWeights,
-    which nerf_grid_query accepts in place of the state dict."""
+    which nerf_grid_query accepts in place of the state dict.  dtype "bf16x3": the weights also hold the split planes of the trunk's
+    matrices, and every consumer of them runs the trunk in that arithmetic."""
+    nerf_check_dtype(dtype)
     c = nerf_grid_config(cfg)
     if not torch.cuda.is_available():
         raise lib.NrpnError("nerf_grid_query needs a gfx950 device (the product path has no CPU fallback)")
@@ -2503,12 +2522,25 @@ def nerf_grid_pack(state_dict, cfg):
     raw = _nerf_raw(t)
     packed = torch.empty(lib.query("nerfgrid_work_bytes", 0, 0) // 4, dtype=torch.float32, device=dev)
     call("nerfgrid_pack", _p(raw), input_ch, _p(packed), _s())
-    return NerfGridWeights(packed, wv[:, W:W + views_ch].contiguous(), t["views_linears.0.bias"], c, wv[:, W:].contiguous(), raw)
+    split = None
+    if dtype == "bf16x3":
+        split = torch.empty(lib.query("nerfgrid_work_bytes", 2, 0) // 2, dtype=torch.bfloat16, device=dev)
+        call("nerfgrid_pack_bf16x3", _p(raw), input_ch, _p(split), _s())
+    return NerfGridWeights(packed, wv[:, W:W + views_ch].contiguous(), t["views_linears.0.bias"], c, wv[:, W:].contiguous(), raw, dtype,
+                           split)
 
 
-def _nerf_weights(who, weights_or_state, cfg):
-    """The NerfGridWeights given, or those of a given network_fn_state_dict; either way they must fit cfg -> NerfGridWeights."""
-    weights = weights_or_state if isinstance(weights_or_state, NerfGridWeights) else nerf_grid_pack(weights_or_state, cfg)
+def _nerf_weights(who, weights_or_state, cfg, dtype=None):
+    """The NerfGridWeights given, or those of a given network_fn_state_dict (packed for ``dtype``, default fp32); either way they
+    must fit cfg, and given weights carry their own arithmetic: a ``dtype`` that contradicts it is an error -> NerfGridWeights."""
+    if dtype is not None:
+        nerf_check_dtype(dtype)
+    if isinstance(weights_or_state, NerfGridWeights):
+        weights = weights_or_state
+        if dtype is not None and dtype != weights.dtype:
+            raise ValueError(f"{who}: dtype {dtype!r} given with weights packed for {weights.dtype!r}")
+    else:
+        weights = nerf_grid_pack(weights_or_state, cfg, dtype or "fp32")
     if weights.config != nerf_grid_config(cfg):
         raise lib.NrpnError(f"{who}: the weights were packed for other options")
     return weights
@@ -2520,7 +2552,7 @@ def _nerf_bounds(bb_center, bb_scale):
     return (*center.reshape(3).tolist(), scale.reshape(()).item())
 
 
-def nerf_grid_query(state_dict, cfg, xs, ys, zs, bb_center, bb_scale, poses, layout="flat", chunk=None):
+def nerf_grid_query(state_dict, cfg, xs, ys, zs, bb_center, bb_scale, poses, layout="flat", chunk=None, dtype=None):
     """extract_nerf of the reference's run_nerf.py (:1157-1194) for the NeRF MLP of DESIGN.md 3.16.
 
     state_dict: the checkpoint's network_fn_state_dict (keys with or without DataParallel's ``module.``), or the NerfGridWeights
@@ -2530,10 +2562,10 @@ def nerf_grid_query(state_dict, cfg, xs, ys, zs, bb_center, bb_scale, poses, lay
     (iz * res_y + iy) * res_x + ix -- the reference's array -- or "wlh" (res_x, res_y, res_z, 4), the grid datasets.py reads.
     Channels: mean over the poses of sigmoid(rgb), summed in pose order, and the raw density.  The trunk of the MLP runs once per point
     on the exact-fp32 MFMA; the poses loop over views_linears.0 / rgb_linear only.  ``chunk`` (points, default 2^20) bounds the scratch
-    and never changes the result."""
+    and never changes the result.  The arithmetic of the trunk is the weights' (nerf_grid_pack's dtype); with a state dict, ``dtype`` selects it."""
     if layout not in _NERF_LAYOUTS:
         raise ValueError(f"layout {layout!r}: expected 'flat' or 'wlh'")
-    weights = _nerf_weights("nerf_grid_query", state_dict, cfg)
+    weights = _nerf_weights("nerf_grid_query", state_dict, cfg, dtype)
     c, packed, dev = weights.config, weights.packed, weights.packed.device
     # c_p = W_d embed_dirs(d_p) + b: the camera embedding is zero at extraction (run_nerf.py:1177), its columns drop out
     poses = torch.as_tensor(poses, dtype=torch.float32).to(dev)
@@ -2556,8 +2588,9 @@ def nerf_grid_query(state_dict, cfg, xs, ys, zs, bb_center, bb_scale, poses, lay
     nbytes = lib.query("nerfgrid_work_bytes", 1, min(chunk, n))
     work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     out = torch.empty((n, 4) if layout == "flat" else (rx, ry, rz, 4), dtype=torch.float32, device=dev)
-    call("nerfgrid_query", _p(axes[0]), _p(axes[1]), _p(axes[2]), rx, ry, rz, *_nerf_bounds(bb_center, bb_scale), c["multires"], _p(packed),
-         _p(ctab), int(ctab.shape[0]), _NERF_LAYOUTS[layout], chunk, _p(work), nbytes, _p(out), _s())
+    name, head = weights.entry("nerfgrid_query", _p(axes[0]), _p(axes[1]), _p(axes[2]), rx, ry, rz, *_nerf_bounds(bb_center, bb_scale),
+                               c["multires"], _p(packed))
+    call(name, *head, _p(ctab), int(ctab.shape[0]), _NERF_LAYOUTS[layout], chunk, _p(work), nbytes, _p(out), _s())
     return out
 
 
@@ -2568,9 +2601,9 @@ NERF_RENDER_DEFAULT_CHUNK = 4096       # rays per launch group: 256 MiB of g scr
 
 
 def _nerf_render_inputs(who, weights_or_state, cfg, H, W, intrinsic, c2w, rays, near, far, bb_center, bb_scale, z_samples, n_samples,
-                        lindisp, embedded_cam, z2, chunk):
+                        lindisp, embedded_cam, z2, chunk, dtype=None):
     """The arguments nerf_render and nerf_camopt_prepare share, checked and on the device -> namespace."""
-    weights = _nerf_weights(who, weights_or_state, cfg)
+    weights = _nerf_weights(who, weights_or_state, cfg, dtype)
     c, packed, dev = weights.config, weights.packed, weights.packed.device
 
     def f32(x, shape=None):
@@ -2633,7 +2666,7 @@ def _nerf_render_inputs(who, weights_or_state, cfg, H, W, intrinsic, c2w, rays, 
 
 def nerf_render(weights_or_state, cfg, H=None, W=None, intrinsic=None, c2w=None, rays=None, near=None, far=None, bb_center=(0., 0., 0.),
                 bb_scale=1., z_samples=None, n_samples=None, lindisp=False, embedded_cam=None, chunk=None, return_samples=False,
-                z2=None, return_stages=False):
+                z2=None, return_stages=False, dtype=None):
     """render (run_nerf.py:82-157) with render_rays (:514-614) at test time for the NeRF MLP of DESIGN.md 3.16, on the GPU.
 
     weights_or_state: the NerfGridWeights of nerf_grid_pack, or a network_fn_state_dict; cfg: the run's args.json.  The rays are those
@@ -2649,9 +2682,10 @@ def nerf_render(weights_or_state, cfg, H=None, W=None, intrinsic=None, c2w=None,
     Returns a dict of float32 device tensors keyed as render_rays returns them -- rgb_map [.., 3], depth_map, acc_map, disp_map [..]
     -- plus depth_std = sqrt(clamp(sum((z - depth)^2 w), 0, 1)) (render_video :184-185), with leading shape (H, W) or (R,);
     return_samples adds z_vals and weights [.., S].  z2 [R, S2]: run the second pass on these samples instead of drawing them;
-    return_stages adds raw1 [R, S1, 4] (the first pass's rgb before the sigmoid and sigma) and z2 (the drawn samples)."""
+    return_stages adds raw1 [R, S1, 4] (the first pass's rgb before the sigmoid and sigma) and z2 (the drawn samples).  The trunk of
+    both passes runs in the weights' arithmetic (nerf_grid_pack's dtype); with a state dict, ``dtype`` selects it."""
     a = _nerf_render_inputs("nerf_render", weights_or_state, cfg, H, W, intrinsic, c2w, rays, near, far, bb_center, bb_scale, z_samples,
-                            n_samples, lindisp, embedded_cam, z2, chunk)
+                            n_samples, lindisp, embedded_cam, z2, chunk, dtype)
     c, n, s1, s2 = a.c, a.n, a.s1, a.s2
     nbytes = lib.query("nerfrender_work_bytes", min(a.chunk, n), s1, s2)
     if nbytes < 0:
@@ -2670,14 +2704,15 @@ def nerf_render(weights_or_state, cfg, H=None, W=None, intrinsic=None, c2w=None,
 
     def opt(k):
         return _p(out[k]) if k in out else None
-    common = (a.near, a.far, *a.center, a.scale, c["multires"], c["multires_views"], a.cam_ch, _p(a.packed), _p(a.weights.w_view),
-              _p(a.weights.b_views), _p(a.cam) if a.cam_ch else None, _p(a.z1), s1, a.mode, _p(a.z2_t) if a.z2_t is not None else None,
+    to_packed = (a.near, a.far, *a.center, a.scale, c["multires"], c["multires_views"], a.cam_ch, _p(a.packed))
+    common = (_p(a.weights.w_view), _p(a.weights.b_views), _p(a.cam) if a.cam_ch else None, _p(a.z1), s1, a.mode, _p(a.z2_t) if a.z2_t is not None else None,
               s2, a.chunk, _p(work), nbytes, _p(out["rgb_map"]), _p(out["depth_map"]), _p(out["acc_map"]), _p(out["disp_map"]),
               _p(out["depth_std"]), opt("z_vals"), opt("weights"), opt("raw1"), opt("z2"), _s())
     if a.rays_t is not None:
-        call("nerfrender_rays", _p(a.rays_t), n, *common)
+        name, head = a.weights.entry("nerfrender_rays", _p(a.rays_t), n, *to_packed)
     else:
-        call("nerfrender_frame", a.lead[0], a.lead[1], _p(a.camera), *common)
+        name, head = a.weights.entry("nerfrender_frame", a.lead[0], a.lead[1], _p(a.camera), *to_packed)
+    call(name, *head, *common)
     return {k: (v if k in ("raw1", "z2") else v.reshape(*a.lead, *v.shape[1:])) for k, v in out.items()}
 
 
@@ -2721,6 +2756,9 @@ def nerf_camopt_prepare(weights_or_state, cfg, target, H=None, W=None, intrinsic
     every evaluation, to the same bits.  ``chunk`` fixes the chunks (default 4096 rays).  -> NerfCamoptState"""
     a = _nerf_render_inputs("nerf_camopt_prepare", weights_or_state, cfg, H, W, intrinsic, c2w, rays, near, far, bb_center, bb_scale,
                             z_samples, n_samples, lindisp, None, z2, chunk)
+    if a.weights.dtype != "fp32":
+        raise NotImplementedError(f"nerf_camopt_prepare: the weights were packed for {a.weights.dtype!r}; the camera-embedding objective "
+                                  "runs in fp32 only")
     if a.cam_ch < 1:
         raise lib.NrpnError("nerf_camopt_prepare: the model has no camera embedding (input_ch_cam is 0)")
     dev, n, s1, s2, chunk = a.dev, a.n, a.s1, a.s2, a.chunk
@@ -2866,13 +2904,14 @@ NERF_QUERY_PARAMS = tuple([f"pts_linears.{i}.weight" for i in range(8)]
 
 class NerfQueryFn(torch.autograd.Function):
     """run_network (run_nerf.py:50-65) and its backward on the GPU (csrc/nerfquery.hip).  forward(pts [R, S, 3], viewdirs [R, 3], cam
-    [input_ch_cam], cfg, bounds, chunk, *params): params are the 24 tensors in NERF_QUERY_PARAMS order -> raw [R, S, 4].  Nothing but
-    the inputs is kept for the backward: it runs the forward again, chunk by chunk, into the scratch."""
+    [input_ch_cam], cfg, bounds, chunk, dtype, *params): params are the 24 tensors in NERF_QUERY_PARAMS order -> raw [R, S, 4].
+    Nothing but the inputs is kept for the backward: it runs the forward again, chunk by chunk, into the scratch, in the arithmetic
+    ``dtype`` of the forward."""
 
     @staticmethod
-    def forward(ctx, pts, viewdirs, cam, cfg, bounds, chunk, *params):
+    def forward(ctx, pts, viewdirs, cam, cfg, bounds, chunk, dtype, *params):
         c = nerf_grid_config(cfg)
-        weights = nerf_grid_pack(dict(zip(NERF_QUERY_PARAMS, params)), cfg)
+        weights = nerf_grid_pack(dict(zip(NERF_QUERY_PARAMS, params)), cfg, dtype)
         R, S = int(pts.shape[0]), int(pts.shape[1])
         size = (R, S, chunk, c["multires"], c["multires_views"], c["input_ch_cam"])
         nbytes = lib.query("nerfquery_work_bytes", 0, *size)
@@ -2880,8 +2919,9 @@ class NerfQueryFn(torch.autograd.Function):
             raise lib.NrpnError(f"nerf_query: {R} rays of {S} points in chunks of {chunk} are outside the supported range")
         work = torch.empty(nbytes, dtype=torch.uint8, device=pts.device)
         raw = torch.empty((R, S, 4), dtype=torch.float32, device=pts.device)
-        call("nerfquery_forward", _p(pts), _p(viewdirs), R, S, *bounds, c["multires"], c["multires_views"], c["input_ch_cam"],
-             _p(weights.packed), _p(weights.w_view), _p(weights.b_views), _p(cam) if c["input_ch_cam"] else None, chunk, _p(work), nbytes,
+        name, head = weights.entry("nerfquery_forward", _p(pts), _p(viewdirs), R, S, *bounds, c["multires"], c["multires_views"],
+                                   c["input_ch_cam"], _p(weights.packed))
+        call(name, *head, _p(weights.w_view), _p(weights.b_views), _p(cam) if c["input_ch_cam"] else None, chunk, _p(work), nbytes,
              _p(raw), _s())
         ctx.save_for_backward(pts, viewdirs, cam)
         ctx.weights, ctx.size, ctx.bounds, ctx.shapes = weights, size, bounds, [tuple(p.shape) for p in params]
@@ -2900,8 +2940,9 @@ class NerfQueryFn(torch.autograd.Function):
         work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         grads = torch.empty(lib.query("nerfquery_work_bytes", 3, *size), dtype=torch.float32, device=dev)
         draw = draw.to(torch.float32).contiguous()
-        call("nerfquery_backward", _p(pts), _p(viewdirs), R, S, *ctx.bounds, multires, multires_views, cam_ch, _p(weights.packed),
-             _p(packed_t), _p(weights.w_view), _p(weights.b_views), _p(cam) if cam_ch else None, _p(draw), chunk, _p(work), nbytes,
+        name, head = weights.entry("nerfquery_backward", _p(pts), _p(viewdirs), R, S, *ctx.bounds, multires, multires_views, cam_ch,
+                                   _p(weights.packed))
+        call(name, *head, _p(packed_t), _p(weights.w_view), _p(weights.b_views), _p(cam) if cam_ch else None, _p(draw), chunk, _p(work), nbytes,
              _p(grads), _s())
         out, at = [], 0
         for shape in ctx.shapes:
@@ -2909,10 +2950,10 @@ class NerfQueryFn(torch.autograd.Function):
             out.append(grads[at:at + n].view(shape))
             at += n
         dcam = grads[at:at + cam_ch]
-        return (None, None, dcam, None, None, None, *out)
+        return (None, None, dcam, None, None, None, None, *out)
 
 
-def nerf_query(params, cfg, pts, viewdirs, embedded_cam=None, bb_center=(0., 0., 0.), bb_scale=1., chunk=None):
+def nerf_query(params, cfg, pts, viewdirs, embedded_cam=None, bb_center=(0., 0., 0.), bb_scale=1., chunk=None, dtype="fp32"):
     """network_query_fn(pts, viewdirs, embedded_cam, network_fn) of the reference (run_network, run_nerf.py:50-65) for the NeRF MLP of
     DESIGN.md 3.16, differentiable with respect to the network's 24 parameter tensors and to embedded_cam.
 
@@ -2927,7 +2968,11 @@ def nerf_query(params, cfg, pts, viewdirs, embedded_cam=None, bb_center=(0., 0.,
     per point (11520 for the default options), plus 512 + 4 * ceil64(views_ch + input_ch_cam) bytes per ray, 16 MiB of slice partials
     and the float64 gradient (lib.query("nerfquery_work_bytes", ...) has the figures).  raw does not depend on chunk, bit for bit.
     The gradients are sums over points: for a given chunk and given inputs they are bit-equal from call to call (no atomics,
-    fixed-order sums); for different chunks they differ in rounding only."""
+    fixed-order sums); for different chunks they differ in rounding only.
+
+    dtype "bf16x3": the trunk's matrix products, in the forward and in the backward's re-run of it, use the split arithmetic of
+    DESIGN.md 3.23; the backward's own products stay exact fp32 on the activations that forward produced."""
+    nerf_check_dtype(dtype)
     c = nerf_grid_config(cfg)
     if not torch.cuda.is_available():
         raise lib.NrpnError("nerf_query needs a gfx950 device (the product path has no CPU fallback)")
@@ -2958,7 +3003,7 @@ def nerf_query(params, cfg, pts, viewdirs, embedded_cam=None, bb_center=(0., 0.,
     chunk = NERF_QUERY_DEFAULT_CHUNK if chunk is None else int(chunk)
     if chunk < 1:
         raise lib.NrpnError(f"nerf_query: chunk {chunk}")
-    return NerfQueryFn.apply(pts, viewdirs, cam, cfg, _nerf_bounds(bb_center, bb_scale), chunk, *(sd[k] for k in NERF_QUERY_PARAMS))
+    return NerfQueryFn.apply(pts, viewdirs, cam, cfg, _nerf_bounds(bb_center, bb_scale), chunk, dtype, *(sd[k] for k in NERF_QUERY_PARAMS))
 
 
 # ======================================================================================================================

@@ -1,7 +1,8 @@
 """Extract the rgb-sigma grid of a trained Dense-Depth-Priors NeRF (reference data/scannet/run_nerf.py, task ``extract``).
 
 Run as ``python -m nerf_rpn_amd.scripts.nerf_extract --expname NAME --ckpt_dir DIR --data_dir DIR --scene_id SCENE --extract_dir DIR
---bbox_json FILE [--max_res 256] [--layout flat|wlh]`` -- the reference's extract flags.  ``<ckpt_dir>/<expname>/args.json`` gives the
+--bbox_json FILE [--max_res 256] [--layout flat|wlh] [--dtype fp32|bf16x3]`` -- the reference's extract flags, and the arithmetic of
+the MLP trunk.  ``<ckpt_dir>/<expname>/args.json`` gives the
 network options, the last sorted checkpoint whose name contains ``000.tar`` gives ``network_fn_state_dict`` (load_checkpoint,
 run_nerf.py:333-342), ``--bbox_json`` (what scannet_generate_bbox writes) gives the grid's box (get_scene_bounding_box, :1197-1210) and
 the grid is min .. max in round(extent / largest extent * max_res) steps per axis (:1160-1168).  Every grid point goes through the MLP
@@ -43,6 +44,8 @@ def build_parser():
     p.add_argument('--image_hw', type=int, nargs=2, default=None, metavar=('H', 'W'))
     p.add_argument('--far', type=float, default=None)
     p.add_argument('--layout', choices=('flat', 'wlh'), default='flat')
+    p.add_argument('--dtype', choices=('fp32', 'bf16x3'), default='fp32',
+                   help='arithmetic of the MLP trunk: exact fp32, or three bf16 MFMA products of split operands (DESIGN.md 3.23)')
     return p
 
 
@@ -107,13 +110,15 @@ def corner_bounds(H, W, intrinsics, poses, far):
     return (hi + lo) / 2., 2. / (hi - lo).max(), lo, hi
 
 
-def extract(cfg, state_dict, poses, bbox_json, max_res, bb_center, bb_scale, layout='flat', chunk=None):
+def extract(cfg, state_dict, poses, bbox_json, max_res, bb_center, bb_scale, layout='flat', chunk=None, dtype='fp32'):
     """extract_nerf -> (rgbsigma numpy float32, resolution list, bbox_min, bbox_max numpy float32)."""
     from nerf_rpn_amd import ops
     lo, hi = scene_bounding_box(bbox_json)
     res, xs, ys, zs = grid_axes(lo, hi, max_res)
     print(f'nerf_extract: grid {res[0]} x {res[1]} x {res[2]} over {lo.tolist()} .. {hi.tolist()}, {len(poses)} poses')
-    out = ops.nerf_grid_query(state_dict, cfg, xs, ys, zs, bb_center, bb_scale, poses, layout=layout, chunk=chunk)
+    # the op takes the arithmetic from packed weights; a state dict is packed by the op itself, in fp32
+    net = state_dict if dtype == 'fp32' else ops.nerf_grid_pack(state_dict, cfg, dtype)
+    out = ops.nerf_grid_query(net, cfg, xs, ys, zs, bb_center, bb_scale, poses, layout=layout, chunk=chunk)
     return out.cpu().numpy(), res, lo.numpy(), hi.numpy()
 
 
@@ -137,7 +142,7 @@ def main(argv=None):
             raise SystemExit('scene bounds: give --bb_center and --bb_scale, or --image_hw H W and --far (or "far" in the transforms json)')
         bb_center, bb_scale, lo, hi = corner_bounds(args.image_hw[0], args.image_hw[1], intrinsics, poses, far)
         print(f'nerf_extract: scene bounds from the corner rays: {lo.tolist()} .. {hi.tolist()}')
-    rgbsigma, res, bbox_min, bbox_max = extract(cfg, state_dict, poses, args.bbox_json, args.max_res, bb_center, bb_scale, args.layout)
+    rgbsigma, res, bbox_min, bbox_max = extract(cfg, state_dict, poses, args.bbox_json, args.max_res, bb_center, bb_scale, args.layout, dtype=args.dtype)
     os.makedirs(args.extract_dir or '.', exist_ok=True)
     path = os.path.join(args.extract_dir, f'{args.scene_id}.npz')
     np.savez_compressed(path, rgbsigma=rgbsigma, resolution=res, bbox_min=bbox_min, bbox_max=bbox_max, scale=1.0, offset=0.0,

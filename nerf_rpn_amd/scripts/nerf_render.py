@@ -2,7 +2,8 @@
 tasks ``video``, ``test`` and ``render_train_depth`` do through render -> render_rays).
 
 Run as ``python -m nerf_rpn_amd.scripts.nerf_render --expname NAME --ckpt_dir DIR --data_dir DIR --scene_id SCENE --image_hw H W
---output_dir DIR [--frames 0 5 9] [--near X] [--far X] [--N_samples N] [--depth_loss_weight W] [--lindisp]``.  The checkpoint and the
+--output_dir DIR [--frames 0 5 9] [--near X] [--far X] [--N_samples N] [--depth_loss_weight W] [--lindisp] [--dtype fp32|bf16x3]``.  The
+checkpoint and the
 network options are found as nerf_extract finds them; N_samples, depth_loss_weight and lindisp default to the training run's
 ``args.json`` (else 256, 0.004, off -- config_parser's defaults, run_nerf.py:955-984).  depth_loss_weight > 0 selects the two-pass
 path of render_rays (:595-600): the N_samples / 2 precomputed quadratic samples (:1076-1077), then as many around the depth they
@@ -47,6 +48,8 @@ def build_parser():
     p.add_argument('--frames', type=int, nargs='*', default=None, help='indices into the transforms json (default: all)')
     p.add_argument('--chunk', type=int, default=None, help='rays per launch group')
     p.add_argument('--output_dir', type=str, default="")
+    p.add_argument('--dtype', choices=('fp32', 'bf16x3'), default='fp32',
+                   help='arithmetic of the MLP trunk: exact fp32, or three bf16 MFMA products of split operands (DESIGN.md 3.23)')
     return p
 
 
@@ -120,7 +123,7 @@ def prepare(args, tool='nerf_render', transforms_name='transforms_test.json'):
         if not 0 <= i < len(poses):
             raise SystemExit(f'{tool}: frame {i} of {len(poses)}')
     z_samples = precompute_quadratic_samples(near, far, n_samples // 2) if two_pass else None
-    weights = ops.nerf_grid_pack(state_dict, cfg)
+    weights = ops.nerf_grid_pack(state_dict, cfg, getattr(args, 'dtype', 'fp32'))
     return SimpleNamespace(cfg=cfg, weights=weights, H=H, W=W, poses=poses, intrinsics=intrinsics, near=near, far=far, meta=meta,
                            transforms=transforms, bb_center=bb_center, bb_scale=bb_scale, frames=frames, z_samples=z_samples,
                            n_samples=n_samples, lindisp=lindisp)

@@ -5,7 +5,9 @@ Run as ``python -m nerf_rpn_amd.scripts.nerf_train --expname NAME --ckpt_dir DIR
 plus the flags of config_parser (:924-1008) that the train task reads, with its defaults: ``--N_rand --lrate --start_decay_lrate
 --end_decay_lrate --no_reload --depth_loss_weight --N_samples --perturb --multires_views --input_ch_cam --raw_noise_std --lindisp
 --i_print --i_weights --chunk``; ``--near --far --bb_center --bb_scale`` as in nerf_render; ``--N_iters`` (default 500001, which the
-reference hard-codes) and ``--depth_std`` (metres).  An option ops.nerf_grid_config rejects (netdepth, netwidth, multires, i_embed,
+reference hard-codes), ``--depth_std`` (metres) and ``--dtype fp32|bf16x3`` (default fp32: the arithmetic of the MLP trunk in every step
+and in the evaluation at the end; it is written to args.json, the checkpoints are float32 with the same keys either
+way).  An option ops.nerf_grid_config rejects (netdepth, netwidth, multires, i_embed,
 N_importance, use_viewdirs) raises as in every NeRF tool here.
 
 Data: ``<data_dir>/<scene_id>/transforms_train.json`` with nerf_extract's keys; the images and depths of its frames as nerf_test
@@ -57,6 +59,8 @@ def build_parser():
     p.add_argument('--lindisp', action='store_true', default=False)
     p.add_argument('--N_iters', type=int, default=500001, help='the loop runs steps 1 .. N_iters - 1')
     p.add_argument('--depth_std', type=float, default=None, help='standard deviation of the depth prior in metres, without a std file')
+    p.add_argument('--dtype', choices=('fp32', 'bf16x3'), default='fp32',
+                   help='arithmetic of the MLP trunk: exact fp32, or three bf16 MFMA products of split operands (DESIGN.md 3.23)')
     return p
 
 
@@ -128,6 +132,7 @@ def main(argv=None):
         targs = NT.build_parser().parse_args(['--expname', args.expname, '--ckpt_dir', args.ckpt_dir, '--data_dir', args.data_dir,
                                               '--scene_id', args.scene_id, '--image_hw', str(run.H), str(run.W)])
         targs.near, targs.far, targs.bb_center, targs.bb_scale = run.near, run.far, args.bb_center, args.bb_scale
+        targs.dtype = args.dtype
         trun = test_run(targs, run, args, result.model)
         NT.run_frames(targs, trun, NT.result_dir(targs), tool='nerf_train')
     return result
@@ -142,7 +147,7 @@ def test_run(targs, run, args, model):
     poses, intrinsics, _, meta = load_transforms(transforms, with_meta=True)
     n_samples, two_pass, lindisp = NR.render_options(targs, cfg)
     z_samples = NR.precompute_quadratic_samples(run.near, run.far, n_samples // 2) if two_pass else None
-    weights = ops.nerf_grid_pack({k: v.detach() for k, v in model.state_dict().items()}, cfg)
+    weights = ops.nerf_grid_pack({k: v.detach() for k, v in model.state_dict().items()}, cfg, getattr(args, 'dtype', 'fp32'))
     return SimpleNamespace(cfg=cfg, weights=weights, H=run.H, W=run.W, poses=poses, intrinsics=intrinsics, near=run.near, far=run.far,
                            meta=meta, transforms=transforms, bb_center=run.bb_center, bb_scale=run.bb_scale,
                            frames=list(range(len(poses))), z_samples=z_samples, n_samples=n_samples, lindisp=lindisp)
