@@ -736,7 +736,7 @@ int nrpn_nerfgrid_query(const float *xs, const float *ys, const float *zs, int r
  * The bf16x3 arithmetic of the trunk, opt-in twins of the fp32 entries.  The ten matrix products of the trunk
  * (pts_linears.0 .. 7, feature_linear, g = W_f f) carry each operand as hi = bf16(x), lo = bf16(x - hi) and add hi*hi + hi*lo + lo*hi
  * on v_mfma_f32_32x32x16_bf16 in fp32 accumulators; encoding, biases, relu, alpha_linear, the heads and every backward product stay
- * exact fp32.  Tensors stay float32.  A twin takes its fp32 entry's arguments plus ``split`` after ``packed``.
+ * exact fp32 (the backward's products: unless nrpn_nerfquery_backward_bf16x3_split is the entry called).  Tensors stay float32.  A twin takes its fp32 entry's arguments plus ``split`` after ``packed``.
  * nrpn_nerfgrid_work_bytes(2, 0): bytes of the planes.
  * nrpn_nerfgrid_pack_bf16x3 (the model of create_nerf, run_nerf.py:344-358, as nrpn_nerfgrid_pack reads it): raw as for
  *   nrpn_nerfgrid_pack -> planes: the hi plane of the ten matrices in the fragment order of the bf16 MFMA, then the lo plane; the zero
@@ -871,7 +871,7 @@ int nrpn_nerfcamopt_eval(const float *rays, int64_t num_rays, float center_x, fl
  * weights of nrpn_nerfgrid_pack; DESIGN.md 3.20.  Points are processed chunk points at a time (rounded up to tiles of 64); no atomics.
  * nrpn_nerfquery_work_bytes(what, num_rays, num_samples, chunk, multires, multires_views, input_ch_cam): what 0: bytes of forward's
  *   scratch; 1: of backward's; 2: of the packed transposes; 3: floats of the gradient array; 4: backward's scratch bytes per point of
- *   a chunk.  -1 for sizes outside the supported range.
+ *   a chunk; 5: bytes of the bf16x3 planes of the packed transposes.  -1 for sizes outside the supported range.
  * nrpn_nerfquery_pack_t: raw as for nrpn_nerfgrid_pack -> packed_t, the h columns of pts_linears.1 .. 7, feature_linear and W_f
  *   transposed, in the B-fragment order of the forward weights.
  * nrpn_nerfquery_forward (run_network :50-65): pts f32 [num_rays][num_samples][3] world points, normalised as (pts - center) *
@@ -909,6 +909,23 @@ int nrpn_nerfquery_backward_bf16x3(const float *pts, const float *viewdirs, int6
                                    const float *packed, const void *split, const float *packed_t, const float *w_view,
                                    const float *b_view, const float *embedded_cam, const float *draw, int64_t chunk, void *work,
                                    int64_t work_bytes, float *grads, nrpn_stream_t stream);
+/* The backward's own products in the bf16x3 arithmetic (ops.nerf_query backward_dtype="bf16x3").
+ * nrpn_nerfquery_work_bytes(5, ..): bytes of the planes of the packed transposes.
+ * nrpn_nerfquery_pack_t_bf16x3: raw as for nrpn_nerfgrid_pack -> planes_t: the nine matrices of nrpn_nerfquery_pack_t as the hi plane
+ *   in the fragment order of the bf16 MFMA, then the lo plane; element for element the split of nrpn_nerfgrid_pack_bf16x3.
+ * nrpn_nerfquery_backward_bf16x3_split (loss.backward() :848 below raw): nrpn_nerfquery_backward_bf16x3 with split_t in place of
+ *   packed_t.  The nine dgrads dX = dY W and the wgrads dW = dY^T X of the trunk's ten matrices (pts_linears.0 .. 7 with their encoding
+ *   columns, feature_linear, the feature columns of views_linears.0) split both operands and add hi*hi + hi*lo + lo*hi on
+ *   v_mfma_f32_32x32x16_bf16 in fp32 accumulators, wgrad 16 points at a time in point order per slice.  The wgrads of rgb_linear,
+ *   alpha_linear and the view and camera columns of views_linears.0, the head's backward, the relu masks, the dsigma w_alpha term, every
+ *   bias gradient (float64 column sums of the unsplit dY in nrpn_nerfquery_backward's order) and embedded_cam's stay exact.  Scratch,
+ *   slices, the float64 reductions and the bit-equality of repeated calls are nrpn_nerfquery_backward's. */
+int nrpn_nerfquery_pack_t_bf16x3(const float *raw, int input_ch, void *planes_t, nrpn_stream_t stream);
+int nrpn_nerfquery_backward_bf16x3_split(const float *pts, const float *viewdirs, int64_t num_rays, int num_samples, float center_x,
+                                         float center_y, float center_z, float bb_scale, int multires, int multires_views,
+                                         int input_ch_cam, const float *packed, const void *split, const void *split_t,
+                                         const float *w_view, const float *b_view, const float *embedded_cam, const float *draw,
+                                         int64_t chunk, void *work, int64_t work_bytes, float *grads, nrpn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The ray stage of NeRF training as differentiable operations, ops.nerf_composite and ops.nerf_ray_losses.  [f10]  Replaces

@@ -16,6 +16,10 @@
 //            dW for one slice and adds its points in order; the bias gradient is the column sum of dY, taken by the same waves
 //   reduce   adds the slices in slice order in float64 into the float64 gradient, chunk after chunk
 // and finish: dcam = W_c^T db_views, everything rounded to float32.  No atomics: for a given chunk size every sum has a fixed order.
+//
+// backward_dtype "bf16x3" (DESIGN.md 3.24): the dgrads and the wgrads of the trunk's ten matrices run in the split arithmetic of the
+// forward (nerf_mlp.cuh) on v_mfma_f32_32x32x16_bf16 -- dgrad on the pre-split planes of W^T (nrpn_nerfquery_pack_t_bf16x3), wgrad on
+// operands split on their way through LDS; the column sums of dY are taken from the unsplit dY in the order of the fp32 wgrad.
 #include "nerf_mlp.cuh"
 
 namespace {
@@ -290,6 +294,23 @@ __global__ void nerfquery_pack_t_kernel(const float *__restrict__ raw, float *__
   }
 }
 
+// The bf16x3 planes of the same nine transposes (splitting commutes with transposing: element for element these are the values of the
+// forward's planes): k-step ks = 16 consecutive rows of W; the eight bf16 of (ks, o, h) hold W[16 ks + 8 h + j][col_off + o], j = 0 .. 7,
+// at ((ks * 256 + o) * 2 + h) * 8 of the hi plane, their residuals at the same place of the lo plane, kPackedTFloats elements on.
+__global__ void nerfquery_pack_t_split_kernel(const float *__restrict__ raw, unsigned short *__restrict__ planes_t, PackTPlan plan) {
+  const PackTSeg s = plan.seg[blockIdx.y];
+  const int64_t total = (int64_t)s.K * kW;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int j = (int)(i & 7), h = (int)((i >> 3) & 1);
+    const int64_t q = i >> 4;
+    const int o = (int)(q % kW), ks = (int)(q / kW);
+    const float v = raw[s.src + (int64_t)(16 * ks + 8 * h + j) * s.ld + s.col_off + o];
+    const __bf16 hb = (__bf16)v;
+    planes_t[s.dst + i] = __builtin_bit_cast(unsigned short, hb);
+    planes_t[kPackedTFloats + s.dst + i] = f32_to_bf16_bits(v - (float)hb);
+  }
+}
+
 // ---- dgrad -----------------------------------------------------------------------------------------------------------------------
 // One workgroup of 256 threads, one tile: out[p][0 .. 255] = (sum_n dy[p][n] W[n][.] + dsig[p] * alpha_w[.]) [mask[p][.] > 0].  dy
 // [rows][K], K = 128 or 256; wt: the packed W^T; dsig: column 3 of dyhead, or null; mask [rows][256] or null; out may be mask.
@@ -328,6 +349,85 @@ __global__ __launch_bounds__(256) void nerfquery_dgrad_kernel(const float *__res
         if (mask) v = mask[row * kW + col] > 0.f ? v : 0.f;
         out[row * kW + col] = v;
       }
+  }
+}
+
+// The same product in the bf16x3 arithmetic: dy split in registers as the forward splits its activations, wt_hi / wt_lo the planes of the
+// packed W^T (nerfquery_pack_t_split_kernel); the epilogue's arithmetic (the dsigma w_alpha fmaf, the relu mask) is the fp32 kernel's.
+// Memory is walked as the trunk's keep() walks it: the tile's loads are all issued before the first is stored to the image, the
+// result goes back through the image, and a thread then takes whole float4 of a row -- its 16 mask loads first, then its 16 stores
+// (out may be mask; an element is read and written by the same thread only).
+// K = 128 without a mask (df) or 256 with one.
+template <int K, bool kMask>
+__global__ __launch_bounds__(256) void nerfquery_dgrad_split_kernel(const float *__restrict__ dy, const uint4 *__restrict__ wt_hi,
+                                                                    const uint4 *__restrict__ wt_lo, const float *__restrict__ dyhead,
+                                                                    const float *__restrict__ alpha_w, const float *mask, float *out) {
+  constexpr int kInVec = kTile * (K / 4) / 256, kOutVec = kTile * (kW / 4) / 256;       // float4 per thread of the dy and the out tile
+  extern __shared__ __align__(16) float act[];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
+  const int64_t row0 = (int64_t)blockIdx.x * kTile;
+  {
+    float4 v[kInVec];
+#pragma unroll
+    for (int i = 0; i < kInVec; ++i) {
+      const int idx = t + 256 * i;
+      v[i] = *reinterpret_cast<const float4 *>(dy + (row0 + idx / (K / 4)) * K + 4 * (idx % (K / 4)));
+    }
+#pragma unroll
+    for (int i = 0; i < kInVec; ++i) {
+      const int idx = t + 256 * i;
+      *reinterpret_cast<float4 *>(act + idx / (K / 4) * kLd + kEnc + 4 * (idx % (K / 4))) = v[i];
+    }
+  }
+  __syncthreads();
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[m][c][e] = 0.f;
+  const int col0 = wave * 64;
+  gemm_tile_split<2>(act, kEnc, K, wt_hi, wt_lo, kW, col0, acc);
+  float ds[2][16];
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) ds[m][e] = dyhead ? dyhead[(row0 + 32 * m + acc_row(e, h)) * kHeadCols + 3] : 0.f;
+  __syncthreads();                                            // every wave has read dy
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    const int col = col0 + 32 * c + r;
+    const float aw = dyhead ? alpha_w[col] : 0.f;
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        float v = acc[m][c][e];
+        if (dyhead) v = fmaf(ds[m][e], aw, v);
+        act[(32 * m + acc_row(e, h)) * kLd + kEnc + col] = v;
+      }
+  }
+  float4 mk[kOutVec];
+  if constexpr (kMask) {
+#pragma unroll
+    for (int i = 0; i < kOutVec; ++i) {
+      const int idx = t + 256 * i;
+      mk[i] = *reinterpret_cast<const float4 *>(mask + (row0 + (idx >> 6)) * kW + 4 * (idx & 63));
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < kOutVec; ++i) {
+    const int idx = t + 256 * i, row = idx >> 6, c4 = idx & 63;
+    float4 v = *reinterpret_cast<const float4 *>(act + row * kLd + kEnc + 4 * c4);
+    if constexpr (kMask) {
+      v.x = mk[i].x > 0.f ? v.x : 0.f;
+      v.y = mk[i].y > 0.f ? v.y : 0.f;
+      v.z = mk[i].z > 0.f ? v.z : 0.f;
+      v.w = mk[i].w > 0.f ? v.w : 0.f;
+    }
+    *reinterpret_cast<float4 *>(out + (row0 + row) * kW + 4 * c4) = v;
   }
 }
 
@@ -418,6 +518,162 @@ __global__ __launch_bounds__(256) void nerfquery_wgrad_kernel(const float *__res
   }
 }
 
+// ---- wgrad in the bf16x3 arithmetic ------------------------------------------------------------------------------------------------
+// The summed index is the point, and the bf16 MFMA wants a lane to hold 8 consecutive points of one channel, while dY and X are
+// [point][channel].  A workgroup therefore stages blocks of kWsPts points of the 320 channels its four waves need -- 64 of one
+// operand and 256 of the other -- through LDS: a thread reads 8 consecutive points of one channel (a wave: 64 consecutive channels of a
+// row, coalesced), splits them once and stores the 16 bytes of each plane at [channel][point].  A channel row is 80 bytes: the 16
+// lanes a ds_read_b128 serves together read rows r, r + 1, .. at 16 distinct 16-byte slots of the 256-byte bank window, and so do
+// the 8 lanes of a ds_write_b128 in its 128-byte one.  Two LDS images alternate; the next block's global loads are issued before the
+// current block's MFMAs and split and stored after them, so one barrier per block suffices.
+constexpr int kWsPts = 32;                                   // points per block: two k-steps of the MFMA
+constexpr int kWsCols = 320;                                 // staged channels, dY's first
+constexpr int kWsRow = kWsPts + 8;                           // bf16 per channel row of a plane
+constexpr int kWsOct = kWsCols * (kWsPts / 8) / 256;         // (channel, 8 points) pieces per thread and block: 5
+constexpr int kWsPlane = kWsCols * kWsRow;                   // bf16 per plane
+constexpr int kWsLdsBytes = 2 * 2 * kWsPlane * 2;            // two images of two planes: 102400
+static_assert(kSlices % 8 == 0, "nerfquery_wgrad_split_kernel spreads the slices over 8 XCDs");
+static_assert(kTile % (2 * kWsPts) == 0, "a slice of whole tiles is whole pairs of blocks: the two LDS images alternate in pairs");
+
+struct WsPiece {            // one thread's share of a block, unsplit
+  float v[kWsOct][8];
+};
+
+// As nerfquery_wgrad_kernel without the column sums, kpad 256 or 64, grid (blocks / 4, kSlices): the four waves of a slice's workgroup
+// ``group`` own the blocks (nb, kb) = (group, wave) of a 256-column X, or (4 group + wave, 0) of a 64-column one.  Per 16 points a
+// wave adds hi hi, hi lo, lo hi of its 64 x 64 block into the same fp32 accumulators, the points in order.
+__global__ __launch_bounds__(256) void nerfquery_wgrad_split_kernel(const float *__restrict__ dy, int ldy, int n, const float *__restrict__ x,
+                                                                    int ldx, int kpad, int64_t rows, int64_t rows_per_slice,
+                                                                    float *__restrict__ partial) {
+  extern __shared__ __align__(16) unsigned short ws[];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
+  const bool wide_x = kpad == 256;
+  const int aw = wide_x ? 64 : 256;                          // staged columns of dY; the other 320 - aw are X's
+  // The gridDim.x workgroups of a slice read the same rows of X.  Workgroups go to the 8 XCDs round-robin in launch order, so the
+  // (column group, slice) of a workgroup is taken from its launch index such that a slice's workgroups share an XCD and its L2; which
+  // workgroup computes a block changes no sum.
+  const int launch = blockIdx.x + gridDim.x * blockIdx.y, xcd = launch & 7, in_xcd = launch >> 3;
+  const int group = in_xcd % gridDim.x;
+  const int64_t slice = xcd + 8 * (in_xcd / gridDim.x);
+  const int a0 = group * aw;
+  const int ai = wide_x ? 0 : wave, bi = wide_x ? wave : 0;  // the wave's 64-column block among the staged ones
+  const int nb = (a0 >> 6) + ai, kb = bi;
+  int64_t p0 = slice * rows_per_slice, p1 = p0 + rows_per_slice;
+  if (p0 > rows) p0 = rows;
+  if (p1 > rows) p1 = rows;
+  const int blocks = (int)((p1 - p0) / kWsPts);              // rows come in whole tiles: a multiple of 2, or 0
+
+  const float *src[kWsOct];
+  int64_t ld[kWsOct];
+  int at[kWsOct];                                            // of the piece in a plane, in bf16
+#pragma unroll
+  for (int i = 0; i < kWsOct; ++i) {
+    const int q = i * 256 + t, c = q % kWsCols, pg = q / kWsCols;
+    ld[i] = c < aw ? ldy : ldx;
+    src[i] = (c < aw ? dy + a0 + c : x + (c - aw)) + (p0 + 8 * pg) * ld[i];
+    at[i] = c * kWsRow + 8 * pg;
+  }
+  auto load = [&](WsPiece &w, int blk) {
+#pragma unroll
+    for (int i = 0; i < kWsOct; ++i)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) w.v[i][j] = src[i][((int64_t)blk * kWsPts + j) * ld[i]];
+  };
+  auto store = [&](const WsPiece &w, int image) {
+    unsigned short *base = ws + image * 2 * kWsPlane;
+#pragma unroll
+    for (int i = 0; i < kWsOct; ++i) {
+      bf16x8 hi, lo;
+      split8(make_float4(w.v[i][0], w.v[i][1], w.v[i][2], w.v[i][3]), make_float4(w.v[i][4], w.v[i][5], w.v[i][6], w.v[i][7]), hi, lo);
+      *reinterpret_cast<uint4 *>(base + at[i]) = __builtin_bit_cast(uint4, hi);
+      *reinterpret_cast<uint4 *>(base + kWsPlane + at[i]) = __builtin_bit_cast(uint4, lo);
+    }
+  };
+
+  f32x16 acc[2][2];
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[m][c][e] = 0.f;
+  const int a_at = (ai * 64 + r) * kWsRow + 8 * h, b_at = (aw + bi * 64 + r) * kWsRow + 8 * h;
+
+  auto mma = [&](int image) {
+    const unsigned short *img = ws + image * 2 * kWsPlane;
+#pragma unroll
+    for (int ks = 0; ks < kWsPts / 16; ++ks) {
+      bf16x8 ah[2], al[2], bh[2], bl[2];
+#pragma unroll
+      for (int m = 0; m < 2; ++m) {
+        ah[m] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4 *>(img + a_at + 32 * m * kWsRow + 16 * ks));
+        al[m] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4 *>(img + kWsPlane + a_at + 32 * m * kWsRow + 16 * ks));
+        bh[m] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4 *>(img + b_at + 32 * m * kWsRow + 16 * ks));
+        bl[m] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4 *>(img + kWsPlane + b_at + 32 * m * kWsRow + 16 * ks));
+      }
+#pragma unroll
+      for (int p = 0; p < 3; ++p)
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+          for (int m = 0; m < 2; ++m)
+            acc[m][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(p == 2 ? al[m] : ah[m], p == 1 ? bl[c] : bh[c], acc[m][c], 0, 0, 0);
+    }
+  };
+
+  // Blocks come in pairs.  Entering the even half of a pair image 0 holds block blk, wb block blk + 1 and wa's loads of block blk + 2
+  // are in flight; each half stores the set loaded longest ago into the image read in the half before (behind that half's barrier),
+  // re-issues that set three blocks ahead and then multiplies: two blocks of loads are in flight under every block of MFMAs.
+  WsPiece wa, wb;
+  if (blocks > 0) {
+    load(wa, 0);
+    load(wb, 1);
+    store(wa, 0);
+    if (blocks > 2) load(wa, 2);
+  }
+  __syncthreads();
+  for (int blk = 0; blk < blocks; blk += 2) {
+    store(wb, 1);
+    if (blk + 3 < blocks) load(wb, blk + 3);
+    mma(0);
+    __syncthreads();
+    if (blk + 2 < blocks) store(wa, 0);
+    if (blk + 4 < blocks) load(wa, blk + 4);
+    mma(1);
+    __syncthreads();
+  }
+  float *out = partial + slice * n * kpad;
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int e = 0; e < 16; ++e)
+        out[(int64_t)(nb * 64 + 32 * m + acc_row(e, h)) * kpad + kb * 64 + 32 * c + r] = acc[m][c][e];
+}
+
+// bias f64 [slice][2][n] as nerfquery_wgrad_kernel leaves it, sum for sum: the column sums of the unsplit dY over the even and the odd
+// rows of a slice, each added in row order in float64.  One thread per (slice, parity, column); rows come in whole tiles.
+constexpr int kCsRows = 32;           // loads in flight per thread
+__global__ __launch_bounds__(128) void nerfquery_colsum_kernel(const float *__restrict__ dy, int ldy, int n, int64_t rows,
+                                                               int64_t rows_per_slice, double *__restrict__ bias) {
+  const int col = blockIdx.x * 64 + (threadIdx.x & 63), h = threadIdx.x >> 6;
+  const int64_t slice = blockIdx.y;
+  int64_t p0 = slice * rows_per_slice, p1 = p0 + rows_per_slice;
+  if (p0 > rows) p0 = rows;
+  if (p1 > rows) p1 = rows;
+  const float *ap = dy + (p0 + h) * ldy + col;
+  double s = 0.0;
+  for (int64_t p = 0; p < p1 - p0; p += 2 * kCsRows) {
+    float v[kCsRows];
+#pragma unroll
+    for (int j = 0; j < kCsRows; ++j) v[j] = ap[(p + 2 * j) * ldy];
+#pragma unroll
+    for (int j = 0; j < kCsRows; ++j) s += (double)v[j];
+  }
+  bias[(slice * 2 + h) * n + col] = s;
+}
+
 // gacc[dst + i * ld + j] += sum over the parts, in order, of partial[part][row_lo + i][col_lo + j], i < nr, j < nc; float64
 template <class T>
 __global__ void nerfquery_reduce_kernel(const T *__restrict__ partial, int parts, int n, int kpad, int row_lo, int nr, int col_lo,
@@ -447,6 +703,17 @@ __global__ void nerfquery_finish_kernel(double *__restrict__ gacc, int64_t total
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
+PackTPlan pack_t_plan(int input_ch) {
+  PackTPlan plan{};
+  int64_t src = (int64_t)kW * input_ch;                       // after pts_linears.0
+  for (int i = 1; i <= 9; ++i) {                              // raw order: pts_linears 1 .. 7, feature_linear, W_f
+    const int ld = i == kSkipLayer ? input_ch + kW : kW, K = i == 9 ? kHalf : kW;
+    plan.seg[i - 1] = PackTSeg{(int64_t)(i - 1) * kSzT, src, ld, i == kSkipLayer ? input_ch : 0, K};
+    src += (int64_t)K * ld;
+  }
+  return plan;
+}
+
 struct QueryCall {
   Points pp;
   Model m;
@@ -456,6 +723,7 @@ struct QueryCall {
   int64_t work_bytes;
   hipStream_t stream;
   const uint4 *split;       // the bf16x3 planes of packed (kSplit launchers only)
+  const uint4 *split_t = nullptr;      // the bf16x3 planes of the packed transposes (backward<true, true> only)
   int64_t chunk_tiles() const { return cdiv64(chunk < pp.num_points ? chunk : pp.num_points, kTile); }
 };
 
@@ -556,18 +824,28 @@ struct Wgrad {            // one product of the backward and where its rows and 
   int64_t dst;            // of the first of them in the gradient
   int ld;
   int64_t bias_dst;       // of column sum row_lo, or -1
+  bool trunk = false;     // one of the trunk's ten matrices: split under kSplitBwd
 };
 
-template <bool kSplit>
+// kSplitBwd (with kSplit): the dgrads and the trunk's wgrads in the bf16x3 arithmetic too, on c.split_t in place of packed_t
+template <bool kSplit, bool kSplitBwd = false>
 int backward(const QueryCall &c, const float *packed_t, const float *draw, float *grads) {
+  static_assert(kSplit || !kSplitBwd, "the split backward belongs to the split forward");
   if (int rc = check("nerfquery_backward", c, true)) return rc;
-  NRPN_REQUIRE(packed_t && draw && grads && (!kSplit || c.split), "nerfquery_backward: null pointer");
+  NRPN_REQUIRE((kSplitBwd ? (const void *)c.split_t : (const void *)packed_t) && draw && grads && (!kSplit || c.split),
+               "nerfquery_backward: null pointer");
   if constexpr (kSplit) {
     NRPN_LDS(nerfquery_trunk_keep_bf16x3_kernel, kLdsBytes);
   } else {
     NRPN_LDS(nerfquery_trunk_keep_kernel, kLdsBytes);
   }
-  NRPN_LDS(nerfquery_dgrad_kernel, kLdsBytes);
+  if constexpr (kSplitBwd) {
+    NRPN_LDS((nerfquery_dgrad_split_kernel<kHalf, false>), kLdsBytes);
+    NRPN_LDS((nerfquery_dgrad_split_kernel<kW, true>), kLdsBytes);
+    NRPN_LDS(nerfquery_wgrad_split_kernel, kWsLdsBytes);
+  } else {
+    NRPN_LDS(nerfquery_dgrad_kernel, kLdsBytes);
+  }
   const Model &m = c.m;
   const Layout l = layout(m, c.num_rays, c.chunk_tiles());
   const GradLayout gl = grad_layout(m);
@@ -590,9 +868,20 @@ int backward(const QueryCall &c, const float *packed_t, const float *draw, float
     // h and f of this chunk are laid out for l.rows rows whatever the chunk's own count: Kept::rows is the stride of h's layers
     auto wgrad = [&](const Wgrad &w) -> int {
       const int blocks = (w.n >> 6) * (w.kpad >> 6);
-      nerfquery_wgrad_kernel<<<dim3((blocks + 3) / 4, kSlices), 256, 0, c.stream>>>(w.dy, w.ldy, w.n, w.x, w.ldx, w.kpad, rows, rps, partial,
-                                                                                   w.bias_dst >= 0 ? bias : nullptr);
-      NRPN_LAUNCH_CHECK("nerfquery_wgrad_kernel");
+      if (kSplitBwd && w.trunk) {
+        NRPN_REQUIRE((w.kpad == kW || w.kpad == kEnc) && blocks % 4 == 0, "nerfquery_backward: a %d x %d split wgrad", w.n, w.kpad);
+        nerfquery_wgrad_split_kernel<<<dim3(blocks / 4, kSlices), 256, kWsLdsBytes, c.stream>>>(w.dy, w.ldy, w.n, w.x, w.ldx, w.kpad, rows, rps,
+                                                                                              partial);
+        NRPN_LAUNCH_CHECK("nerfquery_wgrad_split_kernel");
+        if (w.bias_dst >= 0) {
+          nerfquery_colsum_kernel<<<dim3(w.n >> 6, kSlices), 128, 0, c.stream>>>(w.dy, w.ldy, w.n, rows, rps, bias);
+          NRPN_LAUNCH_CHECK("nerfquery_colsum_kernel");
+        }
+      } else {
+        nerfquery_wgrad_kernel<<<dim3((blocks + 3) / 4, kSlices), 256, 0, c.stream>>>(w.dy, w.ldy, w.n, w.x, w.ldx, w.kpad, rows, rps, partial,
+                                                                                     w.bias_dst >= 0 ? bias : nullptr);
+        NRPN_LAUNCH_CHECK("nerfquery_wgrad_kernel");
+      }
       if (w.nc > 0) {
         nerfquery_reduce_kernel<float><<<(w.nr * w.nc + 255) / 256, 256, 0, c.stream>>>(partial, kSlices, w.n, w.kpad, w.row_lo, w.nr, 0, w.nc, gacc,
                                                                                w.dst, w.ld);
@@ -606,9 +895,21 @@ int backward(const QueryCall &c, const float *packed_t, const float *draw, float
       return NRPN_OK;
     };
     auto dgrad = [&](const float *dy, int K, int64_t wt_at, bool alpha, const float *mask, float *out) -> int {
-      nerfquery_dgrad_kernel<<<tiles, 256, kLdsBytes, c.stream>>>(dy, K, packed_t + wt_at, alpha ? ho.dyhead : nullptr,
-                                                                  c.packed + kOffAlphaW, mask, out);
-      NRPN_LAUNCH_CHECK("nerfquery_dgrad_kernel");
+      if constexpr (kSplitBwd) {
+        const uint4 *hi = c.split_t + wt_at / 8, *lo = c.split_t + (kPackedTFloats + wt_at) / 8;
+        NRPN_REQUIRE((K == kHalf && !mask) || (K == kW && mask), "nerfquery_backward: a split dgrad of K %d", K);
+        if (K == kHalf)
+          nerfquery_dgrad_split_kernel<kHalf, false><<<tiles, 256, kLdsBytes, c.stream>>>(dy, hi, lo, alpha ? ho.dyhead : nullptr,
+                                                                                        c.packed + kOffAlphaW, mask, out);
+        else
+          nerfquery_dgrad_split_kernel<kW, true><<<tiles, 256, kLdsBytes, c.stream>>>(dy, hi, lo, alpha ? ho.dyhead : nullptr,
+                                                                                    c.packed + kOffAlphaW, mask, out);
+        NRPN_LAUNCH_CHECK("nerfquery_dgrad_split_kernel");
+      } else {
+        nerfquery_dgrad_kernel<<<tiles, 256, kLdsBytes, c.stream>>>(dy, K, packed_t + wt_at, alpha ? ho.dyhead : nullptr,
+                                                                    c.packed + kOffAlphaW, mask, out);
+        NRPN_LAUNCH_CHECK("nerfquery_dgrad_kernel");
+      }
       return NRPN_OK;
     };
     auto hl = [&](int i) { return kept.h + (int64_t)i * l.rows * kW; };
@@ -627,20 +928,20 @@ int backward(const QueryCall &c, const float *packed_t, const float *draw, float
     if (int rc = wgrad({ho.dyhead, kHeadCols, kHeadCols, hl(7), kW, kW, 3, 1, kW, gl.w_alpha, kW, gl.b_alpha})) return rc;
     // views_linears.0: the feature columns, then the view and camera columns
     const int ldw = kW + m.ldv();
-    if (int rc = wgrad({ho.dv, kHalf, kHalf, kept.f, kW, kW, 0, kHalf, kW, gl.w_views, ldw, gl.b_views})) return rc;
+    if (int rc = wgrad({ho.dv, kHalf, kHalf, kept.f, kW, kW, 0, kHalf, kW, gl.w_views, ldw, gl.b_views, true})) return rc;
     if (m.ldv() > 0)
       if (int rc = wgrad({ho.dv, kHalf, kHalf, ho.xvp, kv, kv, 0, kHalf, m.ldv(), gl.w_views + kW, ldw, -1})) return rc;
     if (int rc = dgrad(ho.dv, kHalf, kOffTf, false, nullptr, kept.f)) return rc;                          // df
-    if (int rc = wgrad({kept.f, kW, kW, hl(7), kW, kW, 0, kW, kW, gl.w_feat, kW, gl.b_feat})) return rc;
+    if (int rc = wgrad({kept.f, kW, kW, hl(7), kW, kW, 0, kW, kW, gl.w_feat, kW, gl.b_feat, true})) return rc;
     if (int rc = dgrad(kept.f, kW, 7 * kSzT, true, hl(7), hl(7))) return rc;                              // dy_7
     for (int i = kLayers - 1; i >= 1; --i) {
       const int ldi = i == kSkipLayer ? in_ch + kW : kW, hoff = i == kSkipLayer ? in_ch : 0;
-      if (int rc = wgrad({hl(i), kW, kW, hl(i - 1), kW, kW, 0, kW, kW, gl.w_pts[i] + hoff, ldi, gl.b_pts[i]})) return rc;
+      if (int rc = wgrad({hl(i), kW, kW, hl(i - 1), kW, kW, 0, kW, kW, gl.w_pts[i] + hoff, ldi, gl.b_pts[i], true})) return rc;
       if (i == kSkipLayer)
-        if (int rc = wgrad({hl(i), kW, kW, kept.enc, kEnc, kEnc, 0, kW, in_ch, gl.w_pts[i], ldi, -1})) return rc;
+        if (int rc = wgrad({hl(i), kW, kW, kept.enc, kEnc, kEnc, 0, kW, in_ch, gl.w_pts[i], ldi, -1, true})) return rc;
       if (int rc = dgrad(hl(i), kW, (int64_t)(i - 1) * kSzT, false, hl(i - 1), hl(i - 1))) return rc;   // dy_{i-1}
     }
-    if (int rc = wgrad({hl(0), kW, kW, kept.enc, kEnc, kEnc, 0, kW, in_ch, gl.w_pts[0], in_ch, gl.b_pts[0]})) return rc;
+    if (int rc = wgrad({hl(0), kW, kW, kept.enc, kEnc, kEnc, 0, kW, in_ch, gl.w_pts[0], in_ch, gl.b_pts[0], true})) return rc;
   }
   nerfquery_finish_kernel<<<(unsigned)cdiv64(gl.total, 256), 256, 0, c.stream>>>(gacc, gl.total, gl.cam, gl.b_views, c.w_view, m.views_ch(),
                                                                                  m.cam_ch, grads);
@@ -655,7 +956,7 @@ extern "C" {
 int64_t nrpn_nerfquery_work_bytes(int what, int64_t num_rays, int num_samples, int64_t chunk, int multires, int multires_views,
                                   int input_ch_cam) {
   const Model m{multires, multires_views, input_ch_cam};
-  if (what == 2) return kPackedTFloats * 4;
+  if (what == 2 || what == 5) return kPackedTFloats * 4;       // floats, or a hi and a lo bf16 of each
   if (what == 4) return 4 * (int64_t)(kEnc + kLayers * kW + kW + 3 * kHalf + kHeadCols + (model_ok(m) ? m.kv() : 0));
   if (!model_ok(m) || !sizes_ok(num_rays, num_samples, chunk)) return -1;
   if (what == 3) return grad_layout(m).total;
@@ -667,15 +968,17 @@ int64_t nrpn_nerfquery_work_bytes(int what, int64_t num_rays, int num_samples, i
 int nrpn_nerfquery_pack_t(const float *raw, int input_ch, float *packed_t, nrpn_stream_t stream) {
   NRPN_REQUIRE(raw && packed_t, "nerfquery_pack_t: null pointer");
   NRPN_REQUIRE(input_ch >= 3 && input_ch <= kEnc, "nerfquery_pack_t: input_ch %d outside 3 .. %d", input_ch, kEnc);
-  PackTPlan plan{};
-  int64_t src = (int64_t)kW * input_ch;                       // after pts_linears.0
-  for (int i = 1; i <= 9; ++i) {                              // raw order: pts_linears 1 .. 7, feature_linear, W_f
-    const int ld = i == kSkipLayer ? input_ch + kW : kW, K = i == 9 ? kHalf : kW;
-    plan.seg[i - 1] = PackTSeg{(int64_t)(i - 1) * kSzT, src, ld, i == kSkipLayer ? input_ch : 0, K};
-    src += (int64_t)K * ld;
-  }
-  nerfquery_pack_t_kernel<<<dim3(64, 9), 256, 0, as_stream(stream)>>>(raw, packed_t, plan);
+  nerfquery_pack_t_kernel<<<dim3(64, 9), 256, 0, as_stream(stream)>>>(raw, packed_t, pack_t_plan(input_ch));
   NRPN_LAUNCH_CHECK("nerfquery_pack_t_kernel");
+  return NRPN_OK;
+}
+
+int nrpn_nerfquery_pack_t_bf16x3(const float *raw, int input_ch, void *planes_t, nrpn_stream_t stream) {
+  NRPN_REQUIRE(raw && planes_t, "nerfquery_pack_t_bf16x3: null pointer");
+  NRPN_REQUIRE(input_ch >= 3 && input_ch <= kEnc, "nerfquery_pack_t_bf16x3: input_ch %d outside 3 .. %d", input_ch, kEnc);
+  nerfquery_pack_t_split_kernel<<<dim3(64, 9), 256, 0, as_stream(stream)>>>(raw, static_cast<unsigned short *>(planes_t),
+                                                                           pack_t_plan(input_ch));
+  NRPN_LAUNCH_CHECK("nerfquery_pack_t_split_kernel");
   return NRPN_OK;
 }
 
@@ -719,6 +1022,17 @@ int nrpn_nerfquery_backward_bf16x3(const float *pts, const float *viewdirs, int6
               Model{multires, multires_views, input_ch_cam}, viewdirs, packed, w_view, b_view, embedded_cam, num_rays, chunk, work,
               work_bytes, as_stream(stream), static_cast<const uint4 *>(split)};
   return backward<true>(c, packed_t, draw, grads);
+}
+
+int nrpn_nerfquery_backward_bf16x3_split(const float *pts, const float *viewdirs, int64_t num_rays, int num_samples, float center_x,
+                                         float center_y, float center_z, float bb_scale, int multires, int multires_views,
+                                         int input_ch_cam, const float *packed, const void *split, const void *split_t,
+                                         const float *w_view, const float *b_view, const float *embedded_cam, const float *draw,
+                                         int64_t chunk, void *work, int64_t work_bytes, float *grads, nrpn_stream_t stream) {
+  QueryCall c{Points{pts, num_rays * num_samples, num_samples, center_x, center_y, center_z, bb_scale},
+              Model{multires, multires_views, input_ch_cam}, viewdirs, packed, w_view, b_view, embedded_cam, num_rays, chunk, work,
+              work_bytes, as_stream(stream), static_cast<const uint4 *>(split), static_cast<const uint4 *>(split_t)};
+  return backward<true, true>(c, nullptr, draw, grads);
 }
 
 }  // extern "C"

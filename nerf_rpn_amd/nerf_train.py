@@ -139,7 +139,8 @@ def train(run, args, rand=None):
     [N, 4, 4], intrinsics [N, 4], near, far, bb_center [3], bb_scale -- the training views, float32 tensors that are moved to the
     device once; optionally state_dict (a network_fn_state_dict) and embedcam [N, input_ch_cam] to start from.  args: the flags of
     scripts/nerf_train.py; args.dtype ("fp32" when absent, or "bf16x3") is the arithmetic of the trunk in every query of a step, forward
-    and backward.  The seeds are the reference's (:756-758) -- the streams are not: torch's
+    and backward; args.backward_dtype ("fp32" when absent, or "bf16x3" beside dtype "bf16x3") that of the backward's own products
+    (DESIGN.md 3.24).  The seeds are the reference's (:756-758) -- the streams are not: torch's
     generator here is the device's Philox stream of this build, numpy's is numpy's.
 
     Per step: np.random.choice over the views, N_rand pixels without replacement (np.random.choice(H W, N_rand, replace=False), the
@@ -159,7 +160,7 @@ def train(run, args, rand=None):
     gen = torch.Generator(device=dev)
     gen.manual_seed(0)
     # ops.nerf_grid_config raises for an option the kernels do not cover; args.dtype: the arithmetic of the trunk
-    model = NeRF(dict(vars(args)), dtype=getattr(args, "dtype", "fp32")).to(dev)
+    model = NeRF(dict(vars(args)), dtype=getattr(args, "dtype", "fp32"), backward_dtype=getattr(args, "backward_dtype", "fp32")).to(dev)
     params = list(model.parameters())
     optimizer = torch.optim.Adam(params=params, lr=args.lrate, betas=(0.9, 0.999))
     n_views = int(run.images.shape[0])

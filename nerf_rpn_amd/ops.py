@@ -2450,6 +2450,16 @@ def nerf_check_dtype(dtype):
     return dtype
 
 
+def nerf_check_backward_dtype(dtype, backward_dtype):
+    """``backward_dtype`` if it names an arithmetic of the query's backward products that goes with the forward's ``dtype``: "fp32"
+    with either, "bf16x3" with "bf16x3" only; ValueError otherwise."""
+    if backward_dtype not in NERF_DTYPES:
+        raise ValueError(f"backward_dtype {backward_dtype!r}: expected 'fp32' or 'bf16x3'")
+    if backward_dtype == "bf16x3" and dtype != "bf16x3":
+        raise ValueError(f"backward_dtype 'bf16x3' goes with dtype 'bf16x3' only, not with dtype {dtype!r}")
+    return backward_dtype
+
+
 def nerf_grid_config(cfg):
     """The options of the training run's args.json (a dict or a namespace) that decide the network -> dict(multires, multires_views,
     input_ch_cam).  Supported is what run_nerf.py's config_parser defaults to (run_nerf.py:924-1008): netdepth 8, netwidth 256, multires
@@ -2904,12 +2914,12 @@ NERF_QUERY_PARAMS = tuple([f"pts_linears.{i}.weight" for i in range(8)]
 
 class NerfQueryFn(torch.autograd.Function):
     """run_network (run_nerf.py:50-65) and its backward on the GPU (csrc/nerfquery.hip).  forward(pts [R, S, 3], viewdirs [R, 3], cam
-    [input_ch_cam], cfg, bounds, chunk, dtype, *params): params are the 24 tensors in NERF_QUERY_PARAMS order -> raw [R, S, 4].
-    Nothing but the inputs is kept for the backward: it runs the forward again, chunk by chunk, into the scratch, in the arithmetic
-    ``dtype`` of the forward."""
+    [input_ch_cam], cfg, bounds, chunk, dtype, backward_dtype, *params): params are the 24 tensors in NERF_QUERY_PARAMS order -> raw
+    [R, S, 4].  Nothing but the inputs is kept for the backward: it runs the forward again, chunk by chunk, into the scratch, in the
+    arithmetic ``dtype`` of the forward; its own products run in ``backward_dtype``."""
 
     @staticmethod
-    def forward(ctx, pts, viewdirs, cam, cfg, bounds, chunk, dtype, *params):
+    def forward(ctx, pts, viewdirs, cam, cfg, bounds, chunk, dtype, backward_dtype, *params):
         c = nerf_grid_config(cfg)
         weights = nerf_grid_pack(dict(zip(NERF_QUERY_PARAMS, params)), cfg, dtype)
         R, S = int(pts.shape[0]), int(pts.shape[1])
@@ -2925,6 +2935,7 @@ class NerfQueryFn(torch.autograd.Function):
              _p(raw), _s())
         ctx.save_for_backward(pts, viewdirs, cam)
         ctx.weights, ctx.size, ctx.bounds, ctx.shapes = weights, size, bounds, [tuple(p.shape) for p in params]
+        ctx.backward_dtype = backward_dtype
         return raw
 
     @staticmethod
@@ -2934,14 +2945,20 @@ class NerfQueryFn(torch.autograd.Function):
         weights, size = ctx.weights, ctx.size
         R, S, chunk, multires, multires_views, cam_ch = size
         dev = pts.device
-        packed_t = torch.empty(lib.query("nerfquery_work_bytes", 2, *size) // 4, dtype=torch.float32, device=dev)
-        call("nerfquery_pack_t", _p(weights.raw), 3 + 6 * multires, _p(packed_t), _s())
+        if ctx.backward_dtype == "bf16x3":      # the planes of the transposes take packed_t's place
+            packed_t = torch.empty(lib.query("nerfquery_work_bytes", 5, *size) // 2, dtype=torch.bfloat16, device=dev)
+            call("nerfquery_pack_t_bf16x3", _p(weights.raw), 3 + 6 * multires, _p(packed_t), _s())
+        else:
+            packed_t = torch.empty(lib.query("nerfquery_work_bytes", 2, *size) // 4, dtype=torch.float32, device=dev)
+            call("nerfquery_pack_t", _p(weights.raw), 3 + 6 * multires, _p(packed_t), _s())
         nbytes = lib.query("nerfquery_work_bytes", 1, *size)
         work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         grads = torch.empty(lib.query("nerfquery_work_bytes", 3, *size), dtype=torch.float32, device=dev)
         draw = draw.to(torch.float32).contiguous()
         name, head = weights.entry("nerfquery_backward", _p(pts), _p(viewdirs), R, S, *ctx.bounds, multires, multires_views, cam_ch,
                                    _p(weights.packed))
+        if ctx.backward_dtype == "bf16x3":
+            name += "_split"
         call(name, *head, _p(packed_t), _p(weights.w_view), _p(weights.b_views), _p(cam) if cam_ch else None, _p(draw), chunk, _p(work), nbytes,
              _p(grads), _s())
         out, at = [], 0
@@ -2950,10 +2967,11 @@ class NerfQueryFn(torch.autograd.Function):
             out.append(grads[at:at + n].view(shape))
             at += n
         dcam = grads[at:at + cam_ch]
-        return (None, None, dcam, None, None, None, None, *out)
+        return (None, None, dcam, None, None, None, None, None, *out)
 
 
-def nerf_query(params, cfg, pts, viewdirs, embedded_cam=None, bb_center=(0., 0., 0.), bb_scale=1., chunk=None, dtype="fp32"):
+def nerf_query(params, cfg, pts, viewdirs, embedded_cam=None, bb_center=(0., 0., 0.), bb_scale=1., chunk=None, dtype="fp32",
+               backward_dtype="fp32"):
     """network_query_fn(pts, viewdirs, embedded_cam, network_fn) of the reference (run_network, run_nerf.py:50-65) for the NeRF MLP of
     DESIGN.md 3.16, differentiable with respect to the network's 24 parameter tensors and to embedded_cam.
 
@@ -2971,8 +2989,12 @@ def nerf_query(params, cfg, pts, viewdirs, embedded_cam=None, bb_center=(0., 0.,
     fixed-order sums); for different chunks they differ in rounding only.
 
     dtype "bf16x3": the trunk's matrix products, in the forward and in the backward's re-run of it, use the split arithmetic of
-    DESIGN.md 3.23; the backward's own products stay exact fp32 on the activations that forward produced."""
+    DESIGN.md 3.23; the backward's own products stay exact fp32 on the activations that forward produced -- unless backward_dtype is
+    "bf16x3" too (accepted with dtype "bf16x3" only; ValueError otherwise): then the dgrads and the weight gradients of the trunk's ten
+    matrices use the same split arithmetic.  raw, the gradients of rgb_linear, alpha_linear and views_linears.0.bias
+    and embedded_cam's do not depend on backward_dtype, bit for bit."""
     nerf_check_dtype(dtype)
+    nerf_check_backward_dtype(dtype, backward_dtype)
     c = nerf_grid_config(cfg)
     if not torch.cuda.is_available():
         raise lib.NrpnError("nerf_query needs a gfx950 device (the product path has no CPU fallback)")
@@ -3003,7 +3025,8 @@ def nerf_query(params, cfg, pts, viewdirs, embedded_cam=None, bb_center=(0., 0.,
     chunk = NERF_QUERY_DEFAULT_CHUNK if chunk is None else int(chunk)
     if chunk < 1:
         raise lib.NrpnError(f"nerf_query: chunk {chunk}")
-    return NerfQueryFn.apply(pts, viewdirs, cam, cfg, _nerf_bounds(bb_center, bb_scale), chunk, dtype, *(sd[k] for k in NERF_QUERY_PARAMS))
+    return NerfQueryFn.apply(pts, viewdirs, cam, cfg, _nerf_bounds(bb_center, bb_scale), chunk, dtype, backward_dtype,
+                             *(sd[k] for k in NERF_QUERY_PARAMS))
 
 
 # ======================================================================================================================

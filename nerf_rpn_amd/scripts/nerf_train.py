@@ -7,7 +7,8 @@ plus the flags of config_parser (:924-1008) that the train task reads, with its 
 --i_print --i_weights --chunk``; ``--near --far --bb_center --bb_scale`` as in nerf_render; ``--N_iters`` (default 500001, which the
 reference hard-codes), ``--depth_std`` (metres) and ``--dtype fp32|bf16x3`` (default fp32: the arithmetic of the MLP trunk in every step
 and in the evaluation at the end; it is written to args.json, the checkpoints are float32 with the same keys either
-way).  An option ops.nerf_grid_config rejects (netdepth, netwidth, multires, i_embed,
+way) and ``--backward_dtype fp32|bf16x3`` (default fp32: the arithmetic of the backward's own matrix products, DESIGN.md 3.24;
+bf16x3 is refused without ``--dtype bf16x3``; written to args.json too).  An option ops.nerf_grid_config rejects (netdepth, netwidth, multires, i_embed,
 N_importance, use_viewdirs) raises as in every NeRF tool here.
 
 Data: ``<data_dir>/<scene_id>/transforms_train.json`` with nerf_extract's keys; the images and depths of its frames as nerf_test
@@ -61,6 +62,8 @@ def build_parser():
     p.add_argument('--depth_std', type=float, default=None, help='standard deviation of the depth prior in metres, without a std file')
     p.add_argument('--dtype', choices=('fp32', 'bf16x3'), default='fp32',
                    help='arithmetic of the MLP trunk: exact fp32, or three bf16 MFMA products of split operands (DESIGN.md 3.23)')
+    p.add_argument('--backward_dtype', choices=('fp32', 'bf16x3'), default='fp32',
+                   help='arithmetic of the dgrad and weight-gradient products of the trunk; bf16x3 needs --dtype bf16x3 (DESIGN.md 3.24)')
     return p
 
 
@@ -118,7 +121,10 @@ def load_scene(args):
 
 def main(argv=None):
     from nerf_rpn_amd import nerf_train, ops
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.backward_dtype == 'bf16x3' and args.dtype != 'bf16x3':
+        parser.error('--backward_dtype bf16x3 needs --dtype bf16x3')
     ops.nerf_grid_config(args)           # unsupported options stop here, before any file is read
     if args.expname is None:             # run_nerf :1020-1021
         args.expname = '{}_{}'.format(datetime.datetime.fromtimestamp(time.time()).strftime('%Y%m%d_%H%M%S'), args.scene_id)

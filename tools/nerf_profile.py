@@ -17,6 +17,21 @@ def timed(fn, repeats):
     return best
 
 
+def window_times(fn, repeats):
+    """HIP-event times in ms of ``repeats`` calls of fn after a warm-up call, in the order measured."""
+    fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(repeats):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b))
+    return out
+
+
 def kernel_times(fn, kernels):
     """Device time in ms per kernel family (a substring of the kernel's name) of one call of fn, from torch.profiler; None if the
     profiler records nothing of the first family."""
