@@ -1,5 +1,6 @@
 """GPU parity: RPN post-processing / target-assignment kernels vs the golden vectors (reference outputs) and the oracle.
-Integer outputs (sort order, keep indices, labels, anchors) must be bit-exact; IoU / boxes within the stated tolerance."""
+Integer outputs (sort order, keep indices, labels, anchors) must be bit-exact; IoU / boxes within the stated tolerance.
+The coder, filter, select, matcher and sampled-loss kernels are held to float64 references with derived bounds in tests/test_gpu_rpn_kernels.py."""
 import numpy as np
 import pytest
 import torch

@@ -3,7 +3,8 @@ VGG19-EF + FPN + RPN, OBB, --normalize_density): the fixture `stages_obb_160_cfg
 reference's raw logits of all 950 625 anchors, its per-level top-k indices, the deltas / decoded boxes of those candidates, the
 candidates that reach batched_nms, its keep indices and the final proposals (reference rpn.py:292-370, utils.py:215-265).  Each HIP
 stage is fed the reference's OWN tensors and must return equal indices / keep masks (north_star: "anchor indices / NMS keep-masks
-bit-exact"), boxes within 1e-4."""
+bit-exact"), boxes within 1e-4.
+Per-element float64 bounds of the same decode / filter / select kernels: tests/test_gpu_rpn_kernels.py."""
 import numpy as np
 import pytest
 import torch
