@@ -6,6 +6,8 @@
 #ifndef NERFRPN_TOOLS_H
 #define NERFRPN_TOOLS_H
 #include "nerfrpn.h"
+/* in-kernel phase stamps of the K-sliced conv launches: the stamped conv3d forward entry and its layout query, the record's word order */
+#include "nerfrpn_stamps.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -11,6 +11,7 @@
 // issued before the current step's MFMAs so HBM/L2 latency hides under the matrix work.
 //
 // Replaces torch.nn.Conv3d (MIOpen/cuDNN) in reference feature_extractor.py:331-358, fpn.py:109-110, anchor.py:190-198.
+#include "conv_stamp.cuh"
 #include "conv_common.cuh"
 #include "conv_plan.h"
 
@@ -24,8 +25,37 @@
 
 // ROWS (MODE 0): row-list form -- tile row v is voxel p.rows[2 v] of the ragged space with tap word p.rows[2 v + 1] (csrc/cone.hip); the
 // output (and the optional ReLU mask) row is that voxel.  The dense instantiations carry none of it.
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Stamped twins (tools only: nrpn_conv3d_fwd_stamped, include/nerfrpn_stamps.h).  Three kernels of this file -- conv_igemm_kernel,
+// conv_igemm_big_kernel and splitk_epilogue_kernel, the ones between NRPN_K(...) heads -- are compiled TWICE from this one text: the file
+// includes itself once (below splitk_epilogue_kernel) with NRPN_STAMP_PASS defined, and in that second pass everything but those three is
+// skipped and they come out as *_stamped_kernel with one more argument (the record buffer) and the clock reads of conv_stamp.cuh at
+// their phase boundaries.  In the first pass `stamps` is an empty object whose members compile to nothing: the product kernels keep
+// their names, their arguments and, instruction for instruction, their code.  Two thin wrappers around a shared
+// __forceinline__ body would have been plainer, and were tried: they changed the code of 61 of this file's 96 device functions.
+// ---------------------------------------------------------------------------------------------------------------------
+#undef NRPN_K
+#undef NRPN_STAMPED
+#undef NRPN_STAMP_PARAM
+#undef NRPN_STAMP_BUF
+#ifdef NRPN_STAMP_PASS
+#define NRPN_STAMPED true
+#define NRPN_K(name) name##_stamped_kernel
+#define NRPN_STAMP_PARAM , stamp_t *stamp_buf
+#define NRPN_STAMP_BUF stamp_buf
+#else
+#define NRPN_STAMPED false
+#define NRPN_K(name) name##_kernel
+#define NRPN_STAMP_PARAM
+#define NRPN_STAMP_BUF ((stamp_t *)nullptr)
+#endif
+
+// second pass: instantiated for bf16, MODE 0, LDS-DMA, the 128-byte K-step and dense rows only
 template <typename T, int BN, int MODE, bool OUTF32, int KB, bool GLDS, int BM = 128, bool ROWS = false>
-__global__ void __launch_bounds__(256, BM == 128 ? 2 : 1) conv_igemm_kernel(const ConvArgs p) {
+__global__ void __launch_bounds__(256, BM == 128 ? 2 : 1) NRPN_K(conv_igemm)(const ConvArgs p NRPN_STAMP_PARAM) {
+  Stamps<NRPN_STAMPED> stamps(NRPN_STAMP_BUF, blockIdx.x, NRPN_STAMP_KERNEL_CONV128);
+  stamps.template mark<NRPN_SP_ENTRY>();
   constexpr int WAVES_N = (BN == 128) ? 2 : 1;
   constexpr int TM = BM / (32 * (4 / WAVES_N));   // 32x32 tiles per wave along M: 1, 2 or (BM 256) 4
   constexpr int TN = 2;                            // ... along N
@@ -275,6 +305,7 @@ __global__ void __launch_bounds__(256, BM == 128 ? 2 : 1) conv_igemm_kernel(cons
     }
   };
 
+  stamps.template mark<NRPN_SP_PROLOGUE_END>();
   // Software pipeline: while step k is multiplied out of LDS buffer k&1, the loads of step k+1 are in flight into the
   // staging registers and are written to the other buffer after the MFMAs.  The loop is unrolled by two so both LDS
   // buffers are compile-time constants (immediate ds offsets, no address arithmetic in the loop).
@@ -283,19 +314,26 @@ __global__ void __launch_bounds__(256, BM == 128 ? 2 : 1) conv_igemm_kernel(cons
     // 2-buffer LDS-DMA pipeline: the DMA of step k+1 flies while step k is multiplied; __syncthreads() carries the vmcnt(0)
     issue_glds(0);
     __syncthreads();
+    stamps.template mark<NRPN_SP_FIRST_TILE>();
     // pairs of K-steps with ONE exit at the top of the loop (an exit in the middle made the compiler keep the accumulators in two register
     // sets and copy all 64 of them once per pair: 32 v_mov_b64 + s_nop bubbles behind the MFMAs, tools/isa_audit.py); the odd last step follows
     for (; ks + 1 < ks_end; ks += 2) {
       issue_glds(1);
       compute_step(0);
+      stamps.step_wait_begin();
       __syncthreads();
+      stamps.step_wait_end();
       if (ks + 2 < ks_end) issue_glds(0);
       compute_step(1);
+      stamps.step_wait_begin();
       __syncthreads();
+      stamps.step_wait_end();
     }
     if (ks < ks_end) {
       compute_step(0);
+      stamps.step_wait_begin();
       __syncthreads();
+      stamps.step_wait_end();
     }
   } else {
     load_step(ks_begin, ra0, rb0);
@@ -316,6 +354,7 @@ __global__ void __launch_bounds__(256, BM == 128 ? 2 : 1) conv_igemm_kernel(cons
       __syncthreads();
     }
   }
+  stamps.template mark<NRPN_SP_LOOP_END>();
 
   if (my_ks > 1) {   // fp32 partial of this K slice, plain stores (deterministic); the slices are summed in order, then bias /
                      // ReLU / cast, by splitk_epilogue_kernel / rows_epilogue_kernel
@@ -332,6 +371,7 @@ __global__ void __launch_bounds__(256, BM == 128 ? 2 : 1) conv_igemm_kernel(cons
           if (v < p.M) wsz[(v - part_row0) * p.Cout + col] = acc[i][j][r];
         }
     }
+    stamps.finish(tile / ntiles, tile % ntiles, zsplit);
     return;
   }
 
@@ -389,6 +429,7 @@ __global__ void __launch_bounds__(256, BM == 128 ? 2 : 1) conv_igemm_kernel(cons
         *reinterpret_cast<f4 *>(yp + v * p.Cout + col) = val;
       }
     }
+    stamps.finish(tile / ntiles, tile % ntiles, zsplit);
     return;
   }
 #pragma unroll
@@ -413,8 +454,10 @@ __global__ void __launch_bounds__(256, BM == 128 ? 2 : 1) conv_igemm_kernel(cons
       }
     }
   }
+  stamps.finish(tile / ntiles, tile % ntiles, zsplit);
 }
 
+#ifndef NRPN_STAMP_PASS
 // ---------------------------------------------------------------------------------------------------------------------
 // Wave-specialised variant for the heavy bf16 shapes (k1 / k3, Cin*2 % 128 == 0, enough 256x128 tiles to fill the chip).
 // 512 threads = 8 waves, two per SIMD: waves 0-3 are CONSUMERS (each owns a 128x64 block of the 256x128 tile: 8 accumulators,
@@ -611,8 +654,11 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_ws_kernel(const ConvArgs p)
 // none of these branches): bit 0 = every tap reads the centre voxel ("ideal memory"), bit 1 = no per-K-step barrier / DMA drain.
 // RESULTS ARE WRONG with DBG != 0 (timing diagnosis, tools/diag_big_conv.py).
 // ROWS: row-list form (tile row v = voxel p.rows[2 v], tap word p.rows[2 v + 1]; outputs and the ReLU mask at that voxel), cf. conv_igemm_kernel.
+#endif      // NRPN_STAMP_PASS: the next kernel has a stamped twin (instantiated for its production forms only: DBG = 0, dense rows)
 template <bool OUTF32, bool STAG = false, int DBG = 0, bool ROWS = false>
-__global__ void __launch_bounds__(512, 1) conv_igemm_big_kernel(const ConvArgs p) {
+__global__ void __launch_bounds__(512, 1) NRPN_K(conv_igemm_big)(const ConvArgs p NRPN_STAMP_PARAM) {
+  Stamps<NRPN_STAMPED> stamps(NRPN_STAMP_BUF, blockIdx.x, NRPN_STAMP_KERNEL_CONV256);
+  stamps.template mark<NRPN_SP_ENTRY>();
   typedef bf16s T;
   constexpr int BM = 256, BN = 256, KB = 128, KE = 64, PPR = 8, RSTEP = 64, TM = 4, TN = 2;
   constexpr int A_RPT = BM / RSTEP, B_RPT = BN / RSTEP;    // 4 + 4 DMA pieces per lane per K-step
@@ -796,8 +842,10 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_big_kernel(const ConvArgs p
     }
   };
 
+  stamps.template mark<NRPN_SP_PROLOGUE_END>();
   issue(0, ks_begin < nk);
   __syncthreads();
+  stamps.template mark<NRPN_SP_FIRST_TILE>();
   if constexpr (STAG) {
     // Rotated pipeline: the barrier that hands over the next buffer sits BEFORE the MFMAs of the last sub-step instead of after them.
     // The fragments of sub-step 3 are in registers by then, so its 8 MFMAs run while the ds_reads of the next K-step's sub-step 0 are in
@@ -818,7 +866,9 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_big_kernel(const ConvArgs p
         if (sub < 3) {
           load_frags(A, B, sub + 1, af[(sub + 1) & 1], bfv[(sub + 1) & 1]);
         } else {
+          stamps.step_wait_begin();
           if constexpr (!dbg_nosync) __syncthreads();
+          stamps.step_wait_end();
           load_frags(An, An + A_BYTES, 0, af[0], bfv[0]);
         }
         if (sub < 2 && (sub == 1) == late_issue) issue(buf ^ 1, next_live);
@@ -838,9 +888,12 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_big_kernel(const ConvArgs p
 #pragma unroll 1
     for (int ks = ks_begin; ks < nk; ++ks) {
       compute((ks - ks_begin) & 1, ks + 1 < nk);
+      stamps.step_wait_begin();
       if constexpr (!dbg_nosync) __syncthreads();
+      stamps.step_wait_end();
     }
   }
+  stamps.template mark<NRPN_SP_LOOP_END>();
 
   const bool has_bias = (p.flags & NRPN_CONV_BIAS) && p.bias;
   const bool relu = p.flags & NRPN_CONV_RELU;
@@ -861,6 +914,7 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_big_kernel(const ConvArgs p
           if (v < p.M) wsz[(v - part_row0) * p.Cout + col] = acc[i][j][r];
         }
     }
+    stamps.finish(tile / ntiles, tile % ntiles, zsplit);
     return;
   }
   if (!OUTF32 && (p.Cout & 7) == 0) {
@@ -927,6 +981,7 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_big_kernel(const ConvArgs p
       for (int j = 0; j < TN; ++j)
         store_col_stats(p.stats, (m0 / BM) * 2 + wm, p.Cout, n0 + (wn * TN + j) * 32 + efr, ssum[j], qsum[j], elane);
     }
+    stamps.finish(tile / ntiles, tile % ntiles, zsplit);
     return;
   }
 #pragma unroll
@@ -951,8 +1006,10 @@ __global__ void __launch_bounds__(512, 1) conv_igemm_big_kernel(const ConvArgs p
       }
     }
   }
+  stamps.finish(tile / ntiles, tile % ntiles, zsplit);
 }
 
+#ifndef NRPN_STAMP_PASS
 // ---------------------------------------------------------------------------------------------------------------------
 // 256x256 tile on FOUR waves (2 x 2, each 128x128 = 16 accumulators = 256 accumulator registers; one wave per SIMD, 512 registers).
 // Per MFMA this is 0.5 ds_read_b128 instead of the 0.75 of the 8-wave kernel (a third less LDS read traffic and energy -- the part is
@@ -1228,12 +1285,32 @@ __global__ void __launch_bounds__(256, 1) conv_igemm_big4_kernel(const ConvArgs 
 // conv_halo.hip: the "halo" form of the 3x3x3 implicit GEMM (4 x 8 x 8 voxel blocks, input halo staged once per channel chunk)
 int nrpn_launch_conv_halo(const ConvArgs &a, unsigned workgroups, hipStream_t st, int variant);
 
+#endif      // NRPN_STAMP_PASS: the next kernel has a stamped twin (instantiated for bf16)
+// Second pass (splitk_epilogue_stamped_kernel): wave 0 of the workgroup stamps entry, "the partials of its first element are back"
+// (a vmcnt(0) wait the product kernel does not have, first iteration only), last store issued, stores complete and exit, and lane 0
+// writes the record (include/nerfrpn_stamps.h).  The product kernel carries none of it.
 template <typename T, bool OUTF32>
-__global__ void splitk_epilogue_kernel(const float *__restrict__ ws, const float *__restrict__ bias, void *__restrict__ y, long long total,
-                                       int cout, int relu, int nslices, const T *__restrict__ mask, const float *__restrict__ scale) {
+__global__ void NRPN_K(splitk_epilogue)(const float *__restrict__ ws, const float *__restrict__ bias, void *__restrict__ y, long long total,
+                                        int cout, int relu, int nslices, const T *__restrict__ mask,
+                                        const float *__restrict__ scale NRPN_STAMP_PARAM) {
+  constexpr bool STAMP = NRPN_STAMPED;
+  stamp_t rt[NRPN_SE_PHASES] = {}, cy[NRPN_SE_PHASES] = {};
+  unsigned iters = 0;
+  bool w0 = false;
+  if constexpr (STAMP) {
+    w0 = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == 0;
+    if (w0) stamp_read(rt[NRPN_SE_ENTRY], cy[NRPN_SE_ENTRY]);
+  }
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
     float o = ws[i];
     for (int z = 1; z < nslices; ++z) o += ws[z * total + i];
+    if constexpr (STAMP) {
+      if (w0 && iters == 0) {
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(o) : : "memory");      // o: the slice sum is complete before the wait
+        stamp_read(rt[NRPN_SE_FIRST_LOADS], cy[NRPN_SE_FIRST_LOADS]);
+      }
+      ++iters;
+    }
     if (scale) o *= scale[i % cout];
     o += bias ? bias[i % cout] : 0.f;
     if (relu) o = fmaxf(o, 0.f);
@@ -1241,7 +1318,35 @@ __global__ void splitk_epilogue_kernel(const float *__restrict__ ws, const float
     if (OUTF32) reinterpret_cast<float *>(y)[i] = o;
     else elem<T>::st(reinterpret_cast<T *>(y) + i, o);
   }
+  if constexpr (STAMP) {
+    if (w0) {
+      stamp_read(rt[NRPN_SE_LAST_STORE], cy[NRPN_SE_LAST_STORE]);
+      asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
+      stamp_read(rt[NRPN_SE_STORES_DONE], cy[NRPN_SE_STORES_DONE]);
+      stamp_read(rt[NRPN_SE_EXIT], cy[NRPN_SE_EXIT]);
+      unsigned xcc;
+      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(xcc));
+      if (threadIdx.x == 0) {
+        stamp_t *rec = NRPN_STAMP_BUF + (size_t)blockIdx.x * NRPN_STAMP_WORDS;
+#pragma unroll
+        for (int q = 0; q < NRPN_STAMP_WORDS; ++q) rec[q] = 0;
+        rec[NRPN_SW_VERSION] = NRPN_STAMP_VERSION;
+        rec[NRPN_SW_KERNEL] = NRPN_STAMP_KERNEL_EPILOGUE;
+        rec[NRPN_SW_WG] = blockIdx.x;
+        rec[NRPN_SW_XCD] = xcc;
+        rec[NRPN_SW_KSTEPS] = iters;
+#pragma unroll
+        for (int q = 0; q < NRPN_SE_PHASES; ++q) { rec[NRPN_SW_PHASE0 + 2 * q] = rt[q]; rec[NRPN_SW_PHASE0 + 2 * q + 1] = cy[q]; }
+      }
+    }
+  }
 }
+
+#ifndef NRPN_STAMP_PASS
+// the second pass over this file: the stamped twins of the three kernels above (see "Stamped twins")
+#define NRPN_STAMP_PASS
+#include "conv3d.hip"
+#undef NRPN_STAMP_PASS
 
 // the same for the row-list form: partial row r belongs to voxel rows[2 r]; bias / ReLU / ReLU mask / store at that voxel's row of y
 template <typename T, bool OUTF32>
@@ -1382,9 +1487,119 @@ extern "C" int nrpn_conv3d_fwd_stats_rows_ex(int n, int gx, int gy, int gz, int 
   return fwd_query(n, gx, gy, gz, cin, cout, ksize, dtype, opts).stats_rows;
 }
 
+// workgroups of the split-K epilogue launch over `total` output elements
+static inline int splitk_epilogue_blocks(long long total, bool tail) { return (int)min((long long)(tail ? 2048 : 4096), (total + 255) / 256); }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Phase stamps (tools only: nrpn_conv3d_fwd_stamped, include/nerfrpn_stamps.h).  Only that entry passes a StampReq to conv3d_fwd_impl;
+// no flag, option or environment variable of the product entries reaches a stamped instantiation.
+// ---------------------------------------------------------------------------------------------------------------------
+struct StampReq { uint64_t *buf; size_t bytes; };
+// nullptr, or why this plan has no stamped form
+static const char *stamp_unsupported(const ConvShape &s, const Knobs &kn, const FwdPlan &pl, bool stats) {
+  if (s.ragged) return "ragged voxel lists";
+  if (s.elem_bytes != 2) return "fp32";
+  if (stats) return "fused statistics";
+  if (kn.dbg) return "the debug variants";
+  if (pl.code == 7) return "the halo form";
+  if (pl.kind == 4) return "the wave-specialised 256x128 tile";
+  if (pl.kind == 5) return "the 4-wave 256x256 tile";
+  if (!kn.glds) return "register-staged loads";
+  if (pl.kb != 128) return "the 64-byte K-step";
+  if (pl.tail.ks > 1) return "the tail split";
+  return nullptr;
+}
+static void stamp_layout_fill(nrpn_stamp_layout &L, const ConvShape &s, const FwdPlan &pl) {
+  L = nrpn_stamp_layout{};
+  const int bm = pl.kind == 1 ? 256 : 128, bn = pl.kind == 1 ? 256 : s.cout <= 64 ? 64 : 128;
+  L.words = NRPN_STAMP_WORDS;
+  L.plan_code = pl.code;
+  L.conv_records = pl.wgs;
+  L.epilogue_records = pl.ws_slices ? splitk_epilogue_blocks((s.M - pl.ws_row0) * s.cout, false) : 0;
+  L.bytes = (L.conv_records + L.epilogue_records) * NRPN_STAMP_WORDS * 8;
+  L.m_tiles = (int)plan_cdiv(s.M, bm);
+  L.n_tiles = (s.cout + bn - 1) / bn;
+  L.k_slices = pl.ksplit > 1 ? pl.ksplit : 1;
+  L.k_steps = s.taps * (s.cin * 2 / 128);
+  const int per = (L.k_steps + L.k_slices - 1) / L.k_slices;       // the kernels' own slice bounds
+  for (int z = 0; z < L.k_slices && z < NRPN_STAMP_MAX_SLICES; ++z) L.slice_steps[z] = min(L.k_steps, (z + 1) * per) - z * per;
+}
+extern "C" int nrpn_conv3d_fwd_stamp_layout(int n, int gx, int gy, int gz, int cin, int cout, int ksize, int dtype, const nrpn_conv_opts *opts,
+                                            nrpn_stamp_layout *layout) {
+  NRPN_REQUIRE(layout, "conv3d_fwd_stamp_layout: null layout");
+  NRPN_REQUIRE(n > 0 && gx > 0 && gy > 0 && gz > 0 && cin > 0 && cout > 0 && (ksize == 1 || ksize == 3), "conv3d_fwd_stamp_layout: bad sizes");
+  NRPN_REQUIRE(dtype == NRPN_F32 || dtype == NRPN_BF16, "conv3d_fwd_stamp_layout: bad dtype %d", dtype);
+  NRPN_REQUIRE(!opts || opts->size == (int32_t)sizeof(nrpn_conv_opts), "conv3d_fwd_stamp_layout: opts->size must be sizeof(nrpn_conv_opts)");
+  NRPN_REQUIRE((cin * (dtype == NRPN_F32 ? 4 : 2)) % 64 == 0, "conv3d_fwd_stamp_layout: Cin*elemsize must be a multiple of 64 bytes (Cin=%d)", cin);
+  const ConvShape s = conv_shape(n, gx, gy, gz, cin, cout, cout, ksize, dtype);
+  const Knobs kn = resolve_knobs(opts);
+  const FwdPlan pl = fwd_plan(s, kn);
+  if (const char *why = stamp_unsupported(s, kn, pl, opts && opts->stats))
+    return nrpn_fail(NRPN_ERR_ARG, "conv3d_fwd_stamp_layout: plan code %d has no stamped form for %s", pl.code, why);
+  stamp_layout_fill(*layout, s, pl);
+  return NRPN_OK;
+}
+
+// The stamped call: conv3d_fwd_impl has filled `a` and made the plan; every refusal comes before the first launch.  Then the launches of
+// the product path in its order -- conv, and over K slices the split-K epilogue -- on the stamped twins; the epilogue's records follow the
+// conv launch's.
+static int conv3d_fwd_stamped_launch(ConvArgs a, const ConvShape &s, const Knobs &kn, const FwdPlan &pl, int flags, void *workspace, hipStream_t st,
+                                     const StampReq &req) {
+  if (const char *why = stamp_unsupported(s, kn, pl, a.stats != nullptr))
+    return nrpn_fail(NRPN_ERR_ARG, "conv3d_fwd_stamped: plan code %d has no stamped form for %s", pl.code, why);
+  nrpn_stamp_layout sl;
+  stamp_layout_fill(sl, s, pl);
+  NRPN_REQUIRE(req.buf, "conv3d_fwd_stamped: null stamp buffer");
+  NRPN_REQUIRE(req.bytes >= (size_t)sl.bytes, "conv3d_fwd_stamped: the stamp buffer holds %zu bytes, plan code %d needs %lld", req.bytes, pl.code,
+               (long long)sl.bytes);
+  const bool out_f32 = (flags & NRPN_CONV_OUT_F32) != 0;
+  stamp_t *buf = reinterpret_cast<stamp_t *>(req.buf);
+  a.ksplit = pl.ksplit; a.slices = pl.slices; a.tail_tile0 = pl.tail.tile0; a.tail_ks = pl.tail.ks;
+  if (pl.ws_slices) a.ws = reinterpret_cast<float *>(workspace);
+  const dim3 grid((unsigned)pl.wgs);
+  if (pl.kind == 0) {
+    const size_t lds = 2 * (size_t)(128 + (a.Cout <= 64 ? 64 : 128)) * 128;
+    if (a.Cout <= 64) {
+      if (out_f32) hipLaunchKernelGGL((conv_igemm_stamped_kernel<bf16s, 64, 0, true, 128, true>), grid, dim3(256), lds, st, a, buf);
+      else hipLaunchKernelGGL((conv_igemm_stamped_kernel<bf16s, 64, 0, false, 128, true>), grid, dim3(256), lds, st, a, buf);
+    } else {
+      if (out_f32) hipLaunchKernelGGL((conv_igemm_stamped_kernel<bf16s, 128, 0, true, 128, true>), grid, dim3(256), lds, st, a, buf);
+      else hipLaunchKernelGGL((conv_igemm_stamped_kernel<bf16s, 128, 0, false, 128, true>), grid, dim3(256), lds, st, a, buf);
+    }
+  } else {      // kind 1: the same three forms launch_conv picks from
+    const size_t lbig = 2 * (size_t)(256 + 256) * 128;
+    if (out_f32) {
+      NRPN_LDS((conv_igemm_big_stamped_kernel<true, false>), lbig);
+      hipLaunchKernelGGL((conv_igemm_big_stamped_kernel<true, false>), grid, dim3(512), lbig, st, a, buf);
+    } else if (!kn.stagger) {
+      NRPN_LDS((conv_igemm_big_stamped_kernel<false, false>), lbig);
+      hipLaunchKernelGGL((conv_igemm_big_stamped_kernel<false, false>), grid, dim3(512), lbig, st, a, buf);
+    } else {
+      NRPN_LDS((conv_igemm_big_stamped_kernel<false, true>), lbig);
+      hipLaunchKernelGGL((conv_igemm_big_stamped_kernel<false, true>), grid, dim3(512), lbig, st, a, buf);
+    }
+  }
+  NRPN_LAUNCH_CHECK("conv_igemm (stamped)");
+  if (!pl.ws_slices) return NRPN_OK;
+  const long long total = s.M * s.cout;      // no tail split here (stamp_unsupported): the partials cover every row
+  const int blocks = splitk_epilogue_blocks(total, false);
+  const float *b = (flags & NRPN_CONV_BIAS) ? a.bias : nullptr;
+  const int relu = (flags & NRPN_CONV_RELU) ? 1 : 0;
+  stamp_t *rec = buf + (size_t)sl.conv_records * NRPN_STAMP_WORDS;
+  if (out_f32) {
+    hipLaunchKernelGGL((splitk_epilogue_stamped_kernel<bf16s, true>), dim3(blocks), dim3(256), 0, st, a.ws, b, a.y, total, s.cout, relu, pl.ws_slices,
+                       (const bf16s *)a.mask, a.scale, rec);
+  } else {
+    hipLaunchKernelGGL((splitk_epilogue_stamped_kernel<bf16s, false>), dim3(blocks), dim3(256), 0, st, a.ws, b, a.y, total, s.cout, relu, pl.ws_slices,
+                       (const bf16s *)a.mask, a.scale, rec);
+  }
+  NRPN_LAUNCH_CHECK("splitk_epilogue (stamped)");
+  return NRPN_OK;
+}
+
 static int conv3d_fwd_impl(const void *x, const void *wp, const float *bias, const void *mask, void *y, const ConvShape &s, const Segs *segs,
                            int ksize, int dtype, int flags, void *workspace, nrpn_stream_t stream, float *stats = nullptr,
-                           const nrpn_conv_opts *opts = nullptr) {
+                           const nrpn_conv_opts *opts = nullptr, const StampReq *stamp = nullptr) {
   const int cin = s.cin, cout = s.cout, wrows = s.wrows, es = s.elem_bytes;
   NRPN_REQUIRE(ksize == 1 || ksize == 3, "conv3d_fwd: ksize must be 1 or 3 (got %d)", ksize);
   NRPN_REQUIRE(dtype == NRPN_F32 || dtype == NRPN_BF16, "conv3d_fwd: bad dtype %d", dtype);
@@ -1408,6 +1623,7 @@ static int conv3d_fwd_impl(const void *x, const void *wp, const float *bias, con
   const bool out_f32 = (flags & NRPN_CONV_OUT_F32) != 0;
   hipStream_t st = as_stream(stream);
   const FwdPlan pl = fwd_plan(s, kn, workspace != nullptr, out_f32, stats != nullptr);
+  if (stamp) return conv3d_fwd_stamped_launch(a, s, kn, pl, flags, workspace, st, *stamp);      // tools only: nrpn_conv3d_fwd_stamped
   if (pl.code == 7) {
     NRPN_REQUIRE(pl.wgs < (1ll << 31), "conv3d_fwd: too many tiles");
     return nrpn_launch_conv_halo(a, (unsigned)pl.wgs, st, pl.halo_variant);
@@ -1419,7 +1635,7 @@ static int conv3d_fwd_impl(const void *x, const void *wp, const float *bias, con
   // bias / scale / ReLU / mask / cast of the rows that ran on K slices (all of them, or the tail's), from their fp32 partials
   const bool tail = pl.tail.ks > 1;
   const long long off = pl.ws_row0 * cout, total = (s.M - pl.ws_row0) * cout;
-  const int blocks = (int)min((long long)(tail ? 2048 : 4096), (total + 255) / 256);
+  const int blocks = splitk_epilogue_blocks(total, tail);
   const float *b = (flags & NRPN_CONV_BIAS) ? bias : nullptr;
   const int relu = (flags & NRPN_CONV_RELU) ? 1 : 0;
   if (dtype == NRPN_F32) {
@@ -1471,6 +1687,23 @@ extern "C" int nrpn_conv3d_fwd_ex(const void *x, const void *wp, const float *bi
   }
   return conv3d_fwd_impl(x, wp, bias, mask, y, conv_shape(n, gx, gy, gz, cin, cout, wrows, ksize, dtype), nullptr, ksize, dtype, flags,
                          workspace, stream, stats, opts);
+}
+
+// tools only: nrpn_conv3d_fwd_ex on the stamped instantiations -- the same plan from the same inputs, the same launches in the same order
+extern "C" int nrpn_conv3d_fwd_stamped(const void *x, const void *wp, const float *bias, void *y, int n, int gx, int gy, int gz, int cin,
+                                       int cout, int wrows, int ksize, int dtype, int flags, void *workspace, const nrpn_conv_opts *opts,
+                                       nrpn_stream_t stream, uint64_t *stamps, size_t stamps_bytes) {
+  NRPN_REQUIRE(n > 0 && gx > 0 && gy > 0 && gz > 0, "conv3d_fwd_stamped: bad sizes");
+  NRPN_REQUIRE(!opts || opts->size == (int32_t)sizeof(nrpn_conv_opts), "conv3d_fwd_stamped: opts->size must be sizeof(nrpn_conv_opts)");
+  NRPN_REQUIRE(stamps, "conv3d_fwd_stamped: null stamp buffer");
+  NRPN_REQUIRE(!opts || opts->debug == 0, "conv3d_fwd_stamped: the debug variants have no stamped form (opts->debug = %d)", opts ? opts->debug : 0);
+  NRPN_REQUIRE(!(flags & ~(NRPN_CONV_BIAS | NRPN_CONV_RELU | NRPN_CONV_OUT_F32)), "conv3d_fwd_stamped: the debug variants have no stamped form (flags)");
+  NRPN_REQUIRE(!opts || !opts->stats, "conv3d_fwd_stamped: fused statistics have no stamped form");
+  const void *mask = opts ? opts->relu_mask : nullptr;
+  NRPN_REQUIRE(!mask || !(flags & NRPN_CONV_OUT_F32) || dtype == NRPN_F32, "conv3d_fwd_stamped: relu_mask needs outputs in the input dtype");
+  const StampReq req{stamps, stamps_bytes};
+  return conv3d_fwd_impl(x, wp, bias, mask, y, conv_shape(n, gx, gy, gz, cin, cout, wrows, ksize, dtype), nullptr, ksize, dtype, flags,
+                         workspace, stream, nullptr, opts, &req);
 }
 
 extern "C" int nrpn_conv3d_fwd_ragged(const void *x, const void *wp, const float *bias, void *y, int nseg, const int32_t *dims, int cin,
@@ -3002,3 +3235,4 @@ extern "C" int nrpn_unpack_stem_wgrad(const float *gw_packed, int cout, int dtyp
   NRPN_LAUNCH_CHECK("unpack_stem_wgrad");
   return NRPN_OK;
 }
+#endif      // NRPN_STAMP_PASS (opened below splitk_epilogue_kernel)

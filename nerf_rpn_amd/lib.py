@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("NRPN_LIBRARY") or os.path.join(_HERE, "libnerfrpn_hip.so")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "nerfrpn.h")
 TOOLS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "nerfrpn_tools.h")     # measurement switches (nrpn_set_*): not the boundary
+STAMPS_HEADER = os.path.join(os.path.dirname(_HERE), "include", "nerfrpn_stamps.h")   # included by the tools header: stamped conv launches
 
 F32, BF16 = 0, 1
 CONV_BIAS, CONV_RELU, CONV_OUT_F32 = 1, 2, 4
@@ -31,6 +32,19 @@ class ConvOpts(ctypes.Structure):
     def __init__(self, tile=0, lds_dma=-1, kstep_bytes=0, stagger=-1, big_split=-1, debug=0, scale=0, relu_mask=0, stats=0, halo_pairing=0):
         super().__init__(ctypes.sizeof(ConvOpts), tile, lds_dma, kstep_bytes, stagger, big_split, debug, halo_pairing, scale or None,
                          relu_mask or None, stats or None)
+
+    def ptr(self):
+        return ctypes.addressof(self)
+
+
+STAMP_MAX_SLICES = 64
+
+
+class StampLayout(ctypes.Structure):
+    """``nrpn_stamp_layout`` (include/nerfrpn_stamps.h): where the records of a stamped conv launch lie and what their ids range over."""
+    _fields_ = [("words", ctypes.c_int32), ("plan_code", ctypes.c_int32), ("conv_records", ctypes.c_int64), ("epilogue_records", ctypes.c_int64),
+                ("bytes", ctypes.c_int64), ("m_tiles", ctypes.c_int32), ("n_tiles", ctypes.c_int32), ("k_slices", ctypes.c_int32),
+                ("k_steps", ctypes.c_int32), ("slice_steps", ctypes.c_int32 * STAMP_MAX_SLICES)]
 
     def ptr(self):
         return ctypes.addressof(self)
@@ -70,9 +84,9 @@ def _ctype(decl):
     raise NrpnError(f"unmapped C type in nerfrpn.h: {decl!r}")
 
 
-def _prototypes():
+def _prototypes(headers=None):
     """Parse include/nerfrpn.h (+ the tools header) into {name: (restype, [argtypes])} so ctypes converts and checks every argument."""
-    text = open(HEADER).read() + open(TOOLS_HEADER).read()
+    text = "".join(open(h).read() for h in (headers or (HEADER, TOOLS_HEADER)))
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     protos = {}
     for ret, name, args in re.findall(r"\b(int|size_t|int64_t|const char \*)\s*(nrpn_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
@@ -92,7 +106,7 @@ def load():
         raise NrpnError(f"{SO_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                         "(there is no CPU fallback for the HIP path)")
     lib = ctypes.CDLL(SO_PATH)
-    for name, (restype, argtypes) in _prototypes().items():
+    for name, (restype, argtypes) in {**_prototypes(), **_prototypes((STAMPS_HEADER,))}.items():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib

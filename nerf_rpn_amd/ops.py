@@ -846,6 +846,41 @@ CONV_TILE = [int(_os.environ.get("NRPN_CONV_TILE", "0"))]
 CONV_HALO_PAIRING = [int(_os.environ.get("NRPN_HALO_PAIRING", "0"))]      # A/B: 0 = library default, 1 = cross-chunk tap pairing, 2 = off
 
 
+# Tools only (tools/launch_anatomy.py, nerf_rpn_amd/stamps.py): the forward launches on their stamped twins.  Nothing of the product path
+# calls these two.
+def conv3d_stamp_layout(n, gx, gy, gz, cin, cout, ksize, dtype=BF16, opts=None):
+    """nrpn_conv3d_fwd_stamp_layout as a ``stamps.Layout``; raises lib.NrpnError (naming the plan code) for a plan without a stamped form."""
+    from . import stamps
+    lay = lib.StampLayout()
+    call("conv3d_fwd_stamp_layout", n, gx, gy, gz, cin, cout, ksize, dtype, opts.ptr() if opts is not None else 0, lay.ptr())
+    return stamps.Layout(words=lay.words, plan_code=lay.plan_code, conv_records=lay.conv_records, epilogue_records=lay.epilogue_records,
+                         nbytes=lay.bytes, m_tiles=lay.m_tiles, n_tiles=lay.n_tiles, k_slices=lay.k_slices, k_steps=lay.k_steps,
+                         slice_steps=tuple(lay.slice_steps[:lay.k_slices]))
+
+
+def conv3d_fwd_stamped(x, wp, bias, cout, wrows, ksize, flags, out_dtype, opts=None):
+    """The launches of the conv3d_fwd_ex call in ``_conv_fwd`` on the stamped instantiations: same plan, same bits -> (y, records) with
+    records an int64 tensor [records, words] (conv launch first, then its split-K epilogue; decode with ``stamps.decode``).  ``opts``: a
+    lib.ConvOpts (its scale / relu_mask pointers are the caller's to keep alive)."""
+    _chk(x, wp, bias)
+    n, gx, gy, gz, cin = x.shape
+    y = torch.empty((n, gx, gy, gz, cout), dtype=out_dtype, device=x.device)
+    if out_dtype == torch.float32 and x.dtype == torch.bfloat16:
+        flags |= CONV_OUT_F32
+    if bias is not None:
+        flags |= CONV_BIAS
+    if opts is None:
+        opts = lib.ConvOpts(tile=CONV_TILE[0], halo_pairing=CONV_HALO_PAIRING[0])
+    lay = conv3d_stamp_layout(n, gx, gy, gz, cin, cout, ksize, _dt(x), opts)
+    wsb = _query_opts("conv3d_fwd_workspace_bytes_ex", opts, n, gx, gy, gz, cin, cout, ksize, _dt(x))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=x.device) if wsb else None
+    from . import stamps
+    rec = torch.full((lay.conv_records + lay.epilogue_records, lay.words), stamps.FILL_I64, dtype=torch.int64, device=x.device)
+    call("conv3d_fwd_stamped", _p(x), _p(wp), _p(bias), _p(y), n, gx, gy, gz, cin, cout, wrows, ksize, _dt(x), flags, _p(ws), opts.ptr(), _s(),
+         _p(rec), rec.numel() * 8)
+    return y, rec
+
+
 # wgrad workspace = [27-bit tap mask per voxel (k3) | per-slice bias partials]; the masks depend only on the grid, so one workspace per
 # (grid shape, stream) is kept and the masks are built once (NRPN_WGRAD_MASK_READY afterwards); the bias partials are consumed by the
 # same C call that writes them, or by the reduce_slices launch that follows it on the same stream.
