@@ -1,8 +1,18 @@
-// The 8 x 256 trunk of the NeRF MLP of DESIGN.md 3.16 on the exact-fp32 MFMA, shared by nerfgrid.hip (lattice points) and
-// nerfrender.hip (ray samples): packed-weight layout (nrpn_nerfgrid_pack), fragment loads, the k-ordered MFMA product and the body
-// of one workgroup.  A caller supplies where a tile's 64 points come from and where their sigma goes; g goes to a [column][point]
-// tile.  The arithmetic of a point does not depend on the caller, its tile or its neighbours.  trunk_body<true> is the same body with
-// the matrix products in the bf16x3 arithmetic; the default, trunk_body<false>, is the exact-fp32 code unchanged.
+// The 8 x 256 trunk of the NeRF MLP of DESIGN.md 3.16 on the exact-fp32 MFMA, shared by nerfgrid.hip (lattice points),
+// nerfrender.hip (ray samples) and nerfquery.hip (given points): packed-weight layout (nrpn_nerfgrid_pack), fragment loads, the
+// k-ordered MFMA product, the body of one workgroup, and the one kernel and the one launcher that run it.  The arithmetic of a point
+// does not depend on the caller, its tile or its neighbours.  trunk_body<true> is the same body with the matrix products in the bf16x3
+// arithmetic; the default, trunk_body<false>, is the exact-fp32 code unchanged.
+//
+// A consumer says where a tile's 64 points come from and where their sigma goes with a Tile: a small struct of values, passed to
+// trunk_kernel<kSplit, Tile> by value, with
+//   int multires;                    the L of the positional encoding (input_ch = 3 + 6 L)
+//   src(block)  -> a source:         point(i, p) gives the normalised position of point i of workgroup ``block``'s tile
+//   sink(block) -> a sink:           sigma(i, s) takes alpha_linear's output of that point; optionally keep() (see sink_keeps)
+// Both may refer to the Tile they came from, which outlives them.  g = W_f f of the tile goes to gbuf[block] as [column][point].
+// launch_trunk(tile, tiles, packed, split, gbuf, stream) is the only place that knows there are two arithmetics to launch: the
+// planes ``split`` select bf16x3, null selects fp32.  The point arithmetic of a source stays in its consumer's translation unit: the
+// three are compiled with different contraction flags (Makefile).
 #pragma once
 #include "common.h"
 
@@ -18,6 +28,23 @@ constexpr int kLd = 324;         // row stride of the LDS image in floats: 16-by
 constexpr int kLayers = 8;
 constexpr int kSkipLayer = 5;    // the layer after skip 4 reads cat([e, h])
 constexpr int kLdsBytes = kTile * kLd * 4;
+constexpr int kMaxViewsCh = 64;  // 3 + 6 multires_views <= 64 (multires_views <= 10)
+
+// the ranges of (multires, multires_views, input_ch_cam) every entry point accepts
+inline bool model_ok(int multires, int multires_views, int cam_ch) {
+  return multires >= 0 && 3 + 6 * multires <= kEnc && multires_views >= 0 && 3 + 6 * multires_views <= kMaxViewsCh && cam_ch >= 0 &&
+         cam_ch <= 65536;
+}
+
+inline int64_t align16(int64_t b) { return (b + 15) / 16 * 16; }
+
+// One (frequency l, axis a) pair of the reference's embedding [x, sin(2^0 x), cos(2^0 x), sin(2^1 x), ..] of a 3-vector, x = its
+// component a: row is the embedding's first column
+__device__ __forceinline__ void embed_freq(float *row, float x, int l, int a) {
+  const float arg = x * ldexpf(1.0f, l);
+  row[3 + 6 * l + a] = sinf(arg);
+  row[3 + 6 * l + 3 + a] = cosf(arg);
+}
 
 // packed layout, in floats (include/nerfrpn.h: nrpn_nerfgrid_pack)
 constexpr int64_t kOffL0 = 0;
@@ -205,9 +232,7 @@ __device__ __forceinline__ void trunk_body(float *act, const float *__restrict__
     }
     for (int idx = q; idx < 3 * multires; idx += 4) {
       const int l = idx / 3, a = idx - 3 * l;
-      const float arg = p[a] * ldexpf(1.0f, l);
-      row[3 + 6 * l + a] = sinf(arg);
-      row[3 + 6 * l + 3 + a] = cosf(arg);
+      embed_freq(row, p[a], l, a);
     }
   }
   __syncthreads();
@@ -285,6 +310,39 @@ __device__ __forceinline__ void trunk_body(float *act, const float *__restrict__
         *reinterpret_cast<float4 *>(gt + 32 * m + 8 * q + 4 * h) = v;
       }
   }
+}
+
+// the sink of a forward: sigma to raw [point][4]
+struct RawSink {
+  int64_t tile0, num_points;
+  float *raw;
+  __device__ __forceinline__ void sigma(int i, float s) const {
+    const int64_t pi = tile0 + i;
+    if (pi < num_points) raw[pi * 4 + 3] = s;
+  }
+};
+
+// One workgroup per tile of the launch; gbuf [tiles][128][64]
+template <bool kSplit, class Tile>
+__global__ __launch_bounds__(256) void trunk_kernel(Tile tile, const float *__restrict__ packed, const uint4 *__restrict__ split,
+                                                    float *__restrict__ gbuf) {
+  extern __shared__ __align__(16) float act[];
+  trunk_body<kSplit>(act, packed, tile.multires, 3 + 6 * tile.multires, tile.src(blockIdx.x), tile.sink(blockIdx.x),
+                     gbuf + (int64_t)blockIdx.x * (kTile * kHalf), split);
+}
+
+// split: the bf16x3 planes of packed, and the trunk runs in that arithmetic; null: in fp32
+template <class Tile>
+int launch_trunk(const Tile &tile, int tiles, const float *packed, const uint4 *split, float *gbuf, hipStream_t stream) {
+  if (split) {
+    NRPN_LDS((trunk_kernel<true, Tile>), kLdsBytes);
+    trunk_kernel<true, Tile><<<tiles, 256, kLdsBytes, stream>>>(tile, packed, split, gbuf);
+  } else {
+    NRPN_LDS((trunk_kernel<false, Tile>), kLdsBytes);
+    trunk_kernel<false, Tile><<<tiles, 256, kLdsBytes, stream>>>(tile, packed, nullptr, gbuf);
+  }
+  NRPN_LAUNCH_CHECK("nerfmlp_trunk_kernel");
+  return NRPN_OK;
 }
 
 }  // namespace nerfmlp

@@ -27,26 +27,30 @@ struct PackPlan {
   PackSeg seg[16];
 };
 
+// the value of element i of a segment's fragments, kFrag (4 floats or 8 bf16) elements to a fragment: (k-group kg, o, h, j) from i as
+// laid out above, k = 2 kFrag kg + kFrag h + j on the padded k axis
+template <int kFrag>
+__device__ __forceinline__ float pack_elem(const float *__restrict__ raw, const PackSeg &s, int64_t i) {
+  constexpr int kShift = kFrag == 4 ? 2 : 3;
+  static_assert(kFrag == 1 << kShift, "fragments of 4 or 8 elements");
+  const int j = (int)(i & (kFrag - 1)), h = (int)((i >> kShift) & 1);
+  const int64_t q = i >> (kShift + 1);
+  const int o = (int)(q % s.n_out), kg = (int)(q / s.n_out);
+  const int k = 2 * kFrag * kg + kFrag * h + j;
+  float v = 0.f;
+  if (k < s.ka_pad) {
+    if (k < s.ka) v = raw[s.src + (int64_t)o * s.ld + k];
+  } else {
+    v = raw[s.src + (int64_t)o * s.ld + s.ka + (k - s.ka_pad)];
+  }
+  return v;
+}
+
 __global__ void nerfgrid_pack_kernel(const float *__restrict__ raw, float *__restrict__ packed, PackPlan plan) {
   const PackSeg s = plan.seg[blockIdx.y];
   const int64_t total = s.n_out == 0 ? s.kb : (int64_t)(s.ka_pad + s.kb) * s.n_out;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    if (s.n_out == 0) {
-      packed[s.dst + i] = raw[s.src + i];
-      continue;
-    }
-    const int j = (int)(i & 3), h = (int)((i >> 2) & 1);
-    const int64_t q = i >> 3;
-    const int o = (int)(q % s.n_out), kg = (int)(q / s.n_out);
-    const int k = 8 * kg + 4 * h + j;
-    float v = 0.f;
-    if (k < s.ka_pad) {
-      if (k < s.ka) v = raw[s.src + (int64_t)o * s.ld + k];
-    } else {
-      v = raw[s.src + (int64_t)o * s.ld + s.ka + (k - s.ka_pad)];
-    }
-    packed[s.dst + i] = v;
-  }
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x)
+    packed[s.dst + i] = s.n_out == 0 ? raw[s.src + i] : pack_elem<4>(raw, s, i);
 }
 
 // The bf16x3 planes of the same ten matrices (segments with n_out > 0): k-step ks = 16 consecutive k of the k axis above; lane half h
@@ -56,28 +60,18 @@ __global__ void nerfgrid_pack_split_kernel(const float *__restrict__ raw, unsign
   const PackSeg s = plan.seg[blockIdx.y];
   const int64_t total = (int64_t)(s.ka_pad + s.kb) * s.n_out;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int j = (int)(i & 7), h = (int)((i >> 3) & 1);
-    const int64_t q = i >> 4;
-    const int o = (int)(q % s.n_out), ks = (int)(q / s.n_out);
-    const int k = 16 * ks + 8 * h + j;
-    float v = 0.f;
-    if (k < s.ka_pad) {
-      if (k < s.ka) v = raw[s.src + (int64_t)o * s.ld + k];
-    } else {
-      v = raw[s.src + (int64_t)o * s.ld + s.ka + (k - s.ka_pad)];
-    }
+    const float v = pack_elem<8>(raw, s, i);
     const __bf16 hb = (__bf16)v;
     planes[s.dst + i] = __builtin_bit_cast(unsigned short, hb);
     planes[kSplitPlane + s.dst + i] = f32_to_bf16_bits(v - (float)hb);
   }
 }
 
-// ---- trunk (body: nerf_mlp.cuh) --------------------------------------------------------------------------------------------------
+// ---- trunk (kernel: nerf_mlp.cuh) ------------------------------------------------------------------------------------------------
 struct GridArgs {
   const float *xs, *ys, *zs;      // linspace values [rx], [ry], [rz]
   int rx, ry, rz;
   float cx, cy, cz, scale;
-  int multires, input_ch;
   int64_t num_points;             // rx * ry * rz
   int layout;                     // 0 flat (N, 4); 1 wlh (rx, ry, rz, 4)
 };
@@ -92,7 +86,7 @@ __device__ __forceinline__ int64_t out_index(const GridArgs &g, int64_t r) {
 
 // where a tile's points come from (lattice index -> linspace values) and where sigma goes
 struct GridSrc {
-  const GridArgs &ga;
+  GridArgs ga;
   int64_t tile0;
   __device__ __forceinline__ void point(int i, float (&p)[3]) const {
     int64_t pr = tile0 + i;
@@ -106,7 +100,7 @@ struct GridSrc {
   }
 };
 struct GridSink {
-  const GridArgs &ga;
+  GridArgs ga;
   int64_t tile0;
   float *out;
   __device__ __forceinline__ void sigma(int i, float s) const {
@@ -115,22 +109,14 @@ struct GridSink {
   }
 };
 
-__global__ __launch_bounds__(256) void nerfgrid_trunk_kernel(GridArgs ga, const float *__restrict__ packed, int64_t point0,
-                                                             float *__restrict__ gbuf, float *__restrict__ out) {
-  extern __shared__ __align__(16) float act[];
-  const int64_t tile0 = point0 + (int64_t)blockIdx.x * kTile;
-  trunk_body(act, packed, ga.multires, ga.input_ch, GridSrc{ga, tile0}, GridSink{ga, tile0, out},
-             gbuf + (int64_t)blockIdx.x * (kTile * kHalf));
-}
-
-__global__ __launch_bounds__(256) void nerfgrid_trunk_bf16x3_kernel(GridArgs ga, const float *__restrict__ packed,
-                                                                    const uint4 *__restrict__ split, int64_t point0,
-                                                                    float *__restrict__ gbuf, float *__restrict__ out) {
-  extern __shared__ __align__(16) float act[];
-  const int64_t tile0 = point0 + (int64_t)blockIdx.x * kTile;
-  trunk_body<true>(act, packed, ga.multires, ga.input_ch, GridSrc{ga, tile0}, GridSink{ga, tile0, out},
-                   gbuf + (int64_t)blockIdx.x * (kTile * kHalf), split);
-}
+struct GridTile {                 // the tiles of a chunk that starts at lattice point point0
+  GridArgs ga;
+  int multires;
+  int64_t point0;
+  float *out;
+  __device__ __forceinline__ GridSrc src(unsigned block) const { return {ga, point0 + (int64_t)block * kTile}; }
+  __device__ __forceinline__ GridSink sink(unsigned block) const { return {ga, point0 + (int64_t)block * kTile, out}; }
+};
 
 // ---- head ------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kTile) void nerfgrid_head_kernel(GridArgs ga, const float *__restrict__ packed, int64_t point0,
@@ -197,14 +183,13 @@ int matrix_plan(int input_ch, PackPlan &plan, int64_t *src_end) {
   return n;
 }
 
-// kSplit: the trunk in the bf16x3 arithmetic on the planes ``split``; the head is the same kernel either way
-template <bool kSplit>
+// split: the bf16x3 planes of packed, and the trunk runs in that arithmetic; null: in fp32.  The head is the same kernel either way
 int grid_query(const float *xs, const float *ys, const float *zs, int res_x, int res_y, int res_z, float center_x, float center_y,
-               float center_z, float bb_scale, int multires, const float *packed, const void *split, const float *ctab, int num_poses,
+               float center_z, float bb_scale, int multires, const float *packed, const uint4 *split, const float *ctab, int num_poses,
                int layout, int64_t chunk, void *work, int64_t work_bytes, float *out, nrpn_stream_t stream) {
-  NRPN_REQUIRE(xs && ys && zs && packed && ctab && work && out && (!kSplit || split), "nerfgrid_query: null pointer");
+  NRPN_REQUIRE(xs && ys && zs && packed && ctab && work && out, "nerfgrid_query: null pointer");
   NRPN_REQUIRE(res_x >= 1 && res_y >= 1 && res_z >= 1, "nerfgrid_query: resolution %d x %d x %d", res_x, res_y, res_z);
-  NRPN_REQUIRE(multires >= 0 && 3 + 6 * multires <= kEnc, "nerfgrid_query: multires %d does not fit %d encoding columns", multires, kEnc);
+  NRPN_REQUIRE(model_ok(multires, 0, 0), "nerfgrid_query: multires %d does not fit %d encoding columns", multires, kEnc);
   NRPN_REQUIRE(num_poses >= 1, "nerfgrid_query: no poses");
   NRPN_REQUIRE(layout == 0 || layout == 1, "nerfgrid_query: layout %d", layout);
   const int64_t n = (int64_t)res_x * res_y * res_z;
@@ -214,23 +199,12 @@ int grid_query(const float *xs, const float *ys, const float *zs, int res_x, int
   NRPN_REQUIRE(chunk_tiles <= 0x7fffffff, "nerfgrid_query: chunk too large");
   NRPN_REQUIRE(work_bytes >= chunk_tiles * kTile * kHalf * 4, "nerfgrid_query: work buffer of %lld bytes is too small",
                (long long)work_bytes);
-  if constexpr (kSplit) {
-    NRPN_LDS(nerfgrid_trunk_bf16x3_kernel, kLdsBytes);
-  } else {
-    NRPN_LDS(nerfgrid_trunk_kernel, kLdsBytes);
-  }
-  GridArgs ga{xs, ys, zs, res_x, res_y, res_z, center_x, center_y, center_z, bb_scale, multires, 3 + 6 * multires, n, layout};
+  GridArgs ga{xs, ys, zs, res_x, res_y, res_z, center_x, center_y, center_z, bb_scale, n, layout};
   float *gbuf = static_cast<float *>(work);
   for (int64_t p0 = 0; p0 < n; p0 += chunk_tiles * kTile) {
     const int64_t left = n - p0;
     const int tiles = (int)(left < chunk_tiles * kTile ? cdiv64(left, kTile) : chunk_tiles);
-    if constexpr (kSplit) {
-      nerfgrid_trunk_bf16x3_kernel<<<tiles, 256, kLdsBytes, as_stream(stream)>>>(ga, packed, static_cast<const uint4 *>(split), p0, gbuf, out);
-      NRPN_LAUNCH_CHECK("nerfgrid_trunk_bf16x3_kernel");
-    } else {
-      nerfgrid_trunk_kernel<<<tiles, 256, kLdsBytes, as_stream(stream)>>>(ga, packed, p0, gbuf, out);
-      NRPN_LAUNCH_CHECK("nerfgrid_trunk_kernel");
-    }
+    if (int rc = launch_trunk(GridTile{ga, multires, p0, out}, tiles, packed, split, gbuf, as_stream(stream))) return rc;
     nerfgrid_head_kernel<<<tiles, kTile, 0, as_stream(stream)>>>(ga, packed, p0, gbuf, ctab, num_poses, out);
     NRPN_LAUNCH_CHECK("nerfgrid_head_kernel");
   }
@@ -283,16 +257,17 @@ int nrpn_nerfgrid_pack_bf16x3(const float *raw, int input_ch, void *planes, nrpn
 int nrpn_nerfgrid_query(const float *xs, const float *ys, const float *zs, int res_x, int res_y, int res_z, float center_x,
                         float center_y, float center_z, float bb_scale, int multires, const float *packed, const float *ctab,
                         int num_poses, int layout, int64_t chunk, void *work, int64_t work_bytes, float *out, nrpn_stream_t stream) {
-  return grid_query<false>(xs, ys, zs, res_x, res_y, res_z, center_x, center_y, center_z, bb_scale, multires, packed, nullptr, ctab,
-                           num_poses, layout, chunk, work, work_bytes, out, stream);
+  return grid_query(xs, ys, zs, res_x, res_y, res_z, center_x, center_y, center_z, bb_scale, multires, packed, nullptr, ctab, num_poses,
+                    layout, chunk, work, work_bytes, out, stream);
 }
 
 int nrpn_nerfgrid_query_bf16x3(const float *xs, const float *ys, const float *zs, int res_x, int res_y, int res_z, float center_x,
                                float center_y, float center_z, float bb_scale, int multires, const float *packed, const void *split,
                                const float *ctab, int num_poses, int layout, int64_t chunk, void *work, int64_t work_bytes, float *out,
                                nrpn_stream_t stream) {
-  return grid_query<true>(xs, ys, zs, res_x, res_y, res_z, center_x, center_y, center_z, bb_scale, multires, packed, split, ctab,
-                          num_poses, layout, chunk, work, work_bytes, out, stream);
+  NRPN_REQUIRE(split, "nerfgrid_query: null pointer");
+  return grid_query(xs, ys, zs, res_x, res_y, res_z, center_x, center_y, center_z, bb_scale, multires, packed,
+                    static_cast<const uint4 *>(split), ctab, num_poses, layout, chunk, work, work_bytes, out, stream);
 }
 
 }  // extern "C"

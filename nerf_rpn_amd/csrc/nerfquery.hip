@@ -26,7 +26,6 @@ namespace {
 
 using namespace nerfmlp;
 
-constexpr int kMaxViewsCh = 64;       // 3 + 6 multires_views <= 64
 constexpr int kSlices = 64;           // of a chunk's points in wgrad
 constexpr int kHeadCols = 64;         // the head's cotangent rows: draw_rgb, dsigma, zeros (one 64-column block of wgrad)
 constexpr int kLdT = kHalf + 1;       // bank skew of headbwd's transposing tile
@@ -36,10 +35,9 @@ constexpr int64_t kSzT = (int64_t)kW * kW;
 constexpr int64_t kOffTf = 8 * kSzT;
 constexpr int64_t kPackedTFloats = kOffTf + (int64_t)kHalf * kW;
 
-int64_t align16(int64_t b) { return (b + 15) / 16 * 16; }
-
 struct Model {
   int multires, multires_views, cam_ch;
+  bool ok() const { return model_ok(multires, multires_views, cam_ch); }
   int input_ch() const { return 3 + 6 * multires; }
   int views_ch() const { return 3 + 6 * multires_views; }
   int ldv() const { return views_ch() + cam_ch; }                          // view and camera columns of views_linears.0
@@ -85,11 +83,7 @@ __global__ __launch_bounds__(kHalf) void nerfquery_rays_kernel(const float *__re
   if (j < 3) {
     const float d = viewdirs[ray * 3 + j];
     emb[j] = d;
-    for (int l = 0; l < multires_views; ++l) {
-      const float arg = d * ldexpf(1.0f, l);
-      emb[3 + 6 * l + j] = sinf(arg);
-      emb[3 + 6 * l + 3 + j] = cosf(arg);
-    }
+    for (int l = 0; l < multires_views; ++l) embed_freq(emb, d, l, j);
   }
   __syncthreads();
   float c = b_view[j];
@@ -100,7 +94,7 @@ __global__ __launch_bounds__(kHalf) void nerfquery_rays_kernel(const float *__re
     for (int k = j; k < kv; k += kHalf) xv[ray * kv + k] = k < views_ch ? emb[k] : k < ldv ? cam[k - views_ch] : 0.f;
 }
 
-// ---- trunk (body: nerf_mlp.cuh) --------------------------------------------------------------------------------------------------
+// ---- trunk (kernel: nerf_mlp.cuh) ------------------------------------------------------------------------------------------------
 struct Points {
   const float *pts;       // [num_points][3], world
   int64_t num_points;     // of the whole call
@@ -117,15 +111,6 @@ struct PointSrc {
     const float c[3] = {pp.cx, pp.cy, pp.cz};
 #pragma unroll
     for (int a = 0; a < 3; ++a) p[a] = __fmul_rn(__fsub_rn(pp.pts[pi * 3 + a], c[a]), pp.scale);
-  }
-};
-
-struct RawSink {          // forward: sigma to raw [point][4]
-  int64_t tile0, num_points;
-  float *raw;
-  __device__ __forceinline__ void sigma(int i, float s) const {
-    const int64_t pi = tile0 + i;
-    if (pi < num_points) raw[pi * 4 + 3] = s;
   }
 };
 
@@ -159,40 +144,23 @@ struct KeepSink {
   }
 };
 
-__global__ __launch_bounds__(256) void nerfquery_trunk_kernel(Points pp, int multires, const float *__restrict__ packed, int64_t point0,
-                                                              float *__restrict__ gbuf, float *__restrict__ raw) {
-  extern __shared__ __align__(16) float act[];
-  const int64_t tile0 = point0 + (int64_t)blockIdx.x * kTile;
-  trunk_body(act, packed, multires, 3 + 6 * multires, PointSrc{pp, tile0}, RawSink{tile0, pp.num_points, raw},
-             gbuf + (int64_t)blockIdx.x * (kTile * kHalf));
-}
-
-__global__ __launch_bounds__(256) void nerfquery_trunk_keep_kernel(Points pp, int multires, const float *__restrict__ packed,
-                                                                   int64_t point0, float *__restrict__ gbuf, Kept kept) {
-  extern __shared__ __align__(16) float act[];
-  const int64_t tile0 = point0 + (int64_t)blockIdx.x * kTile;
-  trunk_body(act, packed, multires, 3 + 6 * multires, PointSrc{pp, tile0}, KeepSink{kept, (int64_t)blockIdx.x * kTile},
-             gbuf + (int64_t)blockIdx.x * (kTile * kHalf));
-}
-
-// the same two in the bf16x3 arithmetic: the backward keeps what this forward computed
-__global__ __launch_bounds__(256) void nerfquery_trunk_bf16x3_kernel(Points pp, int multires, const float *__restrict__ packed,
-                                                                     const uint4 *__restrict__ split, int64_t point0,
-                                                                     float *__restrict__ gbuf, float *__restrict__ raw) {
-  extern __shared__ __align__(16) float act[];
-  const int64_t tile0 = point0 + (int64_t)blockIdx.x * kTile;
-  trunk_body<true>(act, packed, multires, 3 + 6 * multires, PointSrc{pp, tile0}, RawSink{tile0, pp.num_points, raw},
-                   gbuf + (int64_t)blockIdx.x * (kTile * kHalf), split);
-}
-
-__global__ __launch_bounds__(256) void nerfquery_trunk_keep_bf16x3_kernel(Points pp, int multires, const float *__restrict__ packed,
-                                                                          const uint4 *__restrict__ split, int64_t point0,
-                                                                          float *__restrict__ gbuf, Kept kept) {
-  extern __shared__ __align__(16) float act[];
-  const int64_t tile0 = point0 + (int64_t)blockIdx.x * kTile;
-  trunk_body<true>(act, packed, multires, 3 + 6 * multires, PointSrc{pp, tile0}, KeepSink{kept, (int64_t)blockIdx.x * kTile},
-                   gbuf + (int64_t)blockIdx.x * (kTile * kHalf), split);
-}
+// the tiles of a chunk that starts at point point0: the forward's, and the backward's, which keeps what this forward computed
+struct PointTile {
+  Points pp;
+  int multires;
+  int64_t point0;
+  float *raw;             // [num_points][4]
+  __device__ __forceinline__ PointSrc src(unsigned block) const { return {pp, point0 + (int64_t)block * kTile}; }
+  __device__ __forceinline__ RawSink sink(unsigned block) const { return {point0 + (int64_t)block * kTile, pp.num_points, raw}; }
+};
+struct KeepTile {
+  Points pp;
+  int multires;
+  int64_t point0;
+  Kept kept;
+  __device__ __forceinline__ PointSrc src(unsigned block) const { return {pp, point0 + (int64_t)block * kTile}; }
+  __device__ __forceinline__ KeepSink sink(unsigned block) const { return {kept, (int64_t)block * kTile}; }
+};
 
 // ---- head ------------------------------------------------------------------------------------------------------------------------
 // One workgroup of 64 threads, one tile; rgb_linear over v = relu(g + c_ray) as 128-term fmaf chains in j order
@@ -283,15 +251,22 @@ struct PackTPlan {
   PackTSeg seg[9];
 };
 
+// the value of element i of a segment's fragments, kFrag (4 floats or 8 bf16) elements to a fragment
+template <int kFrag>
+__device__ __forceinline__ float pack_t_elem(const float *__restrict__ raw, const PackTSeg &s, int64_t i) {
+  constexpr int kShift = kFrag == 4 ? 2 : 3;
+  static_assert(kFrag == 1 << kShift, "fragments of 4 or 8 elements");
+  const int j = (int)(i & (kFrag - 1)), h = (int)((i >> kShift) & 1);
+  const int64_t q = i >> (kShift + 1);
+  const int o = (int)(q % kW), kg = (int)(q / kW);
+  return raw[s.src + (int64_t)(2 * kFrag * kg + kFrag * h + j) * s.ld + s.col_off + o];
+}
+
 __global__ void nerfquery_pack_t_kernel(const float *__restrict__ raw, float *__restrict__ packed_t, PackTPlan plan) {
   const PackTSeg s = plan.seg[blockIdx.y];
   const int64_t total = (int64_t)s.K * kW;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int j = (int)(i & 3), h = (int)((i >> 2) & 1);
-    const int64_t q = i >> 3;
-    const int o = (int)(q % kW), kg = (int)(q / kW);
-    packed_t[s.dst + i] = raw[s.src + (int64_t)(8 * kg + 4 * h + j) * s.ld + s.col_off + o];
-  }
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x)
+    packed_t[s.dst + i] = pack_t_elem<4>(raw, s, i);
 }
 
 // The bf16x3 planes of the same nine transposes (splitting commutes with transposing: element for element these are the values of the
@@ -301,10 +276,7 @@ __global__ void nerfquery_pack_t_split_kernel(const float *__restrict__ raw, uns
   const PackTSeg s = plan.seg[blockIdx.y];
   const int64_t total = (int64_t)s.K * kW;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int j = (int)(i & 7), h = (int)((i >> 3) & 1);
-    const int64_t q = i >> 4;
-    const int o = (int)(q % kW), ks = (int)(q / kW);
-    const float v = raw[s.src + (int64_t)(16 * ks + 8 * h + j) * s.ld + s.col_off + o];
+    const float v = pack_t_elem<8>(raw, s, i);
     const __bf16 hb = (__bf16)v;
     planes_t[s.dst + i] = __builtin_bit_cast(unsigned short, hb);
     planes_t[kPackedTFloats + s.dst + i] = f32_to_bf16_bits(v - (float)hb);
@@ -722,18 +694,14 @@ struct QueryCall {
   void *work;
   int64_t work_bytes;
   hipStream_t stream;
-  const uint4 *split;       // the bf16x3 planes of packed (kSplit launchers only)
-  const uint4 *split_t = nullptr;      // the bf16x3 planes of the packed transposes (backward<true, true> only)
+  const uint4 *split;       // the bf16x3 planes of packed: the trunk then runs in that arithmetic; null: fp32
+  const uint4 *split_t;     // the bf16x3 planes of the packed transposes: the backward's dgrads and trunk wgrads then do too (with split)
   int64_t chunk_tiles() const { return cdiv64(chunk < pp.num_points ? chunk : pp.num_points, kTile); }
 };
 
 bool sizes_ok(int64_t num_rays, int samples, int64_t chunk) {
   return num_rays >= 1 && samples >= 1 && samples <= 65536 && num_rays < ((int64_t)1 << 31) && chunk >= 1 &&
          num_rays * samples < ((int64_t)1 << 40);
-}
-bool model_ok(const Model &m) {
-  return m.multires >= 0 && m.input_ch() <= kEnc && m.multires_views >= 0 && m.views_ch() <= kMaxViewsCh && m.cam_ch >= 0 &&
-         m.cam_ch <= 65536;
 }
 
 struct Layout {           // of the work buffer, in bytes; every part 16-byte aligned
@@ -764,7 +732,7 @@ Layout layout(const Model &m, int64_t num_rays, int64_t chunk_tiles) {
 
 int check(const char *who, const QueryCall &c, bool backward) {
   NRPN_REQUIRE(c.pp.pts && c.viewdirs && c.packed && c.w_view && c.b_view && c.work, "%s: null pointer", who);
-  NRPN_REQUIRE(model_ok(c.m), "%s: multires %d / multires_views %d / input_ch_cam %d", who, c.m.multires, c.m.multires_views, c.m.cam_ch);
+  NRPN_REQUIRE(c.m.ok(), "%s: multires %d / multires_views %d / input_ch_cam %d", who, c.m.multires, c.m.multires_views, c.m.cam_ch);
   NRPN_REQUIRE(c.m.cam_ch == 0 || c.cam, "%s: input_ch_cam %d without an embedded_cam", who, c.m.cam_ch);
   NRPN_REQUIRE(sizes_ok(c.num_rays, c.pp.S, c.chunk), "%s: %lld rays of %d points in chunks of %lld", who, (long long)c.num_rays, c.pp.S,
                (long long)c.chunk);
@@ -784,16 +752,10 @@ int launch_rays(const QueryCall &c, const Layout &l, bool with_xv) {
   return NRPN_OK;
 }
 
-// kSplit (here and in backward): the trunk runs in the bf16x3 arithmetic on c.split; everything after it is the same
-template <bool kSplit>
+// c.split (here and in backward): the trunk runs in the bf16x3 arithmetic on it; everything after it is the same
 int forward(const QueryCall &c, float *raw) {
   if (int rc = check("nerfquery_forward", c, false)) return rc;
-  NRPN_REQUIRE(raw && (!kSplit || c.split), "nerfquery_forward: null output or planes");
-  if constexpr (kSplit) {
-    NRPN_LDS(nerfquery_trunk_bf16x3_kernel, kLdsBytes);
-  } else {
-    NRPN_LDS(nerfquery_trunk_kernel, kLdsBytes);
-  }
+  NRPN_REQUIRE(raw, "nerfquery_forward: null output or planes");
   const Layout l = layout(c.m, c.num_rays, c.chunk_tiles());
   char *wk = static_cast<char *>(c.work);
   const float *ctab = reinterpret_cast<float *>(wk + l.ctab);
@@ -802,13 +764,7 @@ int forward(const QueryCall &c, float *raw) {
   for (int64_t p0 = 0; p0 < c.pp.num_points; p0 += l.rows) {
     const int64_t left = c.pp.num_points - p0;
     const int tiles = (int)cdiv64(left < l.rows ? left : l.rows, kTile);
-    if constexpr (kSplit) {
-      nerfquery_trunk_bf16x3_kernel<<<tiles, 256, kLdsBytes, c.stream>>>(c.pp, c.m.multires, c.packed, c.split, p0, gbuf, raw);
-      NRPN_LAUNCH_CHECK("nerfquery_trunk_bf16x3_kernel");
-    } else {
-      nerfquery_trunk_kernel<<<tiles, 256, kLdsBytes, c.stream>>>(c.pp, c.m.multires, c.packed, p0, gbuf, raw);
-      NRPN_LAUNCH_CHECK("nerfquery_trunk_kernel");
-    }
+    if (int rc = launch_trunk(PointTile{c.pp, c.m.multires, p0, raw}, tiles, c.packed, c.split, gbuf, c.stream)) return rc;
     nerfquery_head_kernel<<<tiles, kTile, 0, c.stream>>>(c.pp, c.packed, ctab, p0, gbuf, raw);
     NRPN_LAUNCH_CHECK("nerfquery_head_kernel");
   }
@@ -824,22 +780,15 @@ struct Wgrad {            // one product of the backward and where its rows and 
   int64_t dst;            // of the first of them in the gradient
   int ld;
   int64_t bias_dst;       // of column sum row_lo, or -1
-  bool trunk = false;     // one of the trunk's ten matrices: split under kSplitBwd
+  bool trunk = false;     // one of the trunk's ten matrices: split when the backward is
 };
 
-// kSplitBwd (with kSplit): the dgrads and the trunk's wgrads in the bf16x3 arithmetic too, on c.split_t in place of packed_t
-template <bool kSplit, bool kSplitBwd = false>
+// c.split_t (with c.split): the dgrads and the trunk's wgrads in the bf16x3 arithmetic too, on c.split_t in place of packed_t
 int backward(const QueryCall &c, const float *packed_t, const float *draw, float *grads) {
-  static_assert(kSplit || !kSplitBwd, "the split backward belongs to the split forward");
+  NRPN_REQUIRE(c.split || !c.split_t, "nerfquery_backward: the split backward belongs to the split forward");
   if (int rc = check("nerfquery_backward", c, true)) return rc;
-  NRPN_REQUIRE((kSplitBwd ? (const void *)c.split_t : (const void *)packed_t) && draw && grads && (!kSplit || c.split),
-               "nerfquery_backward: null pointer");
-  if constexpr (kSplit) {
-    NRPN_LDS(nerfquery_trunk_keep_bf16x3_kernel, kLdsBytes);
-  } else {
-    NRPN_LDS(nerfquery_trunk_keep_kernel, kLdsBytes);
-  }
-  if constexpr (kSplitBwd) {
+  NRPN_REQUIRE((c.split_t || packed_t) && draw && grads, "nerfquery_backward: null pointer");
+  if (c.split_t) {
     NRPN_LDS((nerfquery_dgrad_split_kernel<kHalf, false>), kLdsBytes);
     NRPN_LDS((nerfquery_dgrad_split_kernel<kW, true>), kLdsBytes);
     NRPN_LDS(nerfquery_wgrad_split_kernel, kWsLdsBytes);
@@ -868,7 +817,7 @@ int backward(const QueryCall &c, const float *packed_t, const float *draw, float
     // h and f of this chunk are laid out for l.rows rows whatever the chunk's own count: Kept::rows is the stride of h's layers
     auto wgrad = [&](const Wgrad &w) -> int {
       const int blocks = (w.n >> 6) * (w.kpad >> 6);
-      if (kSplitBwd && w.trunk) {
+      if (c.split_t && w.trunk) {
         NRPN_REQUIRE((w.kpad == kW || w.kpad == kEnc) && blocks % 4 == 0, "nerfquery_backward: a %d x %d split wgrad", w.n, w.kpad);
         nerfquery_wgrad_split_kernel<<<dim3(blocks / 4, kSlices), 256, kWsLdsBytes, c.stream>>>(w.dy, w.ldy, w.n, w.x, w.ldx, w.kpad, rows, rps,
                                                                                               partial);
@@ -895,7 +844,7 @@ int backward(const QueryCall &c, const float *packed_t, const float *draw, float
       return NRPN_OK;
     };
     auto dgrad = [&](const float *dy, int K, int64_t wt_at, bool alpha, const float *mask, float *out) -> int {
-      if constexpr (kSplitBwd) {
+      if (c.split_t) {
         const uint4 *hi = c.split_t + wt_at / 8, *lo = c.split_t + (kPackedTFloats + wt_at) / 8;
         NRPN_REQUIRE((K == kHalf && !mask) || (K == kW && mask), "nerfquery_backward: a split dgrad of K %d", K);
         if (K == kHalf)
@@ -914,13 +863,7 @@ int backward(const QueryCall &c, const float *packed_t, const float *draw, float
     };
     auto hl = [&](int i) { return kept.h + (int64_t)i * l.rows * kW; };
 
-    if constexpr (kSplit) {
-      nerfquery_trunk_keep_bf16x3_kernel<<<tiles, 256, kLdsBytes, c.stream>>>(c.pp, m.multires, c.packed, c.split, p0, gbuf, kept);
-      NRPN_LAUNCH_CHECK("nerfquery_trunk_keep_bf16x3_kernel");
-    } else {
-      nerfquery_trunk_keep_kernel<<<tiles, 256, kLdsBytes, c.stream>>>(c.pp, m.multires, c.packed, p0, gbuf, kept);
-      NRPN_LAUNCH_CHECK("nerfquery_trunk_keep_kernel");
-    }
+    if (int rc = launch_trunk(KeepTile{c.pp, m.multires, p0, kept}, tiles, c.packed, c.split, gbuf, c.stream)) return rc;
     nerfquery_headbwd_kernel<<<tiles, kTile, 0, c.stream>>>(c.pp, c.packed, ctab, xv, kv, p0, gbuf, draw, ho);
     NRPN_LAUNCH_CHECK("nerfquery_headbwd_kernel");
     // rgb_linear and alpha_linear: rows 0 .. 2 and row 3 of the head's cotangent
@@ -949,6 +892,16 @@ int backward(const QueryCall &c, const float *packed_t, const float *draw, float
   return NRPN_OK;
 }
 
+// the call of an entry point: the arguments the five share; split / split_t: the planes, or null
+QueryCall query_call(const float *pts, const float *viewdirs, int64_t num_rays, int num_samples, float center_x, float center_y,
+                     float center_z, float bb_scale, int multires, int multires_views, int input_ch_cam, const float *packed,
+                     const float *w_view, const float *b_view, const float *embedded_cam, int64_t chunk, void *work, int64_t work_bytes,
+                     nrpn_stream_t stream, const void *split, const void *split_t) {
+  return QueryCall{Points{pts, num_rays * num_samples, num_samples, center_x, center_y, center_z, bb_scale},
+                   Model{multires, multires_views, input_ch_cam}, viewdirs, packed, w_view, b_view, embedded_cam, num_rays, chunk, work,
+                   work_bytes, as_stream(stream), static_cast<const uint4 *>(split), static_cast<const uint4 *>(split_t)};
+}
+
 }  // namespace
 
 extern "C" {
@@ -957,8 +910,8 @@ int64_t nrpn_nerfquery_work_bytes(int what, int64_t num_rays, int num_samples, i
                                   int input_ch_cam) {
   const Model m{multires, multires_views, input_ch_cam};
   if (what == 2 || what == 5) return kPackedTFloats * 4;       // floats, or a hi and a lo bf16 of each
-  if (what == 4) return 4 * (int64_t)(kEnc + kLayers * kW + kW + 3 * kHalf + kHeadCols + (model_ok(m) ? m.kv() : 0));
-  if (!model_ok(m) || !sizes_ok(num_rays, num_samples, chunk)) return -1;
+  if (what == 4) return 4 * (int64_t)(kEnc + kLayers * kW + kW + 3 * kHalf + kHeadCols + (m.ok() ? m.kv() : 0));
+  if (!m.ok() || !sizes_ok(num_rays, num_samples, chunk)) return -1;
   if (what == 3) return grad_layout(m).total;
   const int64_t n = num_rays * num_samples;
   const Layout l = layout(m, num_rays, cdiv64(chunk < n ? chunk : n, kTile));
@@ -986,10 +939,9 @@ int nrpn_nerfquery_forward(const float *pts, const float *viewdirs, int64_t num_
                            float center_z, float bb_scale, int multires, int multires_views, int input_ch_cam, const float *packed,
                            const float *w_view, const float *b_view, const float *embedded_cam, int64_t chunk, void *work,
                            int64_t work_bytes, float *raw, nrpn_stream_t stream) {
-  QueryCall c{Points{pts, num_rays * num_samples, num_samples, center_x, center_y, center_z, bb_scale},
-              Model{multires, multires_views, input_ch_cam}, viewdirs, packed, w_view, b_view, embedded_cam, num_rays, chunk, work,
-              work_bytes, as_stream(stream), nullptr};
-  return forward<false>(c, raw);
+  return forward(query_call(pts, viewdirs, num_rays, num_samples, center_x, center_y, center_z, bb_scale, multires, multires_views,
+                            input_ch_cam, packed, w_view, b_view, embedded_cam, chunk, work, work_bytes, stream, nullptr, nullptr),
+                 raw);
 }
 
 int nrpn_nerfquery_forward_bf16x3(const float *pts, const float *viewdirs, int64_t num_rays, int num_samples, float center_x,
@@ -997,20 +949,19 @@ int nrpn_nerfquery_forward_bf16x3(const float *pts, const float *viewdirs, int64
                                   const float *packed, const void *split, const float *w_view, const float *b_view,
                                   const float *embedded_cam, int64_t chunk, void *work, int64_t work_bytes, float *raw,
                                   nrpn_stream_t stream) {
-  QueryCall c{Points{pts, num_rays * num_samples, num_samples, center_x, center_y, center_z, bb_scale},
-              Model{multires, multires_views, input_ch_cam}, viewdirs, packed, w_view, b_view, embedded_cam, num_rays, chunk, work,
-              work_bytes, as_stream(stream), static_cast<const uint4 *>(split)};
-  return forward<true>(c, raw);
+  NRPN_REQUIRE(split, "nerfquery_forward: null output or planes");
+  return forward(query_call(pts, viewdirs, num_rays, num_samples, center_x, center_y, center_z, bb_scale, multires, multires_views,
+                            input_ch_cam, packed, w_view, b_view, embedded_cam, chunk, work, work_bytes, stream, split, nullptr),
+                 raw);
 }
 
 int nrpn_nerfquery_backward(const float *pts, const float *viewdirs, int64_t num_rays, int num_samples, float center_x, float center_y,
                             float center_z, float bb_scale, int multires, int multires_views, int input_ch_cam, const float *packed,
                             const float *packed_t, const float *w_view, const float *b_view, const float *embedded_cam,
                             const float *draw, int64_t chunk, void *work, int64_t work_bytes, float *grads, nrpn_stream_t stream) {
-  QueryCall c{Points{pts, num_rays * num_samples, num_samples, center_x, center_y, center_z, bb_scale},
-              Model{multires, multires_views, input_ch_cam}, viewdirs, packed, w_view, b_view, embedded_cam, num_rays, chunk, work,
-              work_bytes, as_stream(stream), nullptr};
-  return backward<false>(c, packed_t, draw, grads);
+  return backward(query_call(pts, viewdirs, num_rays, num_samples, center_x, center_y, center_z, bb_scale, multires, multires_views,
+                             input_ch_cam, packed, w_view, b_view, embedded_cam, chunk, work, work_bytes, stream, nullptr, nullptr),
+                  packed_t, draw, grads);
 }
 
 int nrpn_nerfquery_backward_bf16x3(const float *pts, const float *viewdirs, int64_t num_rays, int num_samples, float center_x,
@@ -1018,10 +969,10 @@ int nrpn_nerfquery_backward_bf16x3(const float *pts, const float *viewdirs, int6
                                    const float *packed, const void *split, const float *packed_t, const float *w_view,
                                    const float *b_view, const float *embedded_cam, const float *draw, int64_t chunk, void *work,
                                    int64_t work_bytes, float *grads, nrpn_stream_t stream) {
-  QueryCall c{Points{pts, num_rays * num_samples, num_samples, center_x, center_y, center_z, bb_scale},
-              Model{multires, multires_views, input_ch_cam}, viewdirs, packed, w_view, b_view, embedded_cam, num_rays, chunk, work,
-              work_bytes, as_stream(stream), static_cast<const uint4 *>(split)};
-  return backward<true>(c, packed_t, draw, grads);
+  NRPN_REQUIRE(split, "nerfquery_backward: null pointer");
+  return backward(query_call(pts, viewdirs, num_rays, num_samples, center_x, center_y, center_z, bb_scale, multires, multires_views,
+                             input_ch_cam, packed, w_view, b_view, embedded_cam, chunk, work, work_bytes, stream, split, nullptr),
+                  packed_t, draw, grads);
 }
 
 int nrpn_nerfquery_backward_bf16x3_split(const float *pts, const float *viewdirs, int64_t num_rays, int num_samples, float center_x,
@@ -1029,10 +980,10 @@ int nrpn_nerfquery_backward_bf16x3_split(const float *pts, const float *viewdirs
                                          int input_ch_cam, const float *packed, const void *split, const void *split_t,
                                          const float *w_view, const float *b_view, const float *embedded_cam, const float *draw,
                                          int64_t chunk, void *work, int64_t work_bytes, float *grads, nrpn_stream_t stream) {
-  QueryCall c{Points{pts, num_rays * num_samples, num_samples, center_x, center_y, center_z, bb_scale},
-              Model{multires, multires_views, input_ch_cam}, viewdirs, packed, w_view, b_view, embedded_cam, num_rays, chunk, work,
-              work_bytes, as_stream(stream), static_cast<const uint4 *>(split), static_cast<const uint4 *>(split_t)};
-  return backward<true, true>(c, nullptr, draw, grads);
+  NRPN_REQUIRE(split && split_t, "nerfquery_backward: null pointer");
+  return backward(query_call(pts, viewdirs, num_rays, num_samples, center_x, center_y, center_z, bb_scale, multires, multires_views,
+                             input_ch_cam, packed, w_view, b_view, embedded_cam, chunk, work, work_bytes, stream, split, split_t),
+                  nullptr, draw, grads);
 }
 
 }  // extern "C"

@@ -22,7 +22,6 @@ using namespace nerfmlp;
 using namespace nerfray;      // ray_norm, sample_weight, MergeCursor, merged_walk, RaySums, sizes_ok
 static_assert(kRayTile == kTile, "the size limits count the trunk's tiles");
 
-constexpr int kMaxViewsCh = 64;       // 3 + 6 multires_views <= 64 (multires_views <= 10)
 constexpr int kCtileLd = kHalf + 1;   // bank skew between the rays of a head tile
 
 struct RayPoints {
@@ -41,7 +40,7 @@ __global__ void nerfrender_rays_kernel(const float *__restrict__ camera, int W, 
   pixel_ray(camera, W, ray0 + i, rays + (int64_t)i * 6);
 }
 
-// ---- trunk -----------------------------------------------------------------------------------------------------------------------
+// ---- trunk (kernel: nerf_mlp.cuh) ------------------------------------------------------------------------------------------------
 struct RaySrc {
   const RayPoints &rp;
   int64_t tile0;
@@ -57,31 +56,13 @@ struct RaySrc {
     for (int a = 0; a < 3; ++a) p[a] = __fmul_rn(__fsub_rn(__fadd_rn(o[a], __fmul_rn(o[3 + a], zv)), c[a]), rp.scale);
   }
 };
-struct RaySink {
-  int64_t tile0, num_points;
-  float *raw;
-  __device__ __forceinline__ void sigma(int i, float s) const {
-    const int64_t pi = tile0 + i;
-    if (pi < num_points) raw[pi * 4 + 3] = s;
-  }
+struct RayTile {          // the tiles of one pass over a chunk's rays
+  RayPoints rp;
+  int multires;
+  float *raw;             // [points of the pass][4]
+  __device__ __forceinline__ RaySrc src(unsigned block) const { return {rp, (int64_t)block * kTile}; }
+  __device__ __forceinline__ RawSink sink(unsigned block) const { return {(int64_t)block * kTile, rp.num_points, raw}; }
 };
-
-__global__ __launch_bounds__(256) void nerfrender_trunk_kernel(RayPoints rp, int multires, const float *__restrict__ packed,
-                                                               float *__restrict__ gbuf, float *__restrict__ raw) {
-  extern __shared__ __align__(16) float act[];
-  const int64_t tile0 = (int64_t)blockIdx.x * kTile;
-  trunk_body(act, packed, multires, 3 + 6 * multires, RaySrc{rp, tile0}, RaySink{tile0, rp.num_points, raw},
-             gbuf + (int64_t)blockIdx.x * (kTile * kHalf));
-}
-
-__global__ __launch_bounds__(256) void nerfrender_trunk_bf16x3_kernel(RayPoints rp, int multires, const float *__restrict__ packed,
-                                                                      const uint4 *__restrict__ split, float *__restrict__ gbuf,
-                                                                      float *__restrict__ raw) {
-  extern __shared__ __align__(16) float act[];
-  const int64_t tile0 = (int64_t)blockIdx.x * kTile;
-  trunk_body<true>(act, packed, multires, 3 + 6 * multires, RaySrc{rp, tile0}, RaySink{tile0, rp.num_points, raw},
-                   gbuf + (int64_t)blockIdx.x * (kTile * kHalf), split);
-}
 
 // ---- head ------------------------------------------------------------------------------------------------------------------------
 // rgb_linear over v = relu(g + c) for one point: g the point's 128 trunk outputs in registers, c[j] the view part of its ray.
@@ -129,11 +110,7 @@ __device__ __forceinline__ void head_tile(const RayPoints &rp, const float *__re
     const float vd[3] = {__fdiv_rn(d[0], n), __fdiv_rn(d[1], n), __fdiv_rn(d[2], n)};
     for (int a = 0; a < 3; ++a) emb[t][a] = vd[a];
     for (int l = 0; l < multires_views; ++l)
-      for (int a = 0; a < 3; ++a) {
-        const float arg = vd[a] * ldexpf(1.0f, l);
-        emb[t][3 + 6 * l + a] = sinf(arg);
-        emb[t][3 + 6 * l + 3 + a] = cosf(arg);
-      }
+      for (int a = 0; a < 3; ++a) embed_freq(emb[t], vd[a], l, a);
   }
   __syncthreads();
   for (int idx = t; idx < nr * kHalf; idx += kTile) {
@@ -236,9 +213,8 @@ __global__ void nerfrender_composite_kernel(const float *__restrict__ raw1, cons
 constexpr int64_t kMaxRenderRays = (int64_t)1 << 40, kMaxCamoptRays = (int64_t)1 << 31;
 
 int check_model(const char *who, int multires, int multires_views, int cam_ch) {
-  NRPN_REQUIRE(multires >= 0 && 3 + 6 * multires <= kEnc, "%s: multires %d does not fit %d encoding columns", who, multires, kEnc);
-  NRPN_REQUIRE(multires_views >= 0 && 3 + 6 * multires_views <= kMaxViewsCh && cam_ch >= 0 && cam_ch <= 65536,
-               "%s: multires_views %d / input_ch_cam %d", who, multires_views, cam_ch);
+  NRPN_REQUIRE(model_ok(multires, 0, 0), "%s: multires %d does not fit %d encoding columns", who, multires, kEnc);
+  NRPN_REQUIRE(model_ok(multires, multires_views, cam_ch), "%s: multires_views %d / input_ch_cam %d", who, multires_views, cam_ch);
   return NRPN_OK;
 }
 
@@ -260,7 +236,7 @@ struct RayCall {          // what a render and the camera-embedding objective sh
   void *work;
   int64_t work_bytes;
   hipStream_t stream;
-  const uint4 *split = nullptr;       // the bf16x3 planes of packed: the trunk then runs in that arithmetic (renders only)
+  const uint4 *split = nullptr;       // the bf16x3 planes of packed: the trunk then runs in that arithmetic (renders only); null: fp32
   int64_t chunk_rays() const { return chunk < num_rays ? chunk : num_rays; }
   int64_t chunks() const { return cdiv64(num_rays, chunk_rays()); }
 };
@@ -272,15 +248,11 @@ int check_call(const char *who, const RayCall &c, int64_t max_rays) {
   return NRPN_OK;
 }
 
-// after check_call: the work buffer holds ``need`` bytes and the trunk may have its LDS
+// after check_call: the work buffer holds ``need`` bytes
 int check_work(const char *who, const RayCall &c, int64_t need) {
   NRPN_REQUIRE(c.work_bytes >= need, "%s: work buffer of %lld bytes is too small", who, (long long)c.work_bytes);
-  NRPN_LDS(nerfrender_trunk_kernel, kLdsBytes);
-  if (c.split) NRPN_LDS(nerfrender_trunk_bf16x3_kernel, kLdsBytes);
   return NRPN_OK;
 }
-
-int64_t align16(int64_t b) { return (b + 15) / 16 * 16; }
 
 struct PassLayout {       // of a chunk's two passes in the work buffer, in bytes; every part 16-byte aligned
   int64_t raw1, raw2, z2, gbuf, end;      // z2: the drawn samples, where the caller keeps them here
@@ -321,16 +293,9 @@ Chunk chunk_at(const RayCall &c, int64_t ci, const float *rays, bool rays_whole,
   return k;
 }
 
-int launch_trunk(const RayCall &c, const RayPoints &rp, float *gbuf, float *raw) {
-  if (c.split) {
-    nerfrender_trunk_bf16x3_kernel<<<(int)cdiv64(rp.num_points, kTile), 256, kLdsBytes, c.stream>>>(rp, c.multires, c.packed, c.split, gbuf,
-                                                                                                  raw);
-    NRPN_LAUNCH_CHECK("nerfrender_trunk_bf16x3_kernel");
-    return NRPN_OK;
-  }
-  nerfrender_trunk_kernel<<<(int)cdiv64(rp.num_points, kTile), 256, kLdsBytes, c.stream>>>(rp, c.multires, c.packed, gbuf, raw);
-  NRPN_LAUNCH_CHECK("nerfrender_trunk_kernel");
-  return NRPN_OK;
+// the trunk over pass ``pass`` of a chunk, in the call's arithmetic
+int trunk_pass(const RayCall &c, const Chunk &k, int pass, float *gbuf, float *raw) {
+  return launch_trunk(RayTile{k.rp[pass], c.multires, raw}, k.tiles[pass], c.packed, c.split, gbuf, c.stream);
 }
 
 struct RenderCall : RayCall {
@@ -346,7 +311,7 @@ struct RenderCall : RayCall {
 };
 
 int mlp_pass(const RenderCall &c, const Chunk &k, int pass, float *gbuf, float *raw) {
-  if (int rc = launch_trunk(c, k.rp[pass], gbuf, raw)) return rc;
+  if (int rc = trunk_pass(c, k, pass, gbuf, raw)) return rc;
   nerfrender_head_kernel<<<k.tiles[pass], kTile, 0, c.stream>>>(k.rp[pass], c.packed, c.w_view, c.b_view, c.cam, c.multires_views,
                                                                 c.cam_ch, gbuf, raw);
   NRPN_LAUNCH_CHECK("nerfrender_head_kernel");
@@ -389,31 +354,27 @@ int render(const RenderCall &c) {
   return NRPN_OK;
 }
 
-// the two entries of a render; kSplit: the planes are required and the trunk runs in the bf16x3 arithmetic
-template <bool kSplit>
+// the two entries of a render; split: the bf16x3 planes of packed, or null for the fp32 trunk
 int render_rays(const float *rays, int64_t num_rays, float near, float far, float center_x, float center_y, float center_z, float bb_scale,
                 int multires, int multires_views, int input_ch_cam, const float *packed, const void *split, const float *w_view,
                 const float *b_view, const float *embedded_cam, const float *z1, int s1, int z2_mode, const float *z2_in, int s2,
                 int64_t chunk, void *work, int64_t work_bytes, const CompositeOut &out, float *raw1_out, float *z2_out,
                 nrpn_stream_t stream) {
   NRPN_REQUIRE(rays, "nerfrender_rays: null rays");
-  NRPN_REQUIRE(!kSplit || split, "nerfrender_rays: null planes");
   RenderCall c{{num_rays, center_x, center_y, center_z, bb_scale, multires, packed, z1, s1, s2, chunk, work, work_bytes, as_stream(stream),
-                kSplit ? static_cast<const uint4 *>(split) : nullptr},
+                static_cast<const uint4 *>(split)},
                rays, nullptr, 0, near, far, multires_views, input_ch_cam, w_view, b_view, embedded_cam, z2_mode, z2_in, out, raw1_out, z2_out};
   return render(c);
 }
 
-template <bool kSplit>
 int render_frame(int height, int width, const float *camera, float near, float far, float center_x, float center_y, float center_z,
                  float bb_scale, int multires, int multires_views, int input_ch_cam, const float *packed, const void *split,
                  const float *w_view, const float *b_view, const float *embedded_cam, const float *z1, int s1, int z2_mode,
                  const float *z2_in, int s2, int64_t chunk, void *work, int64_t work_bytes, const CompositeOut &out, float *raw1_out,
                  float *z2_out, nrpn_stream_t stream) {
   NRPN_REQUIRE(camera && height >= 1 && width >= 1, "nerfrender_frame: camera / %d x %d", height, width);
-  NRPN_REQUIRE(!kSplit || split, "nerfrender_frame: null planes");
   RenderCall c{{(int64_t)height * width, center_x, center_y, center_z, bb_scale, multires, packed, z1, s1, s2, chunk, work, work_bytes,
-                as_stream(stream), kSplit ? static_cast<const uint4 *>(split) : nullptr},
+                as_stream(stream), static_cast<const uint4 *>(split)},
                nullptr, camera, width, near, far, multires_views, input_ch_cam, w_view, b_view, embedded_cam, z2_mode, z2_in, out, raw1_out,
                z2_out};
   return render(c);
@@ -635,13 +596,13 @@ int camopt_prepare(const CamoptCall &c, const float *camera, int W, float near, 
       nerfrender_rays_kernel<<<k.blocks, 64, 0, c.stream>>>(camera, W, k.r0, k.n, rays_out + k.r0 * 6);
       NRPN_LAUNCH_CHECK("nerfrender_rays_kernel");
     }
-    if (int rc = launch_trunk(c, k.rp[0], c.g_of(lay, ci, 0), raw1)) return rc;
+    if (int rc = trunk_pass(c, k, 0, c.g_of(lay, ci, 0), raw1)) return rc;
     if (draw_z2) {
       nerfrender_sample_kernel<<<k.blocks, 64, 0, c.stream>>>(raw1, k.rays, c.z1, c.s1, near, far, k.n, z2_out + k.r0 * c.s2);
       NRPN_LAUNCH_CHECK("nerfrender_sample_kernel");
     }
     if (k.z2)
-      if (int rc = launch_trunk(c, k.rp[1], c.g_of(lay, ci, 1), raw2)) return rc;
+      if (int rc = trunk_pass(c, k, 1, c.g_of(lay, ci, 1), raw2)) return rc;
     nerfcamopt_weights_kernel<<<k.blocks, 64, 0, c.stream>>>(raw1, c.z1, c.s1, raw2, k.zb, c.s2, k.rays, k.n, w1 + k.r0 * c.s1,
                                                              c.s2 ? w2 + k.r0 * c.s2 : w1);
     NRPN_LAUNCH_CHECK("nerfcamopt_weights_kernel");
@@ -667,7 +628,7 @@ int camopt_eval(const CamoptCall &c, int multires_views, int cam_ch, const float
     for (int pass = 0; pass < (c.s2 ? 2 : 1); ++pass) {
       float *g = c.g_of(lay, ci, pass);
       if (ci >= c.cached_chunks)        // the same kernel on the same points as in prepare: the same g
-        if (int rc = launch_trunk(c, k.rp[pass], g, raws[pass])) return rc;
+        if (int rc = trunk_pass(c, k, pass, g, raws[pass])) return rc;
       nerfcamopt_head_kernel<<<k.tiles[pass], kTile, 0, c.stream>>>(k.rp[pass], c.packed, w_view, b_view, cam, multires_views, cam_ch, g,
                                                                     raws[pass], masks[pass]);
       NRPN_LAUNCH_CHECK("nerfcamopt_head_kernel");
@@ -717,9 +678,9 @@ int nrpn_nerfrender_rays(const float *rays, int64_t num_rays, float near, float 
                          const float *b_view, const float *embedded_cam, const float *z1, int s1, int z2_mode, const float *z2_in, int s2,
                          int64_t chunk, void *work, int64_t work_bytes, float *rgb, float *depth, float *acc, float *disp,
                          float *depth_std, float *z_vals, float *weights, float *raw1_out, float *z2_out, nrpn_stream_t stream) {
-  return render_rays<false>(rays, num_rays, near, far, center_x, center_y, center_z, bb_scale, multires, multires_views, input_ch_cam,
-                            packed, nullptr, w_view, b_view, embedded_cam, z1, s1, z2_mode, z2_in, s2, chunk, work, work_bytes,
-                            CompositeOut{rgb, depth, acc, disp, depth_std, z_vals, weights}, raw1_out, z2_out, stream);
+  return render_rays(rays, num_rays, near, far, center_x, center_y, center_z, bb_scale, multires, multires_views, input_ch_cam, packed,
+                     nullptr, w_view, b_view, embedded_cam, z1, s1, z2_mode, z2_in, s2, chunk, work, work_bytes,
+                     CompositeOut{rgb, depth, acc, disp, depth_std, z_vals, weights}, raw1_out, z2_out, stream);
 }
 
 int nrpn_nerfrender_rays_bf16x3(const float *rays, int64_t num_rays, float near, float far, float center_x, float center_y,
@@ -728,9 +689,10 @@ int nrpn_nerfrender_rays_bf16x3(const float *rays, int64_t num_rays, float near,
                                 int s1, int z2_mode, const float *z2_in, int s2, int64_t chunk, void *work, int64_t work_bytes,
                                 float *rgb, float *depth, float *acc, float *disp, float *depth_std, float *z_vals, float *weights,
                                 float *raw1_out, float *z2_out, nrpn_stream_t stream) {
-  return render_rays<true>(rays, num_rays, near, far, center_x, center_y, center_z, bb_scale, multires, multires_views, input_ch_cam,
-                           packed, split, w_view, b_view, embedded_cam, z1, s1, z2_mode, z2_in, s2, chunk, work, work_bytes,
-                           CompositeOut{rgb, depth, acc, disp, depth_std, z_vals, weights}, raw1_out, z2_out, stream);
+  NRPN_REQUIRE(split, "nerfrender_rays: null planes");
+  return render_rays(rays, num_rays, near, far, center_x, center_y, center_z, bb_scale, multires, multires_views, input_ch_cam, packed,
+                     split, w_view, b_view, embedded_cam, z1, s1, z2_mode, z2_in, s2, chunk, work, work_bytes,
+                     CompositeOut{rgb, depth, acc, disp, depth_std, z_vals, weights}, raw1_out, z2_out, stream);
 }
 
 int nrpn_nerfrender_frame(int height, int width, const float *camera, float near, float far, float center_x, float center_y,
@@ -739,9 +701,9 @@ int nrpn_nerfrender_frame(int height, int width, const float *camera, float near
                           const float *z2_in, int s2, int64_t chunk, void *work, int64_t work_bytes, float *rgb, float *depth, float *acc,
                           float *disp, float *depth_std, float *z_vals, float *weights, float *raw1_out, float *z2_out,
                           nrpn_stream_t stream) {
-  return render_frame<false>(height, width, camera, near, far, center_x, center_y, center_z, bb_scale, multires, multires_views,
-                             input_ch_cam, packed, nullptr, w_view, b_view, embedded_cam, z1, s1, z2_mode, z2_in, s2, chunk, work,
-                             work_bytes, CompositeOut{rgb, depth, acc, disp, depth_std, z_vals, weights}, raw1_out, z2_out, stream);
+  return render_frame(height, width, camera, near, far, center_x, center_y, center_z, bb_scale, multires, multires_views, input_ch_cam,
+                      packed, nullptr, w_view, b_view, embedded_cam, z1, s1, z2_mode, z2_in, s2, chunk, work, work_bytes,
+                      CompositeOut{rgb, depth, acc, disp, depth_std, z_vals, weights}, raw1_out, z2_out, stream);
 }
 
 int nrpn_nerfrender_frame_bf16x3(int height, int width, const float *camera, float near, float far, float center_x, float center_y,
@@ -750,9 +712,10 @@ int nrpn_nerfrender_frame_bf16x3(int height, int width, const float *camera, flo
                                  int s1, int z2_mode, const float *z2_in, int s2, int64_t chunk, void *work, int64_t work_bytes,
                                  float *rgb, float *depth, float *acc, float *disp, float *depth_std, float *z_vals, float *weights,
                                  float *raw1_out, float *z2_out, nrpn_stream_t stream) {
-  return render_frame<true>(height, width, camera, near, far, center_x, center_y, center_z, bb_scale, multires, multires_views,
-                            input_ch_cam, packed, split, w_view, b_view, embedded_cam, z1, s1, z2_mode, z2_in, s2, chunk, work,
-                            work_bytes, CompositeOut{rgb, depth, acc, disp, depth_std, z_vals, weights}, raw1_out, z2_out, stream);
+  NRPN_REQUIRE(split, "nerfrender_frame: null planes");
+  return render_frame(height, width, camera, near, far, center_x, center_y, center_z, bb_scale, multires, multires_views, input_ch_cam,
+                      packed, split, w_view, b_view, embedded_cam, z1, s1, z2_mode, z2_in, s2, chunk, work, work_bytes,
+                      CompositeOut{rgb, depth, acc, disp, depth_std, z_vals, weights}, raw1_out, z2_out, stream);
 }
 
 int64_t nrpn_nerfcamopt_work_bytes(int what, int64_t num_rays, int64_t chunk_rays, int s1, int s2) {

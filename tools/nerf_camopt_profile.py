@@ -24,12 +24,12 @@ for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
         sys.path.insert(0, p)
 
 import nerf_extract_ref as R  # noqa: E402
-from nerf_profile import kernel_times, timed  # noqa: E402
+from nerf_profile import kernel_times, timed, trunk_kernel  # noqa: E402
 from nerf_render_profile import FRAME, N_SAMPLES  # noqa: E402
 
 ATTAINABLE_TBPS = (6.0, 6.3)
 KERNELS = ("nerfcamopt_head_kernel", "nerfcamopt_colour_kernel", "nerfcamopt_backward_kernel", "nerfcamopt_sum_rows_kernel",
-           "nerfcamopt_finish_kernel", "nerfrender_trunk_kernel", "Memcpy")
+           "nerfcamopt_finish_kernel", trunk_kernel("RayTile"), "Memcpy")
 
 
 def main():

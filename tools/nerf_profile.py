@@ -32,6 +32,13 @@ def window_times(fn, repeats):
     return out
 
 
+def trunk_kernel(tile, arithmetic="fp32"):
+    """The family (see kernel_times) of one instantiation of nerf_mlp.cuh's trunk_kernel<kSplit, Tile>, as the profiler spells it.
+    tile: the consumer's Tile -- GridTile (nerfgrid.hip), RayTile (nerfrender.hip), PointTile or KeepTile (nerfquery.hip: the forward,
+    and the backward's trunk that keeps its activations).  Neither the two arithmetics nor two tiles share a family."""
+    return "trunk_kernel<%s, (anonymous namespace)::%s>" % ("true" if arithmetic == "bf16x3" else "false", tile)
+
+
 def kernel_times(fn, kernels):
     """Device time in ms per kernel family (a substring of the kernel's name) of one call of fn, from torch.profiler; None if the
     profiler records nothing of the first family."""

@@ -23,10 +23,10 @@ for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
         sys.path.insert(0, p)
 
 import nerf_extract_ref as R  # noqa: E402
-from nerf_profile import kernel_times, timed  # noqa: E402
+from nerf_profile import kernel_times, timed, trunk_kernel  # noqa: E402
 
 RAYS, SAMPLES = 1024, 256
-KERNELS = ("nerfquery_trunk_keep_kernel", "nerfquery_trunk_kernel", "nerfquery_head_kernel", "nerfquery_headbwd_kernel",
+KERNELS = (trunk_kernel("KeepTile"), trunk_kernel("PointTile"), "nerfquery_head_kernel", "nerfquery_headbwd_kernel",
            "nerfquery_dgrad_kernel", "nerfquery_wgrad_kernel", "nerfquery_reduce_kernel", "nerfquery_finish_kernel",
            "nerfquery_pack_t_kernel", "nerfgrid_pack_kernel", "nerfquery_rays_kernel")
 
@@ -75,7 +75,7 @@ def main():
         except Exception as e:      # the profiler is optional: the event times stand without it
             km, rec["note"] = None, f"torch.profiler failed: {type(e).__name__}"
         if km:
-            # "nerfquery_trunk_kernel" is no substring of the keep kernel's name, so the families do not overlap
+            # the two trunk families name different tiles, so they do not overlap
             rec["kernel_ms"] = {k: round(v, 3) for k, v in km.items()}
 
         model = R.build_model(state, cfg).to(dev).train()

@@ -21,13 +21,14 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
         sys.path.insert(0, p)
 
 import nerf_extract_ref as R  # noqa: E402
-from nerf_profile import kernel_times, timed  # noqa: E402
+from nerf_profile import kernel_times, timed, trunk_kernel  # noqa: E402
 
 FRAME = (468, 624)
 N_SAMPLES = 256
 PEAK_TFLOPS = 157.0
 TRUNK_FLOP_PER_POINT = 2 * (57 * 256 + 4 * 256 * 256 + 313 * 256 + 2 * 256 * 256 + 256 * 256 + 256 + 256 * 128)
-KERNELS = ("nerfrender_trunk_kernel", "nerfrender_head_kernel", "nerfrender_sample_kernel", "nerfrender_composite_kernel",
+TRUNK = trunk_kernel("RayTile")
+KERNELS = (TRUNK, "nerfrender_head_kernel", "nerfrender_sample_kernel", "nerfrender_composite_kernel",
            "nerfrender_rays_kernel")
 
 
@@ -59,7 +60,7 @@ def main():
         except Exception as e:      # the profiler is optional: the event times above stand without it
             km, rec["note"] = None, f"torch.profiler failed: {type(e).__name__}"
         if km:
-            trunk = km["nerfrender_trunk_kernel"]
+            trunk = km[TRUNK]
             tf = points * TRUNK_FLOP_PER_POINT / (trunk * 1e-3) / 1e12
             rec.update(kernel_ms={k: round(v, 3) for k, v in km.items()}, trunk_share_of_kernel_time=round(trunk / sum(km.values()), 4),
                        trunk_tflops=round(tf, 2), trunk_fraction_of_peak=round(tf / PEAK_TFLOPS, 3))

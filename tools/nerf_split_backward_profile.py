@@ -26,11 +26,11 @@ for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
         sys.path.insert(0, p)
 
 import nerf_train_ref as T  # noqa: E402
-from nerf_profile import kernel_times, window_times  # noqa: E402
+from nerf_profile import kernel_times, trunk_kernel, window_times  # noqa: E402
 
 RAYS, S, H, W, NEAR, FAR = 1024, 128, 468, 624, 0.1, 4.0
 SWITCH = ("fp32", "bf16x3")
-FAMILIES = ("nerfquery_trunk_keep_bf16x3_kernel", "nerfquery_headbwd_kernel", "nerfquery_dgrad_kernel", "nerfquery_dgrad_split_kernel",
+FAMILIES = (trunk_kernel("KeepTile", "bf16x3"), "nerfquery_headbwd_kernel", "nerfquery_dgrad_kernel", "nerfquery_dgrad_split_kernel",
             "nerfquery_wgrad_kernel", "nerfquery_wgrad_split_kernel", "nerfquery_colsum_kernel", "nerfquery_reduce_kernel")
 
 

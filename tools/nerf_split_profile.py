@@ -25,12 +25,12 @@ for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
         sys.path.insert(0, p)
 
 import nerf_train_ref as T  # noqa: E402
-from nerf_profile import kernel_times, timed  # noqa: E402
+from nerf_profile import kernel_times, timed, trunk_kernel  # noqa: E402
 
 RAYS, S, H, W, NEAR, FAR = 1024, 128, 468, 624, 0.1, 4.0
 POINTS = (1 << 16, 1 << 18)
 MODES = ("fp32", "bf16x3")
-TRUNK = {"fp32": "nerfquery_trunk_kernel", "bf16x3": "nerfquery_trunk_bf16x3_kernel"}
+TRUNK = {m: trunk_kernel("PointTile", m) for m in ("fp32", "bf16x3")}
 
 
 def main():
