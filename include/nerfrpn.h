@@ -802,6 +802,35 @@ int nrpn_nerfrender_frame_bf16x3(int height, int width, const float *camera, flo
                                  int s1, int z2_mode, const float *z2_in, int s2, int64_t chunk, void *work, int64_t work_bytes,
                                  float *rgb, float *depth, float *acc, float *disp, float *depth_std, float *z_vals, float *weights,
                                  float *raw1_out, float *z2_out, nrpn_stream_t stream);
+/* nrpn_nerfrender_rays_boxes / nrpn_nerfrender_frame_boxes (scripts/nerf_render_boxes.py): the render of
+ *   nrpn_nerfrender_rays / nrpn_nerfrender_frame (render :82-157, render_rays :514-614) restricted to 3D boxes -- the counterpart, for
+ *   the NeRFs of this library, of the crop boxes nerf_rpn/scripts/proposals2ngp.py :10-196 writes for the instant-ngp viewer.  The
+ *   arguments are those of the fp32 entries, plus: split, the planes of nrpn_nerfgrid_pack_bf16x3 (null: the fp32 trunk); boxes f64
+ *   [num_boxes][8] on the device = centre (3), half extents (3), cos(theta), sin(theta) of the rotation about z, in world
+ *   coordinates (before center / bb_scale), never null (with num_boxes 0 nothing of it is read), num_boxes <= 1024; mode 0: keep, 1:
+ *   remove; skip: not 0 leaves out the trunk and the head of every 64-point tile without a counted point, 0 runs every tile (the
+ *   results are the same bits); tiles_run i64 [2] on the device (may be null): per pass, the tiles whose trunk ran, summed over the
+ *   chunks.  A sample's world point is the float32 o + d z of the plain render; it is inside a box if, in float64, |R(-theta)(p -
+ *   c)| <= the half extent on every axis.  It counts if it is inside at least one box (keep) or none (remove).  After the head of
+ *   each pass the four raw values of every sample that does not count are +0: it has no density and weight 0, the second list is
+ *   drawn from the masked first pass and masked again; raw1_out is the masked raw.  A ray without a counted sample gets rgb,
+ *   depth and acc 0 and disp 0 / 0.  work: nrpn_nerfrender_boxes_work_bytes(min(chunk, num_rays), s1, s2) bytes (the plain render's
+ *   scratch, a byte per point and a flag per tile), 16-byte aligned; -1 for sizes outside the supported range. */
+int64_t nrpn_nerfrender_boxes_work_bytes(int64_t chunk_rays, int s1, int s2);
+int nrpn_nerfrender_rays_boxes(const float *rays, int64_t num_rays, float near, float far, float center_x, float center_y, float center_z,
+                               float bb_scale, int multires, int multires_views, int input_ch_cam, const float *packed,
+                               const void *split, const float *w_view, const float *b_view, const float *embedded_cam, const float *z1,
+                               int s1, int z2_mode, const float *z2_in, int s2, int64_t chunk, void *work, int64_t work_bytes, float *rgb,
+                               float *depth, float *acc, float *disp, float *depth_std, float *z_vals, float *weights, float *raw1_out,
+                               float *z2_out, const double *boxes, int num_boxes, int mode, int skip, int64_t *tiles_run,
+                               nrpn_stream_t stream);
+int nrpn_nerfrender_frame_boxes(int height, int width, const float *camera, float near, float far, float center_x, float center_y,
+                                float center_z, float bb_scale, int multires, int multires_views, int input_ch_cam, const float *packed,
+                                const void *split, const float *w_view, const float *b_view, const float *embedded_cam, const float *z1,
+                                int s1, int z2_mode, const float *z2_in, int s2, int64_t chunk, void *work, int64_t work_bytes, float *rgb,
+                                float *depth, float *acc, float *disp, float *depth_std, float *z_vals, float *weights, float *raw1_out,
+                                float *z2_out, const double *boxes, int num_boxes, int mode, int skip, int64_t *tiles_run,
+                                nrpn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Metrics of a rendered view against its ground truth, scripts/nerf_test.py.  [f7]  Replaces what render_images_with_metrics

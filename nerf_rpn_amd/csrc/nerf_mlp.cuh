@@ -10,13 +10,15 @@
 //   src(block)  -> a source:         point(i, p) gives the normalised position of point i of workgroup ``block``'s tile
 //   sink(block) -> a sink:           sigma(i, s) takes alpha_linear's output of that point; optionally keep() (see sink_keeps)
 // Both may refer to the Tile they came from, which outlives them.  g = W_f f of the tile goes to gbuf[block] as [column][point].
-// launch_trunk(tile, tiles, packed, split, gbuf, stream) is the only place that knows there are two arithmetics to launch: the
-// planes ``split`` select bf16x3, null selects fp32.  The point arithmetic of a source stays in its consumer's translation unit: the
+// launch_trunk(tile, tiles, packed, split, gbuf, stream[, flags]) is the only place that knows there are two arithmetics to launch: the
+// planes ``split`` select bf16x3, null selects fp32; per-tile ``flags`` select the sibling kernel that leaves unflagged tiles alone.  The point arithmetic of a source stays in its consumer's translation unit: the
 // three are compiled with different contraction flags (Makefile).
 #pragma once
 #include "common.h"
 
 #include <cmath>
+#include <cstddef>
+#include <type_traits>
 
 namespace nerfmlp {
 
@@ -331,9 +333,37 @@ __global__ __launch_bounds__(256) void trunk_kernel(Tile tile, const float *__re
                      gbuf + (int64_t)blockIdx.x * (kTile * kHalf), split);
 }
 
-// split: the bf16x3 planes of packed, and the trunk runs in that arithmetic; null: in fp32
-template <class Tile>
-int launch_trunk(const Tile &tile, int tiles, const float *packed, const uint4 *split, float *gbuf, hipStream_t stream) {
+// The same kernel for a launch whose tiles carry a flag each (nerfrender.hip: a render restricted to boxes): a workgroup whose tile's
+// flag is 0 returns before the body, so gbuf and the sink get nothing of that tile.  The branch is uniform over the workgroup and comes
+// before any barrier.
+template <bool kSplit, class Tile>
+__global__ __launch_bounds__(256) void trunk_flagged_kernel(Tile tile, const float *__restrict__ packed, const uint4 *__restrict__ split,
+                                                            float *__restrict__ gbuf, const uint32_t *__restrict__ flags) {
+  extern __shared__ __align__(16) float act[];
+  if (flags[blockIdx.x] == 0) return;
+  trunk_body<kSplit>(act, packed, tile.multires, 3 + 6 * tile.multires, tile.src(blockIdx.x), tile.sink(blockIdx.x),
+                     gbuf + (int64_t)blockIdx.x * (kTile * kHalf), split);
+}
+
+// split: the bf16x3 planes of packed, and the trunk runs in that arithmetic; null: in fp32.  flags: one uint32 per tile, and only the
+// tiles whose flag is not 0 run (trunk_flagged_kernel); null, or no argument at all, launches trunk_kernel over every tile.  A caller
+// that never passes flags does not instantiate the flagged kernel.
+template <class Tile, class Flags = std::nullptr_t>
+int launch_trunk(const Tile &tile, int tiles, const float *packed, const uint4 *split, float *gbuf, hipStream_t stream,
+                 Flags flags = nullptr) {
+  if constexpr (!std::is_same_v<Flags, std::nullptr_t>) {
+    if (flags) {
+      if (split) {
+        NRPN_LDS((trunk_flagged_kernel<true, Tile>), kLdsBytes);
+        trunk_flagged_kernel<true, Tile><<<tiles, 256, kLdsBytes, stream>>>(tile, packed, split, gbuf, flags);
+      } else {
+        NRPN_LDS((trunk_flagged_kernel<false, Tile>), kLdsBytes);
+        trunk_flagged_kernel<false, Tile><<<tiles, 256, kLdsBytes, stream>>>(tile, packed, nullptr, gbuf, flags);
+      }
+      NRPN_LAUNCH_CHECK("nerfmlp_trunk_flagged_kernel");
+      return NRPN_OK;
+    }
+  }
   if (split) {
     NRPN_LDS((trunk_kernel<true, Tile>), kLdsBytes);
     trunk_kernel<true, Tile><<<tiles, 256, kLdsBytes, stream>>>(tile, packed, split, gbuf);

@@ -147,6 +147,82 @@ __global__ __launch_bounds__(kTile) void nerfrender_head_kernel(RayPoints rp, co
   head_tile<false>(rp, packed, w_view, b_view, cam, multires_views, cam_ch, gbuf, raw, nullptr);
 }
 
+// ---- boxes (scripts/nerf_render_boxes.py) ------------------------------------------------------------------------
+// A render restricted to K boxes counts a sample if its world point lies in at least one box (keep) or in none (remove); the raw
+// values of every other sample become +0, so it has no density and no weight.  A box is 8 doubles: centre, half extents, cos(theta),
+// sin(theta) of its rotation about z.  Per pass of a chunk:
+//   boxmask   one wave per tile of the pass: a byte per point (counted or not) and a flag per tile (any point counted)
+//   trunk     the flagged sibling of the trunk kernel and the flagged head below: a tile whose flag is 0 runs neither
+//   boxzero   +0 into raw of every point whose byte is 0, points of skipped tiles included
+constexpr int kMaxBoxes = 1024;
+
+// The world point of a sample is RaySrc's o + d z before the normalisation, the same float32 operations; the test is float64 and
+// closed: |R(-theta)(p - c)| <= half extent on each axis.  The box table is read through wave-uniform addresses.  A partial last
+// tile tests only its valid points.
+__global__ __launch_bounds__(kTile) void nerfrender_boxmask_kernel(RayPoints rp, const double *__restrict__ boxes, int num_boxes,
+                                                                   int remove, uint8_t *__restrict__ counted,
+                                                                   uint32_t *__restrict__ flags) {
+  const int t = threadIdx.x;
+  const int64_t pi = (int64_t)blockIdx.x * kTile + t;
+  const bool valid = pi < rp.num_points;
+  const int64_t pc = valid ? pi : rp.num_points - 1;
+  const int64_t ray = pc / rp.S;
+  const int s = (int)(pc - ray * rp.S);
+  const float zv = rp.z[ray * rp.z_stride + s];
+  const float *o = rp.rays + ray * 6;
+  double p[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) p[a] = (double)__fadd_rn(o[a], __fmul_rn(o[3 + a], zv));
+  bool in = false;
+  for (int k = 0; k < num_boxes; ++k) {
+    const double *b = boxes + (int64_t)k * 8;
+    const double dx = p[0] - b[0], dy = p[1] - b[1], dz = p[2] - b[2];
+    const double u = b[6] * dx + b[7] * dy, v = b[6] * dy - b[7] * dx;
+    in = in || (fabs(u) <= b[3] && fabs(v) <= b[4] && fabs(dz) <= b[5]);
+  }
+  const bool c = valid && (remove ? !in : in);
+  if (valid) counted[pi] = c ? 1 : 0;
+  const bool any = __ballot(c) != 0ull;
+  if (t == 0) flags[blockIdx.x] = any ? 1u : 0u;
+}
+
+// the head of the box path: as nerfrender_head_kernel, for the tiles whose flag is not 0
+__global__ __launch_bounds__(kTile) void nerfrender_head_flagged_kernel(RayPoints rp, const float *__restrict__ packed,
+                                                                        const float *__restrict__ w_view,
+                                                                        const float *__restrict__ b_view, const float *__restrict__ cam,
+                                                                        int multires_views, int cam_ch, const float *__restrict__ gbuf,
+                                                                        float *__restrict__ raw, const uint32_t *__restrict__ flags) {
+  if (flags[blockIdx.x] == 0) return;
+  head_tile<false>(rp, packed, w_view, b_view, cam, multires_views, cam_ch, gbuf, raw, nullptr);
+}
+
+// raw [points][4]: +0 to the four values of every point that does not count
+__global__ __launch_bounds__(256) void nerfrender_boxzero_kernel(const uint8_t *__restrict__ counted, int64_t num_points,
+                                                                 float *__restrict__ raw) {
+  const int64_t pi = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (pi < num_points && counted[pi] == 0) *reinterpret_cast<float4 *>(raw + pi * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// tiles_run[pass] = the tiles of the chunk's pass that ran (every tile without skip, else those flagged), added to what the earlier
+// chunks left there; one workgroup per pass, fixed-order sums
+__global__ __launch_bounds__(256) void nerfrender_boxcount_kernel(const uint32_t *__restrict__ flags1, int tiles1,
+                                                                  const uint32_t *__restrict__ flags2, int tiles2, int skip, int first,
+                                                                  int64_t *__restrict__ tiles_run) {
+  __shared__ int64_t part[256];
+  const int t = threadIdx.x, pass = blockIdx.x;
+  const uint32_t *flags = pass ? flags2 : flags1;
+  const int n = pass ? tiles2 : tiles1;
+  int64_t a = 0;
+  for (int i = t; i < n; i += 256) a += skip ? (int64_t)(flags[i] != 0) : 1;
+  part[t] = a;
+  __syncthreads();
+  for (int w = 128; w >= 1; w >>= 1) {
+    if (t < w) part[t] += part[t + w];
+    __syncthreads();
+  }
+  if (t == 0) tiles_run[pass] = (first ? 0 : tiles_run[pass]) + part[0];
+}
+
 // ---- per-ray reductions, float64 ---------------------------------------------------------------------------------------------
 // raw [rays][S][4], z [S] shared, rays [rays][6] -> z2 [rays][S]; Bins and the depth / variance walk are nerf_ray.cuh's
 __global__ void nerfrender_sample_kernel(const float *__restrict__ raw, const float *__restrict__ rays, const float *__restrict__ z, int S,
@@ -270,6 +346,19 @@ PassLayout pass_layout(int64_t at, int64_t chunk, int s1, int s2, bool with_z2) 
 // a render's work buffer: the chunk's generated rays at byte 0, then the passes
 PassLayout render_layout(int64_t chunk, int s1, int s2) { return pass_layout(align16(chunk * 6 * 4), chunk, s1, s2, true); }
 
+struct BoxLayout : PassLayout {       // a render's work buffer followed by what the box path keeps per pass
+  int64_t counted[2], flags[2], total;      // a byte per point, a uint32 per tile
+};
+BoxLayout box_layout(int64_t chunk, int s1, int s2) {
+  BoxLayout l{render_layout(chunk, s1, s2)};
+  l.counted[0] = l.end;
+  l.counted[1] = l.counted[0] + align16(chunk * s1);
+  l.flags[0] = l.counted[1] + align16(chunk * s2);
+  l.flags[1] = l.flags[0] + align16(cdiv64(chunk * s1, kTile) * 4);
+  l.total = l.flags[1] + align16(cdiv64(chunk * s2, kTile) * 4);
+  return l;
+}
+
 struct Chunk {
   int64_t r0;               // its first ray
   int n, blocks;            // rays; workgroups of the one-thread-per-ray kernels
@@ -293,9 +382,9 @@ Chunk chunk_at(const RayCall &c, int64_t ci, const float *rays, bool rays_whole,
   return k;
 }
 
-// the trunk over pass ``pass`` of a chunk, in the call's arithmetic
-int trunk_pass(const RayCall &c, const Chunk &k, int pass, float *gbuf, float *raw) {
-  return launch_trunk(RayTile{k.rp[pass], c.multires, raw}, k.tiles[pass], c.packed, c.split, gbuf, c.stream);
+// the trunk over pass ``pass`` of a chunk, in the call's arithmetic; flags: of the pass's tiles, and only the flagged ones run
+int trunk_pass(const RayCall &c, const Chunk &k, int pass, float *gbuf, float *raw, const uint32_t *flags = nullptr) {
+  return launch_trunk(RayTile{k.rp[pass], c.multires, raw}, k.tiles[pass], c.packed, c.split, gbuf, c.stream, flags);
 }
 
 struct RenderCall : RayCall {
@@ -308,13 +397,42 @@ struct RenderCall : RayCall {
   const float *z2_in;
   CompositeOut out;
   float *raw1_out, *z2_out;
+  // a render restricted to boxes: the table [num_boxes][8] (null: the plain render), keep or remove, whether tiles without a counted
+  // point are skipped, and where the count of the tiles that ran goes (may be null)
+  const double *boxes = nullptr;
+  int num_boxes = 0, remove = 0, skip = 0;
+  int64_t *tiles_run = nullptr;
 };
 
-int mlp_pass(const RenderCall &c, const Chunk &k, int pass, float *gbuf, float *raw) {
-  if (int rc = trunk_pass(c, k, pass, gbuf, raw)) return rc;
-  nerfrender_head_kernel<<<k.tiles[pass], kTile, 0, c.stream>>>(k.rp[pass], c.packed, c.w_view, c.b_view, c.cam, c.multires_views,
-                                                                c.cam_ch, gbuf, raw);
-  NRPN_LAUNCH_CHECK("nerfrender_head_kernel");
+struct BoxBufs {          // of the work buffer, per pass; null without boxes
+  uint8_t *counted[2];
+  uint32_t *flags[2];
+};
+
+int mlp_pass(const RenderCall &c, const Chunk &k, int pass, float *gbuf, float *raw, const BoxBufs &bb) {
+  if (!c.boxes) {
+    if (int rc = trunk_pass(c, k, pass, gbuf, raw)) return rc;
+    nerfrender_head_kernel<<<k.tiles[pass], kTile, 0, c.stream>>>(k.rp[pass], c.packed, c.w_view, c.b_view, c.cam, c.multires_views,
+                                                                  c.cam_ch, gbuf, raw);
+    NRPN_LAUNCH_CHECK("nerfrender_head_kernel");
+    return NRPN_OK;
+  }
+  nerfrender_boxmask_kernel<<<k.tiles[pass], kTile, 0, c.stream>>>(k.rp[pass], c.boxes, c.num_boxes, c.remove, bb.counted[pass],
+                                                                   bb.flags[pass]);
+  NRPN_LAUNCH_CHECK("nerfrender_boxmask_kernel");
+  const uint32_t *flags = c.skip ? bb.flags[pass] : nullptr;
+  if (int rc = trunk_pass(c, k, pass, gbuf, raw, flags)) return rc;
+  if (flags) {
+    nerfrender_head_flagged_kernel<<<k.tiles[pass], kTile, 0, c.stream>>>(k.rp[pass], c.packed, c.w_view, c.b_view, c.cam,
+                                                                          c.multires_views, c.cam_ch, gbuf, raw, flags);
+    NRPN_LAUNCH_CHECK("nerfrender_head_flagged_kernel");
+  } else {
+    nerfrender_head_kernel<<<k.tiles[pass], kTile, 0, c.stream>>>(k.rp[pass], c.packed, c.w_view, c.b_view, c.cam, c.multires_views,
+                                                                  c.cam_ch, gbuf, raw);
+    NRPN_LAUNCH_CHECK("nerfrender_head_kernel");
+  }
+  nerfrender_boxzero_kernel<<<(unsigned)cdiv64(k.rp[pass].num_points, 256), 256, 0, c.stream>>>(bb.counted[pass], k.rp[pass].num_points, raw);
+  NRPN_LAUNCH_CHECK("nerfrender_boxzero_kernel");
   return NRPN_OK;
 }
 
@@ -325,9 +443,15 @@ int render(const RenderCall &c) {
   NRPN_REQUIRE(c.out.rgb && c.out.depth && c.out.acc && c.out.disp && c.out.depth_std, "nerfrender: null output");
   if (int rc = check_model("nerfrender", c.multires, c.multires_views, c.cam_ch)) return rc;
   if (int rc = check_samples("nerfrender", c.z2_mode, c.s1, c.s2, c.z2_in)) return rc;
-  const PassLayout lay = render_layout(c.chunk_rays(), c.s1, c.s2);
-  if (int rc = check_work("nerfrender", c, lay.end)) return rc;
+  const BoxLayout lay = box_layout(c.chunk_rays(), c.s1, c.s2);
+  if (int rc = check_work("nerfrender", c, c.boxes ? lay.total : lay.end)) return rc;
   char *wk = static_cast<char *>(c.work);
+  BoxBufs bb{};
+  if (c.boxes)
+    for (int pass = 0; pass < 2; ++pass) {
+      bb.counted[pass] = reinterpret_cast<uint8_t *>(wk + lay.counted[pass]);
+      bb.flags[pass] = reinterpret_cast<uint32_t *>(wk + lay.flags[pass]);
+    }
   float *gen = reinterpret_cast<float *>(wk), *gbuf = reinterpret_cast<float *>(wk + lay.gbuf);
   float *raw2 = reinterpret_cast<float *>(wk + lay.raw2);
   // drawn samples go to z2_out or, a chunk at a time, to the work buffer
@@ -340,17 +464,36 @@ int render(const RenderCall &c) {
       NRPN_LAUNCH_CHECK("nerfrender_rays_kernel");
     }
     float *raw1 = c.raw1_out ? c.raw1_out + k.r0 * c.s1 * 4 : reinterpret_cast<float *>(wk + lay.raw1);
-    if (int rc = mlp_pass(c, k, 0, gbuf, raw1)) return rc;
+    if (int rc = mlp_pass(c, k, 0, gbuf, raw1, bb)) return rc;
     if (c.z2_mode == 1) {
       nerfrender_sample_kernel<<<k.blocks, 64, 0, c.stream>>>(raw1, k.rays, c.z1, c.s1, c.near, c.far, k.n,
                                                               const_cast<float *>(k.z2));      // in z2_drawn
       NRPN_LAUNCH_CHECK("nerfrender_sample_kernel");
     }
     if (k.z2)
-      if (int rc = mlp_pass(c, k, 1, gbuf, raw2)) return rc;
+      if (int rc = mlp_pass(c, k, 1, gbuf, raw2, bb)) return rc;
     nerfrender_composite_kernel<<<k.blocks, 64, 0, c.stream>>>(raw1, c.z1, 0, c.s1, raw2, k.zb, c.s2, k.rays, k.n, k.r0, c.out);
     NRPN_LAUNCH_CHECK("nerfrender_composite_kernel");
+    if (c.boxes && c.tiles_run) {
+      nerfrender_boxcount_kernel<<<2, 256, 0, c.stream>>>(bb.flags[0], k.tiles[0], bb.flags[1], k.z2 ? k.tiles[1] : 0, c.skip, ci == 0,
+                                                          c.tiles_run);
+      NRPN_LAUNCH_CHECK("nerfrender_boxcount_kernel");
+    }
   }
+  return NRPN_OK;
+}
+
+struct BoxArgs {          // what the box entries add to a render; boxes null: the plain render
+  const double *boxes = nullptr;
+  int num_boxes = 0, mode = 0, skip = 0;
+  int64_t *tiles_run = nullptr;
+};
+// mode 0: keep, 1: remove
+int with_boxes(const char *who, RenderCall &c, const BoxArgs &b) {
+  if (!b.boxes) return NRPN_OK;
+  NRPN_REQUIRE(b.num_boxes >= 0 && b.num_boxes <= kMaxBoxes, "%s: %d boxes, at most %d are supported", who, b.num_boxes, kMaxBoxes);
+  NRPN_REQUIRE(b.mode == 0 || b.mode == 1, "%s: mode %d (0: keep, 1: remove)", who, b.mode);
+  c.boxes = b.boxes, c.num_boxes = b.num_boxes, c.remove = b.mode, c.skip = b.skip != 0, c.tiles_run = b.tiles_run;
   return NRPN_OK;
 }
 
@@ -359,11 +502,12 @@ int render_rays(const float *rays, int64_t num_rays, float near, float far, floa
                 int multires, int multires_views, int input_ch_cam, const float *packed, const void *split, const float *w_view,
                 const float *b_view, const float *embedded_cam, const float *z1, int s1, int z2_mode, const float *z2_in, int s2,
                 int64_t chunk, void *work, int64_t work_bytes, const CompositeOut &out, float *raw1_out, float *z2_out,
-                nrpn_stream_t stream) {
+                nrpn_stream_t stream, const BoxArgs &box = {}) {
   NRPN_REQUIRE(rays, "nerfrender_rays: null rays");
   RenderCall c{{num_rays, center_x, center_y, center_z, bb_scale, multires, packed, z1, s1, s2, chunk, work, work_bytes, as_stream(stream),
                 static_cast<const uint4 *>(split)},
                rays, nullptr, 0, near, far, multires_views, input_ch_cam, w_view, b_view, embedded_cam, z2_mode, z2_in, out, raw1_out, z2_out};
+  if (int rc = with_boxes("nerfrender_rays_boxes", c, box)) return rc;
   return render(c);
 }
 
@@ -371,12 +515,13 @@ int render_frame(int height, int width, const float *camera, float near, float f
                  float bb_scale, int multires, int multires_views, int input_ch_cam, const float *packed, const void *split,
                  const float *w_view, const float *b_view, const float *embedded_cam, const float *z1, int s1, int z2_mode,
                  const float *z2_in, int s2, int64_t chunk, void *work, int64_t work_bytes, const CompositeOut &out, float *raw1_out,
-                 float *z2_out, nrpn_stream_t stream) {
+                 float *z2_out, nrpn_stream_t stream, const BoxArgs &box = {}) {
   NRPN_REQUIRE(camera && height >= 1 && width >= 1, "nerfrender_frame: camera / %d x %d", height, width);
   RenderCall c{{(int64_t)height * width, center_x, center_y, center_z, bb_scale, multires, packed, z1, s1, s2, chunk, work, work_bytes,
                 as_stream(stream), static_cast<const uint4 *>(split)},
                nullptr, camera, width, near, far, multires_views, input_ch_cam, w_view, b_view, embedded_cam, z2_mode, z2_in, out, raw1_out,
                z2_out};
+  if (int rc = with_boxes("nerfrender_frame_boxes", c, box)) return rc;
   return render(c);
 }
 
@@ -716,6 +861,39 @@ int nrpn_nerfrender_frame_bf16x3(int height, int width, const float *camera, flo
   return render_frame(height, width, camera, near, far, center_x, center_y, center_z, bb_scale, multires, multires_views, input_ch_cam,
                       packed, split, w_view, b_view, embedded_cam, z1, s1, z2_mode, z2_in, s2, chunk, work, work_bytes,
                       CompositeOut{rgb, depth, acc, disp, depth_std, z_vals, weights}, raw1_out, z2_out, stream);
+}
+
+int64_t nrpn_nerfrender_boxes_work_bytes(int64_t chunk_rays, int s1, int s2) {
+  if (!sizes_ok(chunk_rays, kMaxRenderRays, chunk_rays, s1, s2)) return -1;
+  return box_layout(chunk_rays, s1, s2).total;
+}
+
+int nrpn_nerfrender_rays_boxes(const float *rays, int64_t num_rays, float near, float far, float center_x, float center_y, float center_z,
+                               float bb_scale, int multires, int multires_views, int input_ch_cam, const float *packed,
+                               const void *split, const float *w_view, const float *b_view, const float *embedded_cam, const float *z1,
+                               int s1, int z2_mode, const float *z2_in, int s2, int64_t chunk, void *work, int64_t work_bytes, float *rgb,
+                               float *depth, float *acc, float *disp, float *depth_std, float *z_vals, float *weights, float *raw1_out,
+                               float *z2_out, const double *boxes, int num_boxes, int mode, int skip, int64_t *tiles_run,
+                               nrpn_stream_t stream) {
+  NRPN_REQUIRE(boxes, "nerfrender_rays_boxes: null box table (%d boxes)", num_boxes);
+  return render_rays(rays, num_rays, near, far, center_x, center_y, center_z, bb_scale, multires, multires_views, input_ch_cam, packed,
+                     split, w_view, b_view, embedded_cam, z1, s1, z2_mode, z2_in, s2, chunk, work, work_bytes,
+                     CompositeOut{rgb, depth, acc, disp, depth_std, z_vals, weights}, raw1_out, z2_out, stream,
+                     BoxArgs{boxes, num_boxes, mode, skip, tiles_run});
+}
+
+int nrpn_nerfrender_frame_boxes(int height, int width, const float *camera, float near, float far, float center_x, float center_y,
+                                float center_z, float bb_scale, int multires, int multires_views, int input_ch_cam, const float *packed,
+                                const void *split, const float *w_view, const float *b_view, const float *embedded_cam, const float *z1,
+                                int s1, int z2_mode, const float *z2_in, int s2, int64_t chunk, void *work, int64_t work_bytes, float *rgb,
+                                float *depth, float *acc, float *disp, float *depth_std, float *z_vals, float *weights, float *raw1_out,
+                                float *z2_out, const double *boxes, int num_boxes, int mode, int skip, int64_t *tiles_run,
+                                nrpn_stream_t stream) {
+  NRPN_REQUIRE(boxes, "nerfrender_frame_boxes: null box table (%d boxes)", num_boxes);
+  return render_frame(height, width, camera, near, far, center_x, center_y, center_z, bb_scale, multires, multires_views, input_ch_cam,
+                      packed, split, w_view, b_view, embedded_cam, z1, s1, z2_mode, z2_in, s2, chunk, work, work_bytes,
+                      CompositeOut{rgb, depth, acc, disp, depth_std, z_vals, weights}, raw1_out, z2_out, stream,
+                      BoxArgs{boxes, num_boxes, mode, skip, tiles_run});
 }
 
 int64_t nrpn_nerfcamopt_work_bytes(int what, int64_t num_rays, int64_t chunk_rays, int s1, int s2) {

@@ -10,6 +10,7 @@ import math
 from collections import namedtuple
 from types import SimpleNamespace
 
+import numpy as np
 import torch
 
 from . import lib
@@ -2759,6 +2760,124 @@ def nerf_render(weights_or_state, cfg, H=None, W=None, intrinsic=None, c2w=None,
         name, head = a.weights.entry("nerfrender_frame", a.lead[0], a.lead[1], _p(a.camera), *to_packed)
     call(name, *head, *common)
     return {k: (v if k in ("raw1", "z2") else v.reshape(*a.lead, *v.shape[1:])) for k, v in out.items()}
+
+
+NERF_BOX_MODES = ("keep", "remove")
+NERF_MAX_BOXES = 1024
+
+
+def nerf_box_table(boxes):
+    """boxes [K, 7] = (cx, cy, cz, w, l, h, theta), rotated about z by theta (the ``obb`` of scannet_generate_bbox's instance json,
+    proposals2ngp.obb_to_ngp_boxes' convention), or [K, 6] = (min, max) with theta = 0, in the NeRF's world coordinates -> float64
+    numpy [K, 8]: centre, half extents, cos(theta), sin(theta) -- what the kernels and the checker read.  K = 0 is allowed.
+    ValueError for another shape, a value that is not finite, an extent <= 0 or K > 1024."""
+    b = np.asarray(boxes.detach().cpu().numpy() if isinstance(boxes, torch.Tensor) else boxes, dtype=np.float64)
+    if b.ndim == 1 and b.size == 0:
+        b = b.reshape(0, 7)
+    if b.ndim != 2 or b.shape[1] not in (6, 7):
+        raise ValueError(f"boxes of shape {tuple(b.shape)}: expected [K, 7] = (cx, cy, cz, w, l, h, theta) or [K, 6] = (min, max)")
+    if b.shape[0] > NERF_MAX_BOXES:
+        raise ValueError(f"{b.shape[0]} boxes: at most {NERF_MAX_BOXES} are supported")
+    bad = np.argwhere(~np.isfinite(b))
+    if len(bad):
+        k, j = bad[0]
+        raise ValueError(f"box {int(k)} has the value {float(b[k, j])!r} in column {int(j)}")
+    if b.shape[1] == 6:
+        centre, half, theta = (b[:, :3] + b[:, 3:]) * 0.5, (b[:, 3:] - b[:, :3]) * 0.5, np.zeros(len(b))
+    else:
+        centre, half, theta = b[:, :3], b[:, 3:6] * 0.5, b[:, 6]
+    small = np.argwhere(~(half > 0))
+    if len(small):
+        k, j = small[0]
+        raise ValueError(f"box {int(k)} has the extent {float(2 * half[k, j])!r} on axis {int(j)}: extents must be > 0")
+    return np.ascontiguousarray(np.concatenate([centre, half, np.cos(theta)[:, None], np.sin(theta)[:, None]], 1))
+
+
+def nerf_check_box_mode(mode):
+    if mode not in NERF_BOX_MODES:
+        raise ValueError(f"mode {mode!r}: expected 'keep' or 'remove'")
+    return NERF_BOX_MODES.index(mode)
+
+
+def nerf_boxes_to_world(boxes_grid, features):
+    """Proposals in grid coordinates -> boxes in the world coordinates of the NeRF the grid was extracted from.  boxes_grid [K, 7] =
+    (x, y, z, w, l, h, theta) or [K, 6] = (min, max) as run_rpn / run_fcos write them; features: the feature file of nerf_extract (a
+    mapping with resolution, bbox_min, bbox_max, scale, offset, from_ddp_nerf).  Per axis p / resolution * (bbox_max - bbox_min) +
+    bbox_min for centres and corners and the same scale for extents, as proposals2ngp does; theta is kept.  Scenes of instant-ngp
+    (from_ddp_nerf false, or a scale / offset other than 1 / 0) are refused: they keep going through proposals2ngp.  Host numpy."""
+    keys = features.keys() if hasattr(features, "keys") else ()
+    ddp = bool(np.asarray(features["from_ddp_nerf"]).item()) if "from_ddp_nerf" in keys else False
+    if not ddp:
+        raise ValueError("nerf_boxes_to_world: the feature file is not from_ddp_nerf; instant-ngp scenes go through proposals2ngp")
+    scale, offset = np.asarray(features["scale"], dtype=np.float64), np.asarray(features["offset"], dtype=np.float64)
+    if not (np.all(scale == 1.0) and np.all(offset == 0.0)):
+        raise ValueError(f"nerf_boxes_to_world: scale {scale.tolist()!r} / offset {offset.tolist()!r}: expected 1 and 0")
+    b = np.asarray(boxes_grid, dtype=np.float64)
+    if b.ndim == 1 and b.size == 0:
+        b = b.reshape(0, 7)
+    if b.ndim != 2 or b.shape[1] not in (6, 7):
+        raise ValueError(f"nerf_boxes_to_world: boxes of shape {tuple(b.shape)}: expected [K, 7] or [K, 6]")
+    res = np.asarray(features["resolution"], dtype=np.float64).reshape(3)
+    lo, hi = (np.asarray(features[k], dtype=np.float64).reshape(3) for k in ("bbox_min", "bbox_max"))
+    diag = hi - lo
+    if b.shape[1] == 6:
+        return np.concatenate([b[:, :3] / res * diag + lo, b[:, 3:] / res * diag + lo], 1)
+    return np.concatenate([b[:, :3] / res * diag + lo, b[:, 3:6] / res * diag, b[:, 6:]], 1)
+
+
+def nerf_render_boxes(weights_or_state, cfg, boxes, mode="keep", *, skip=True, H=None, W=None, intrinsic=None, c2w=None, rays=None,
+                      near=None, far=None, bb_center=(0., 0., 0.), bb_scale=1., z_samples=None, n_samples=None, lindisp=False,
+                      embedded_cam=None, chunk=None, return_samples=False, z2=None, return_stages=False, dtype=None):
+    """nerf_render restricted to 3D boxes: the scene inside the boxes only (mode "keep": a proposed object, cut out) or with them
+    removed (mode "remove").  boxes: nerf_box_table's input, in the NeRF's world coordinates (before bb_center / bb_scale); every
+    other argument is nerf_render's.  A sample counts if its float32 world point o + d z lies in at least one box (keep) or in none
+    (remove), tested in float64 with closed faces; the raw values of every other sample are +0 after the head of each pass, so the
+    second list is drawn from the masked first pass and the composite gives those samples weight 0.  A ray without a counted sample
+    has rgb, depth and acc 0 and a NaN disp_map (the reference's 0 / 0).  skip: leave out the trunk and head of every 64-point tile
+    without a counted point; False runs every tile and gives the same bits.
+
+    Returns nerf_render's dict (return_samples / return_stages included; raw1 is the masked raw) plus tiles_total and tiles_run:
+    int64 device tensors [2], the 64-point tiles of each pass over all chunks and those whose trunk ran."""
+    table = nerf_box_table(boxes)
+    mode_i = nerf_check_box_mode(mode)
+    a = _nerf_render_inputs("nerf_render_boxes", weights_or_state, cfg, H, W, intrinsic, c2w, rays, near, far, bb_center, bb_scale,
+                            z_samples, n_samples, lindisp, embedded_cam, z2, chunk, dtype)
+    c, n, s1, s2 = a.c, a.n, a.s1, a.s2
+    per = min(a.chunk, n)
+    nbytes = lib.query("nerfrender_boxes_work_bytes", per, s1, s2)
+    if nbytes < 0:
+        raise lib.NrpnError(f"nerf_render_boxes: chunk {a.chunk} with {s1} + {s2} samples is outside the supported range")
+    work = torch.empty(nbytes, dtype=torch.uint8, device=a.dev)
+    k = int(table.shape[0])
+    boxes_t = torch.from_numpy(table if k else np.zeros((1, 8))).to(a.dev)      # never null; with K = 0 nothing of it is read
+
+    def new(*shape):
+        return torch.empty(shape, dtype=torch.float32, device=a.dev)
+    out = {"rgb_map": new(n, 3), "depth_map": new(n), "acc_map": new(n), "disp_map": new(n), "depth_std": new(n)}
+    if return_samples:
+        out["z_vals"], out["weights"] = new(n, s1 + s2), new(n, s1 + s2)
+    if return_stages:
+        out["raw1"] = new(n, s1, 4)
+        if a.mode == 1:
+            out["z2"] = new(n, s2)
+    sizes = [per] * (n // per) + ([n % per] if n % per else [])
+    tiles_total = torch.tensor([sum(-(-r * s // 64) for r in sizes) for s in (s1, s2)], dtype=torch.int64).to(a.dev)
+    tiles_run = torch.empty(2, dtype=torch.int64, device=a.dev)
+
+    def opt(key):
+        return _p(out[key]) if key in out else None
+    args = (a.near, a.far, *a.center, a.scale, c["multires"], c["multires_views"], a.cam_ch, _p(a.packed),
+            _p(a.weights.split) if a.weights.dtype == "bf16x3" else None, _p(a.weights.w_view), _p(a.weights.b_views),
+            _p(a.cam) if a.cam_ch else None, _p(a.z1), s1, a.mode, _p(a.z2_t) if a.z2_t is not None else None, s2, a.chunk, _p(work),
+            nbytes, _p(out["rgb_map"]), _p(out["depth_map"]), _p(out["acc_map"]), _p(out["disp_map"]), _p(out["depth_std"]),
+            opt("z_vals"), opt("weights"), opt("raw1"), opt("z2"), _p(boxes_t), k, mode_i, 1 if skip else 0, _p(tiles_run), _s())
+    if a.rays_t is not None:
+        call("nerfrender_rays_boxes", _p(a.rays_t), n, *args)
+    else:
+        call("nerfrender_frame_boxes", a.lead[0], a.lead[1], _p(a.camera), *args)
+    res = {key: (v if key in ("raw1", "z2") else v.reshape(*a.lead, *v.shape[1:])) for key, v in out.items()}
+    res["tiles_total"], res["tiles_run"] = tiles_total, tiles_run
+    return res
 
 
 def nerf_render_samples(raw, rays, z_samples, near, far):
