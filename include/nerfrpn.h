@@ -195,6 +195,28 @@ int nrpn_sample_pos_neg(const float *labels, int64_t total, int max_pos, int bat
 int nrpn_rpn_sampled_loss_f32(const float *logits, const float *deltas, int dw, const float *targets,
                               const int64_t *pos, int64_t npos, const int64_t *neg, int64_t nneg, float beta,
                               float *loss2, float *g_logits, float *g_deltas, nrpn_stream_t stream);
+/* The same two losses read in place from the padded head rows of the cone head, head f32 [V][ld] (columns [0,A) logits,
+ * [A, A+A*dw) deltas), without the flattened copies.  The level table is host memory, copied into the launch: level l
+ * holds cells[l] voxels per scene and its rows start at level_start[l] (level-major, scene-major, packed); n scenes of
+ * T = A * sum(cells) anchors.  A sampled flat index r = scene * T + t maps to row level_start[l] + scene * cells[l] +
+ * cell and anchor slot a, with (l, cell, a) from t in the reference's (level, x, y, z, a) order.  loss2 has the bits of
+ * nrpn_rpn_sampled_loss_f32 on the flattened rows.  The gradient factors come out compact instead of scattered:
+ * g_obj_rows [npos+nneg] (positives first) and g_reg_rows [npos][dw] are the values that function writes at the
+ * sampled positions; deltas_pos [npos][dw] are the positives' deltas.  Only rows of sampled anchors are read. */
+int nrpn_rpn_sampled_loss_rows_f32(const float *head, int ld, const int64_t *level_start, const int64_t *cells,
+                                   int levels, int n, int64_t T, int A, int dw, const float *targets,
+                                   const int64_t *pos, int64_t npos, const int64_t *neg, int64_t nneg, float beta,
+                                   float *loss2, float *g_obj_rows, float *g_reg_rows, float *deltas_pos,
+                                   nrpn_stream_t stream);
+/* Backward of the above into the head rows: for each of the nrows rows of the cone list `rows` (uint32 pairs, voxel id
+ * first; nrpn_cone_build) all ld columns of d_head (f32|bf16 [V][ld]) are written -- (dtype)(g * s) at the columns of
+ * the sampled anchors of that row, g from g_obj_rows / g_reg_rows and s = *s_obj / *s_reg (device scalars: the
+ * upstream gradients of the two losses), +0 at every other column.  pos / neg must be ascending and distinct.  Rows
+ * outside the list are not written. */
+int nrpn_head_grad_rows(void *d_head, int dtype, int ld, const void *rows, int64_t nrows, const int64_t *level_start,
+                        const int64_t *cells, int levels, int n, int64_t T, int A, int dw, const int64_t *pos,
+                        int64_t npos, const int64_t *neg, int64_t nneg, const float *g_obj_rows,
+                        const float *g_reg_rows, const float *s_obj, const float *s_reg, nrpn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Conv3d family, channels-last, implicit GEMM on MFMA.  [a3, a4, a7, a21]

@@ -1421,6 +1421,18 @@ __device__ __forceinline__ float block_sum_256(float v, float *sh) {
   return r;
 }
 
+// per-element terms of the two losses and their derivatives (shared by the dense-buffer and the head-row kernels: one text, one rounding)
+__device__ __forceinline__ float bce_logits_term(float x, float y) { return fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x))); }
+__device__ __forceinline__ float bce_logits_grad(float x, float y, float inv) { return (1.0f / (1.0f + expf(-x)) - y) * inv; }
+__device__ __forceinline__ float smooth_l1_term(float d, float beta) {
+  const float ad = fabsf(d);
+  return (ad < beta) ? 0.5f * d * d / beta : ad - 0.5f * beta;
+}
+__device__ __forceinline__ float smooth_l1_grad(float d, float beta, float inv) {
+  const float ad = fabsf(d);
+  return ((ad < beta) ? d / beta : (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f))) * inv;
+}
+
 __global__ void __launch_bounds__(256)
 sampled_loss_kernel(const float *__restrict__ logits, const float *__restrict__ deltas, int dw, const float *__restrict__ targets,
                     const int64_t *__restrict__ pos, int64_t npos, const int64_t *__restrict__ neg, int64_t nneg, float beta,
@@ -1433,17 +1445,16 @@ sampled_loss_kernel(const float *__restrict__ logits, const float *__restrict__ 
     const bool is_pos = i < npos;
     const int64_t r = is_pos ? pos[i] : neg[i - npos];
     const float x = logits[r], y = is_pos ? 1.f : 0.f;
-    bce += fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x)));
-    if (g_logits) g_logits[r] = (1.0f / (1.0f + expf(-x)) - y) * inv;
+    bce += bce_logits_term(x, y);
+    if (g_logits) g_logits[r] = bce_logits_grad(x, y, inv);
   }
   for (int64_t i = threadIdx.x; i < npos * dw; i += blockDim.x) {
     const int64_t p = i / dw;
     const int k = (int)(i - p * dw);
     const int64_t r = pos[p];
     const float d = deltas[r * dw + k] - targets[p * dw + k];
-    const float ad = fabsf(d);
-    reg += (ad < beta) ? 0.5f * d * d / beta : ad - 0.5f * beta;
-    if (g_deltas) g_deltas[r * dw + k] = ((ad < beta) ? d / beta : (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f))) * inv;
+    reg += smooth_l1_term(d, beta);
+    if (g_deltas) g_deltas[r * dw + k] = smooth_l1_grad(d, beta, inv);
   }
   const float b = block_sum_256(bce, sh);
   const float g = block_sum_256(reg, sh);
@@ -1459,6 +1470,171 @@ extern "C" int nrpn_rpn_sampled_loss_f32(const float *logits, const float *delta
   hipLaunchKernelGGL(sampled_loss_kernel, dim3(1), dim3(256), 0, as_stream(stream), logits, deltas, dw, targets, pos, npos, neg, nneg,
                      beta, loss2, g_logits, g_deltas);
   NRPN_LAUNCH_CHECK("sampled_loss");
+  return NRPN_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The same losses read in place from the padded head rows [V][ld] of the cone head, and their backward into those rows.
+// The level table travels by value: rows of level l, scene i start at start[l] + i * cells[l]; its anchors at aoff[l] inside a scene.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int kHeadMaxLevels = 16;
+struct HeadLevels {
+  int64_t start[kHeadMaxLevels], cells[kHeadMaxLevels], aoff[kHeadMaxLevels + 1];
+  int64_t T, V;
+  int levels, n, A, dw, ld;
+};
+
+// flat batch index r (scene * T + anchor) -> head row and anchor slot; row < 0 when r lies outside the pyramid
+__device__ __forceinline__ int64_t head_row_of_anchor(const HeadLevels &h, int64_t r, int &a) {
+  a = 0;
+  if (r < 0 || r >= h.T * h.n) return -1;
+  const int64_t i = r / h.T, t = r - i * h.T;
+  int l = 0;
+  while (l + 1 < h.levels && t >= h.aoff[l + 1]) ++l;
+  const int64_t u = t - h.aoff[l], cell = u / h.A;
+  a = (int)(u - cell * h.A);
+  return h.start[l] + i * h.cells[l] + cell;
+}
+
+// head row -> flat batch index of its anchor 0 (the row's A anchors are consecutive); < 0 when the row lies outside the table
+__device__ __forceinline__ int64_t head_anchor_of_row(const HeadLevels &h, int64_t row) {
+  if (row < 0 || row >= h.V) return -1;
+  int l = 0;
+  while (l + 1 < h.levels && row >= h.start[l + 1]) ++l;
+  const int64_t u = row - h.start[l], i = u / h.cells[l], cell = u - i * h.cells[l];
+  return i * h.T + h.aoff[l] + cell * h.A;
+}
+
+// same i -> thread assignment and the same two reductions as sampled_loss_kernel: the loss bits are those of the flattened form
+__global__ void __launch_bounds__(256)
+sampled_loss_rows_kernel(const float *__restrict__ head, HeadLevels h, const float *__restrict__ targets, const int64_t *__restrict__ pos,
+                         int64_t npos, const int64_t *__restrict__ neg, int64_t nneg, float beta, float *__restrict__ loss2,
+                         float *__restrict__ g_obj_rows, float *__restrict__ g_reg_rows, float *__restrict__ deltas_pos) {
+  __shared__ float sh[4];
+  const int64_t ns = npos + nneg;
+  const float inv = 1.0f / (float)ns;
+  const int dw = h.dw;
+  float bce = 0.f, reg = 0.f;
+  for (int64_t i = threadIdx.x; i < ns; i += blockDim.x) {
+    const bool is_pos = i < npos;
+    int a;
+    const int64_t row = head_row_of_anchor(h, is_pos ? pos[i] : neg[i - npos], a);
+    float g = 0.f;
+    if (row >= 0) {       // (an index outside the pyramid was refused when the cone plan was built; never read out of bounds)
+      const float x = head[row * h.ld + a], y = is_pos ? 1.f : 0.f;
+      bce += bce_logits_term(x, y);
+      g = bce_logits_grad(x, y, inv);
+    }
+    g_obj_rows[i] = g;
+  }
+  for (int64_t i = threadIdx.x; i < npos * dw; i += blockDim.x) {
+    const int64_t p = i / dw;
+    const int k = (int)(i - p * dw);
+    int a;
+    const int64_t row = head_row_of_anchor(h, pos[p], a);
+    float v = 0.f, g = 0.f;
+    if (row >= 0) {
+      v = head[row * h.ld + h.A + a * dw + k];
+      const float d = v - targets[p * dw + k];
+      reg += smooth_l1_term(d, beta);
+      g = smooth_l1_grad(d, beta, inv);
+    }
+    deltas_pos[i] = v;
+    g_reg_rows[i] = g;
+  }
+  const float b = block_sum_256(bce, sh);
+  const float g = block_sum_256(reg, sh);
+  if (threadIdx.x == 0) { loss2[0] = b * inv; loss2[1] = g * inv; }
+}
+
+static int head_levels_fill(HeadLevels &h, const int64_t *level_start, const int64_t *cells, int levels, int n, int64_t T, int A, int dw,
+                            int ld, const char *who) {
+  NRPN_REQUIRE(level_start && cells && levels > 0 && levels <= kHeadMaxLevels && n > 0, "%s: need 1..%d levels and n > 0", who, kHeadMaxLevels);
+  NRPN_REQUIRE(dw == 6 || dw == 8, "%s: dw must be 6 or 8 (got %d)", who, dw);
+  NRPN_REQUIRE(A > 0 && A * (1 + dw) <= ld, "%s: A * (1 + dw) must fit the row (A %d, dw %d, ld %d)", who, A, dw, ld);
+  int64_t aoff = 0, row = 0;
+  for (int l = 0; l < levels; ++l) {
+    NRPN_REQUIRE(cells[l] > 0 && level_start[l] == row, "%s: level %d of the table is not packed (level, scene)-major", who, l);
+    h.start[l] = level_start[l]; h.cells[l] = cells[l]; h.aoff[l] = aoff;
+    aoff += cells[l] * A; row += cells[l] * n;
+  }
+  for (int l = levels; l < kHeadMaxLevels; ++l) { h.start[l] = row; h.cells[l] = 1; h.aoff[l] = aoff; }
+  h.aoff[kHeadMaxLevels] = aoff;
+  NRPN_REQUIRE(aoff == T, "%s: the level table holds %lld anchors per scene, T is %lld", who, (long long)aoff, (long long)T);
+  h.T = T; h.V = row; h.levels = levels; h.n = n; h.A = A; h.dw = dw; h.ld = ld;
+  return NRPN_OK;
+}
+
+extern "C" int nrpn_rpn_sampled_loss_rows_f32(const float *head, int ld, const int64_t *level_start, const int64_t *cells, int levels, int n,
+                                              int64_t T, int A, int dw, const float *targets, const int64_t *pos, int64_t npos,
+                                              const int64_t *neg, int64_t nneg, float beta, float *loss2, float *g_obj_rows,
+                                              float *g_reg_rows, float *deltas_pos, nrpn_stream_t stream) {
+  HeadLevels h;
+  if (int rc = head_levels_fill(h, level_start, cells, levels, n, T, A, dw, ld, "sampled loss rows")) return rc;
+  NRPN_REQUIRE(npos >= 0 && nneg >= 0 && npos + nneg > 0, "sampled loss rows: empty sample");
+  NRPN_REQUIRE(head && loss2 && g_obj_rows && (npos == 0 || (pos && targets && g_reg_rows && deltas_pos)) && (nneg == 0 || neg),
+               "sampled loss rows: null pointer");
+  hipLaunchKernelGGL(sampled_loss_rows_kernel, dim3(1), dim3(256), 0, as_stream(stream), head, h, targets, pos, npos, neg, nneg, beta, loss2,
+                     g_obj_rows, g_reg_rows, deltas_pos);
+  NRPN_LAUNCH_CHECK("sampled_loss_rows");
+  return NRPN_OK;
+}
+
+// position of v in the ascending list a[0, n), or -1
+__device__ __forceinline__ int64_t find_sorted(const int64_t *__restrict__ a, int64_t n, int64_t v) {
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (a[mid] < v) lo = mid + 1; else hi = mid;
+  }
+  return (lo < n && a[lo] == v) ? lo : -1;
+}
+
+// one workgroup per listed row writes all ld columns of it: cast(g * s) at the columns of sampled anchors (looked up in the ascending
+// pos / neg lists), +0 everywhere else.  The multiply and the store are those of torch's fp32 multiply + head_flatten_kernel<T, false>.
+template <typename T>
+__global__ void __launch_bounds__(128)
+head_grad_rows_kernel(T *__restrict__ d_head, const unsigned *__restrict__ rows, HeadLevels h, const int64_t *__restrict__ pos, int64_t npos,
+                      const int64_t *__restrict__ neg, int64_t nneg, const float *__restrict__ g_obj_rows, const float *__restrict__ g_reg_rows,
+                      const float *__restrict__ s_obj, const float *__restrict__ s_reg) {
+  const int64_t row = (int64_t)rows[2 * (int64_t)blockIdx.x];
+  const int64_t r0 = head_anchor_of_row(h, row);
+  if (r0 < 0) return;
+  const int per = h.A * (1 + h.dw);
+  for (int k = threadIdx.x; k < h.ld; k += blockDim.x) {
+    float v = 0.f;
+    if (k < h.A) {
+      int64_t j = find_sorted(pos, npos, r0 + k);
+      if (j < 0) { j = find_sorted(neg, nneg, r0 + k); if (j >= 0) j += npos; }
+      if (j >= 0) v = g_obj_rows[j] * s_obj[0];
+    } else if (k < per) {
+      const int a = (k - h.A) / h.dw;
+      const int64_t j = find_sorted(pos, npos, r0 + a);
+      if (j >= 0) v = g_reg_rows[j * h.dw + (k - h.A - a * h.dw)] * s_reg[0];
+    }
+    elem<T>::st(d_head + row * h.ld + k, v);
+  }
+}
+
+extern "C" int nrpn_head_grad_rows(void *d_head, int dtype, int ld, const void *rows, int64_t nrows, const int64_t *level_start,
+                                   const int64_t *cells, int levels, int n, int64_t T, int A, int dw, const int64_t *pos, int64_t npos,
+                                   const int64_t *neg, int64_t nneg, const float *g_obj_rows, const float *g_reg_rows, const float *s_obj,
+                                   const float *s_reg, nrpn_stream_t stream) {
+  HeadLevels h;
+  if (int rc = head_levels_fill(h, level_start, cells, levels, n, T, A, dw, ld, "head grad rows")) return rc;
+  NRPN_REQUIRE(dtype == NRPN_F32 || dtype == NRPN_BF16, "head grad rows: dtype must be f32 or bf16 (got %d)", dtype);
+  NRPN_REQUIRE(nrows >= 0 && nrows <= h.V && npos >= 0 && nneg >= 0, "head grad rows: bad counts");
+  if (nrows == 0) return NRPN_OK;
+  NRPN_REQUIRE(d_head && rows && g_obj_rows && s_obj && s_reg && (npos == 0 || (pos && g_reg_rows)) && (nneg == 0 || neg),
+               "head grad rows: null pointer");
+  const unsigned *list = reinterpret_cast<const unsigned *>(rows);
+  if (dtype == NRPN_F32)
+    hipLaunchKernelGGL((head_grad_rows_kernel<float>), dim3((unsigned)nrows), dim3(128), 0, as_stream(stream), (float *)d_head, list, h, pos,
+                       npos, neg, nneg, g_obj_rows, g_reg_rows, s_obj, s_reg);
+  else
+    hipLaunchKernelGGL((head_grad_rows_kernel<unsigned short>), dim3((unsigned)nrows), dim3(128), 0, as_stream(stream),
+                       (unsigned short *)d_head, list, h, pos, npos, neg, nneg, g_obj_rows, g_reg_rows, s_obj, s_reg);
+  NRPN_LAUNCH_CHECK("head_grad_rows");
   return NRPN_OK;
 }
 

@@ -130,11 +130,12 @@ class RPNHead(nn.Module):
                 return None
         return max(len(mods) // 2 - 1, 0)
 
-    def forward_cone(self, feats_cl: List[Tensor], plan):
+    def forward_cone(self, feats_cl: List[Tensor], plan, loss_pack=None):
         """Training only: logits [N,T] / deltas [N,T,dw] that are exact on the voxels of the sampled anchors and zero elsewhere
-        (ops.ConeHeadFn: the head evaluated on the sampled-anchor cones of ``plan``)."""
+        (ops.ConeHeadFn: the head evaluated on the sampled-anchor cones of ``plan``).  With ``loss_pack`` = (targets, pos, neg, beta, T) the
+        sampled loss is taken from the head rows directly: (loss_objectness, smooth-L1 box loss, deltas of the positives [npos, dw], detached)."""
         convs = [m for m in self.conv if isinstance(m, nn.Conv3d)]
-        return ops.ConeHeadFn.apply(plan, self, self.num_anchors, self.delta_width, *feats_cl, *[c.weight for c in convs], *[c.bias for c in convs],
+        return ops.ConeHeadFn.apply(plan, self, self.num_anchors, self.delta_width, loss_pack, *feats_cl, *[c.weight for c in convs], *[c.bias for c in convs],
                                     self.cls_logits.weight, self.bbox_pred.weight, self.cls_logits.bias, self.bbox_pred.bias)
 
     def forward(self, x: List[Tensor]) -> Tuple[List[Tensor], List[Tensor]]:

@@ -255,16 +255,25 @@ class RegionProposalNetwork(nn.Module):
         return dict(mesh_size=tuple(mesh_size), grids=[tuple(g) for g in grids], table=table, pad=pad, labels=labels, matched=matched,
                     flags=flags, pos=pos, neg=neg, matched_gt=matched_gt, reg_targets=reg_targets, anchors_pos=anchors_pos, cone=cone)
 
-    def compute_loss(self, prep, logits, deltas, max_mesh_dim):
-        """reference rpn.py:372-456 on the sampled rows only."""
+    def need_box_grad(self):
+        """True when a loss term differentiates through the decoded boxes of the positives (rotated-IoU or the 2-D projection loss)."""
+        return self.rotated_iou_loss is not None or self.loss_2d_requires_grad
+
+    def compute_loss(self, prep, logits, deltas, max_mesh_dim, rows_loss=None):
+        """reference rpn.py:372-456 on the sampled rows only.  ``rows_loss``: (loss_obj, smooth-L1 loss, deltas of the positives) already
+        taken from the head rows by the cone head (ops.ConeHeadFn with a loss pack; no box gradient needed); logits / deltas are None then."""
         pos, neg, matched_gt = prep["pos"], prep["neg"], prep["matched_gt"]
-        flat_logits, flat_deltas = logits.reshape(-1), deltas.reshape(-1, self.num_delta_digits)
-        loss_obj, loss_reg_l1 = ops.SampledLossFn.apply(flat_logits, flat_deltas, prep["reg_targets"], pos, neg, 1.0 / 9)
-        need_box_grad = self.rotated_iou_loss is not None or self.loss_2d_requires_grad
-        if need_box_grad:
-            pred_pos = self.box_coder.decode_single_diff(flat_deltas[pos], prep["anchors_pos"])
+        need_box_grad = self.need_box_grad()
+        if rows_loss is not None:
+            loss_obj, loss_reg_l1, deltas_pos = rows_loss
+            pred_pos = self.box_coder.decode_single(deltas_pos, prep["anchors_pos"])
         else:
-            pred_pos = self.box_coder.decode_single(flat_deltas[pos], prep["anchors_pos"])
+            flat_logits, flat_deltas = logits.reshape(-1), deltas.reshape(-1, self.num_delta_digits)
+            loss_obj, loss_reg_l1 = ops.SampledLossFn.apply(flat_logits, flat_deltas, prep["reg_targets"], pos, neg, 1.0 / 9)
+            if need_box_grad:
+                pred_pos = self.box_coder.decode_single_diff(flat_deltas[pos], prep["anchors_pos"])
+            else:
+                pred_pos = self.box_coder.decode_single(flat_deltas[pos], prep["anchors_pos"])
         if self.rotated_iou_loss is not None:
             loss_reg = self.rotated_iou_loss(pred_pos, matched_gt) / (pos.numel() + neg.numel())
         else:
@@ -306,7 +315,16 @@ class RegionProposalNetwork(nn.Module):
         cone = prepared.get("cone") if (self.training and prepared is not None and objectness_output_paths is None
                                         and prepared["grids"] == grids and prepared["mesh_size"] == mesh_size) else None
         self.last_cone = None
-        if cone is not None:
+        rows_loss = None
+        if cone is not None and ops.CONE_ROWS_LOSS[0] and targets is not None and not self.need_box_grad():
+            # ... and when no loss term differentiates through the decoded boxes, the sampled loss and its gradient are taken from the
+            # head rows of the sampled voxels directly: no flattened logits / deltas and no dense gradient buffers
+            table = prepared["table"]
+            pack = (prepared["reg_targets"], prepared["pos"], prepared["neg"], 1.0 / 9, table.total)
+            rows_loss = self.head.forward_cone(feats_cl, cone, pack)
+            logits = deltas = None
+            self.last_cone = dict(rows=list(cone.counts), total_voxels=cone.total)
+        elif cone is not None:
             # training: only the sampled anchors' logits / deltas are read below, so the head is evaluated on their cones (zeros elsewhere)
             logits, deltas = self.head.forward_cone(feats_cl, cone)
             self.last_cone = dict(rows=list(cone.counts), total_voxels=cone.total)       # sizes only (bench / logging)
@@ -328,7 +346,7 @@ class RegionProposalNetwork(nn.Module):
                 raise ValueError("targets should not be None")
             if prepared is None or prepared["grids"] != grids or prepared["mesh_size"] != mesh_size:
                 prepared = self.prepare_targets(mesh_size, grids, targets, original_mesh_sizes, logits.device)
-            lo, lr, l2 = self.compute_loss(prepared, logits, deltas, max(mesh_size))
+            lo, lr, l2 = self.compute_loss(prepared, logits, deltas, max(mesh_size), rows_loss)
             losses = {"loss_objectness": lo, "loss_rpn_box_reg": lr, "loss_rpn_box_reg_2d": l2}
         return boxes, level_indexes, losses, scores
 

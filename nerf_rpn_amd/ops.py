@@ -1147,6 +1147,20 @@ class ConePlan:
         return [self.lists, self.counts_dev]
 
 
+# A/B switch: with the cone head and no box gradient needed, take the sampled loss and its gradient from the head rows of S_0 directly
+# (no flattened logits / deltas, no dense gradient buffers); default on
+CONE_ROWS_LOSS = [_os.environ.get("NRPN_CONE_ROWS_LOSS", "1") != "0"]
+
+
+def _head_levels(plan):
+    """(level_start, cells, levels) of ``plan`` as the host arrays nrpn_rpn_sampled_loss_rows_f32 / nrpn_head_grad_rows copy into their launch."""
+    if getattr(plan, "_head_levels", None) is None:
+        L = len(plan.cells)
+        plan._head_levels = ((ctypes.c_int64 * L)(*plan.level_start[:L]), (ctypes.c_int64 * L)(*plan.cells))
+    start, cells = plan._head_levels
+    return ctypes.addressof(start), ctypes.addressof(cells), len(plan.cells)
+
+
 def cone_from_indices(plan, pos, neg, table):
     """Build ``plan`` from flat batch indices (scene * T + anchor), e.g. a test's injected sample; synchronises (sizes of boolean selections)."""
     T, n = table.total, plan.n
@@ -1238,10 +1252,13 @@ class ConeHeadFn(torch.autograd.Function):
     D layers) is computed on S_{D-1-i}, the output GEMM on S_0; backward visits the same sets (weight gradients from the listed rows, input
     gradients on the next larger set, the first layer's input gradient densely per level for the FPN).  One autograd node, ~25 launches,
     instead of ~150 for the dense head at four levels.  logits / deltas are exact on the sampled anchors' voxels and ZERO elsewhere: only
-    the training loss, which reads the sampled rows, may consume them (RegionProposalNetwork.forward decides)."""
+    the training loss, which reads the sampled rows, may consume them (RegionProposalNetwork.forward decides).
+    With a loss pack ``(targets, pos, neg, beta, T)`` (CONE_ROWS_LOSS; no loss term differentiates through the decoded boxes) the node ends in
+    the sampled loss itself, read in place from the head rows of S_0: it returns (loss_objectness, smooth-L1 box loss, deltas of the positives
+    [npos, dw], non-differentiable), its backward takes the two scalar gradients, and nothing outside S_0 is filled, copied or scaled."""
 
     @staticmethod
-    def forward(ctx, plan, head, A, dw, *tensors):
+    def forward(ctx, plan, head, A, dw, pack, *tensors):
         L = len(plan.grids)
         feats = tensors[:L]
         convs = [m for m in head.conv if isinstance(m, torch.nn.Conv3d)]
@@ -1278,9 +1295,34 @@ class ConeHeadFn(torch.autograd.Function):
         rows_total = head.head_rows
         wpo, wpdo = head._pack.get(list(ow), dt, rows_total, True, C)
         bias_o = head._pack.fused_bias(ob, rows_total) if ob[0] is not None else None
-        out = torch.zeros((V, rows_total), dtype=torch.float32, device=dev)
+        # with a loss pack only the rows of S_0 are ever read (the loss kernel visits the sampled anchors' rows): no fill
+        out = (torch.zeros if pack is None else torch.empty)((V, rows_total), dtype=torch.float32, device=dev)
         conv_rows_fwd(hs[-1], wpo, bias_o, out, plan, 0, C, rows_total, rows_total, 1, 0)
         T = sum(plan.cells) * A
+        ctx.save_for_backward(*hs, *ops_w, wpdo, *cw, *[b for b in cb if b is not None], *ow, *[b for b in ob if b is not None])
+        ctx.meta = (plan, head, A, dw, L, D, n, C, dt, rows_total, [b is not None for b in cb], [b is not None for b in ob], need_dgrad)
+        ctx.x3 = x3
+        # gradient sinks are attributes of the Parameter objects: looked up here, on the objects the caller passed (as ConvFn does)
+        ctx.sinks = ([_sink(w) for w in cw], [_sink(b) for b in cb], [_sink(w) for w in ow], [_sink(b) for b in ob])
+        ctx.rows_loss = None
+        if pack is not None:
+            # the sampled loss read in place from the head rows: no flattened logits / deltas, compact gradient factors for the backward
+            targets, pos, neg, beta, pack_T = pack
+            if pack_T != T or n != plan.n:
+                raise lib.NrpnError("ConeHeadFn: the loss pack and the cone plan disagree on the anchor count")
+            targets = targets.contiguous()
+            _chk(targets, pos, neg)
+            npos, nneg = pos.numel(), neg.numel()
+            loss2 = torch.empty(2, dtype=torch.float32, device=dev)
+            g_obj = torch.empty(npos + nneg, dtype=torch.float32, device=dev)
+            g_reg = torch.empty((npos, dw), dtype=torch.float32, device=dev)
+            deltas_pos = torch.empty((npos, dw), dtype=torch.float32, device=dev)
+            call("rpn_sampled_loss_rows_f32", _p(out), rows_total, *_head_levels(plan), n, T, A, dw, _p(targets), _p(pos), npos, _p(neg), nneg,
+                 float(beta), _p(loss2), _p(g_obj), _p(g_reg), _p(deltas_pos), _s())
+            ctx.rows_loss = (pos, neg, g_obj, g_reg, T)
+            ctx.mark_non_differentiable(deltas_pos)
+            ctx.set_materialize_grads(False)      # no zero tensor (a fill launch) for the gradient slot of deltas_pos
+            return loss2[0], loss2[1], deltas_pos
         logits = torch.empty((n, T), dtype=torch.float32, device=dev)
         deltas = torch.empty((n, T, dw), dtype=torch.float32, device=dev)
         off = 0
@@ -1289,15 +1331,10 @@ class ConeHeadFn(torch.autograd.Function):
                 r0 = plan.level_start[l] + i * c
                 call("head_flatten_f32", _p(out[r0:r0 + c]), c, rows_total, A, dw, _p(logits[i, off:]), _p(deltas[i, off:]), _s())
             off += c * A
-        ctx.save_for_backward(*hs, *ops_w, wpdo, *cw, *[b for b in cb if b is not None], *ow, *[b for b in ob if b is not None])
-        ctx.meta = (plan, head, A, dw, L, D, n, C, dt, rows_total, [b is not None for b in cb], [b is not None for b in ob], need_dgrad)
-        ctx.x3 = x3
-        # gradient sinks are attributes of the Parameter objects: looked up here, on the objects the caller passed (as ConvFn does)
-        ctx.sinks = ([_sink(w) for w in cw], [_sink(b) for b in cb], [_sink(w) for w in ow], [_sink(b) for b in ob])
         return logits, deltas
 
     @staticmethod
-    def backward(ctx, g_logits, g_deltas):
+    def backward(ctx, g_logits, g_deltas, _g_deltas_pos=None):
         IN_BACKWARD[0] += 1
         try:
             return ConeHeadFn._backward(ctx, g_logits, g_deltas)
@@ -1306,6 +1343,7 @@ class ConeHeadFn(torch.autograd.Function):
 
     @staticmethod
     def _backward(ctx, g_logits, g_deltas):
+        """``g_logits`` / ``g_deltas``: the dense gradients of the two outputs, or -- with a loss pack -- the scalar gradients of the two losses."""
         plan, head, A, dw, L, D, n, C, dt, rows_total, has_cb, has_ob, need_dgrad = ctx.meta
         saved = list(ctx.saved_tensors)
         hs, saved = saved[:D + 1], saved[D + 1:]
@@ -1319,14 +1357,24 @@ class ConeHeadFn(torch.autograd.Function):
         ob = [saved.pop(0) if h else None for h in has_ob]
         dev = hs[0].device
         V = plan.total
-        g_logits, g_deltas = g_logits.contiguous(), g_deltas.contiguous()
         dout = torch.empty((V, rows_total), dtype=dt, device=dev)
-        off = 0
-        for l, c in enumerate(plan.cells):
-            for i in range(n):
-                r0 = plan.level_start[l] + i * c
-                call("head_unflatten", _p(g_logits[i, off:]), _p(g_deltas[i, off:]), c, rows_total, A, dw, 0, _p(dout[r0:r0 + c]), _dt(dout), _s())
-            off += c * A
+        if ctx.rows_loss is not None:
+            # only the rows of S_0 are written (sampled columns: factor x upstream scalar, read on the device; the rest of the row zero);
+            # the weight gradient and the dgrad below read those rows only
+            pos, neg, g_obj, g_reg, T = ctx.rows_loss
+            # (gradients are not materialised on this path: a loss the caller left out of its total arrives as None)
+            s_obj, s_reg = [torch.zeros((), dtype=torch.float32, device=dev) if g is None else g.float().contiguous() for g in (g_logits, g_deltas)]
+            rows, nrows = plan.rows(0)
+            call("head_grad_rows", _p(dout), _dt(dout), rows_total, rows, nrows, *_head_levels(plan), n, T, A, dw, _p(pos), pos.numel(), _p(neg),
+                 neg.numel(), _p(g_obj), _p(g_reg), _p(s_obj), _p(s_reg), _s())
+        else:
+            g_logits, g_deltas = g_logits.contiguous(), g_deltas.contiguous()
+            off = 0
+            for l, c in enumerate(plan.cells):
+                for i in range(n):
+                    r0 = plan.level_start[l] + i * c
+                    call("head_unflatten", _p(g_logits[i, off:]), _p(g_deltas[i, off:]), c, rows_total, A, dw, 0, _p(dout[r0:r0 + c]), _dt(dout), _s())
+                off += c * A
         _wait_dgrad_operands()
 
         cws, cbs, ows, obs = ctx.sinks
@@ -1371,7 +1419,7 @@ class ConeHeadFn(torch.autograd.Function):
                         continue
                     dyl = dh[plan.level_start[l]:plan.level_start[l + 1]].view(n, g[0], g[1], g[2], C)
                     g_feats[l] = _conv_fwd(dyl, wpds[0], None, C, C, 3, 0, dt)
-        return (None, None, None, None, *g_feats, *g_cw, *g_cb, *g_ow)
+        return (None, None, None, None, None, *g_feats, *g_cw, *g_cb, *g_ow)
 
 
 STEM_HALO = [_os.environ.get("NRPN_STEM_HALO", "1") != "0"]      # A/B switch: halo-form stem forward (bf16, stride 2, even Z, Cout 64); default on
