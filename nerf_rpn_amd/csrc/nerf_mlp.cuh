@@ -13,6 +13,11 @@
 // launch_trunk(tile, tiles, packed, split, gbuf, stream[, flags]) is the only place that knows there are two arithmetics to launch: the
 // planes ``split`` select bf16x3, null selects fp32; per-tile ``flags`` select the sibling kernel that leaves unflagged tiles alone.  The point arithmetic of a source stays in its consumer's translation unit: the
 // three are compiled with different contraction flags (Makefile).
+//
+// Also here, each defined once for the three consumers: the pack of a weight matrix into B fragments (PackSeg, pack_elem, launch_pack:
+// the forward's matrices and nerfquery.hip's transposes, fp32 and bf16x3), and what runs after the trunk -- the view branch of
+// views_linears.0 (unit_dir, embed_dirs, view_row) and rgb_linear over relu(g + c) (head_pre, rgb_head, rgb_store).  nerf_render and
+// nerf_query give the same raw on the same points and view directions because they run these, not copies of them.
 #pragma once
 #include "common.h"
 
@@ -36,6 +41,13 @@ constexpr int kMaxViewsCh = 64;  // 3 + 6 multires_views <= 64 (multires_views <
 inline bool model_ok(int multires, int multires_views, int cam_ch) {
   return multires >= 0 && 3 + 6 * multires <= kEnc && multires_views >= 0 && 3 + 6 * multires_views <= kMaxViewsCh && cam_ch >= 0 &&
          cam_ch <= 65536;
+}
+
+// ... and the sizes nerfquery.hip accepts: num_rays rays of ``samples`` given points each, in chunks of ``chunk`` points (the renders'
+// limits, which count rays per chunk and two passes, are nerfray::sizes_ok)
+inline bool query_sizes_ok(int64_t num_rays, int samples, int64_t chunk) {
+  return num_rays >= 1 && samples >= 1 && samples <= 65536 && num_rays < ((int64_t)1 << 31) && chunk >= 1 &&
+         num_rays * samples < ((int64_t)1 << 40);
 }
 
 inline int64_t align16(int64_t b) { return (b + 15) / 16 * 16; }
@@ -67,6 +79,44 @@ constexpr int64_t kPackedFloats = kOffRgbB + 4;
 // matrices at the offsets off_layer gives, the lo plane follows it.  Every offset is a multiple of 8: a fragment is one uint4.
 constexpr int64_t kSplitPlane = kOffBias;
 constexpr int64_t kSplitElems = 2 * kSplitPlane;
+
+// ---- pack: a matrix of raw as the B fragments gemm_tile and gemm_tile_split load ---------------------------------------------------
+// One segment of a pack.  W is read at raw[src + (col_off + o) * ld_o + k * ld_k] for output column o and k: ld_o is W's row stride and
+// ld_k = 1 for a torch Linear weight [n_out][ld] as the forward multiplies it, and the other way round for its transpose, whose output
+// columns are W's columns from col_off.  The packed k axis is [ka k of W, zero-padded to ka_pad][kb k of W from ka on]; a transpose
+// has ka = ka_pad = 0.  fp32 (kFrag 4): k-group kg = 8 consecutive k, lane half h takes k = 8 kg + 4 h + j in element j, so the float4
+// of (kg, o, h) sits at ((kg * n_out + o) * 2 + h) * 4 of dst.  bf16x3 (kFrag 8): k-step ks = 16 consecutive k, k = 16 ks + 8 h + j, the
+// eight bf16 of (ks, o, h) at ((ks * n_out + o) * 2 + h) * 8 of dst in the hi plane, their residuals at the same place of the lo plane;
+// padding is zero in both.  n_out == 0: a plain copy of kb floats (fp32 only).
+struct PackSeg {
+  int64_t dst, src;
+  int n_out, ld_o, ld_k, col_off, ka, ka_pad, kb;
+};
+struct PackPlan {
+  PackSeg seg[16];
+};
+
+// the value of element i of a segment's fragments, kFrag elements to a fragment
+template <int kFrag>
+__device__ __forceinline__ float pack_elem(const float *__restrict__ raw, const PackSeg &s, int64_t i) {
+  constexpr int kShift = kFrag == 4 ? 2 : 3;
+  static_assert(kFrag == 1 << kShift, "fragments of 4 or 8 elements");
+  const int j = (int)(i & (kFrag - 1)), h = (int)((i >> kShift) & 1);
+  const int64_t q = i >> (kShift + 1);
+  const int o = (int)(q % s.n_out), kg = (int)(q / s.n_out);
+  int k = 2 * kFrag * kg + kFrag * h + j;
+  if (k < s.ka_pad) {
+    if (k >= s.ka) return 0.f;
+  } else {
+    k += s.ka - s.ka_pad;
+  }
+  return raw[s.src + (int64_t)(s.col_off + o) * s.ld_o + (int64_t)k * s.ld_k];
+}
+
+// The ``segs`` segments of plan from raw: into the floats ``packed``, or, packed null, into the bf16x3 planes ``planes`` whose lo plane
+// starts lo_plane elements after the hi plane (nerfgrid.hip has the two kernels).  Raises nothing but a failed launch.
+int launch_pack(const float *raw, const PackPlan &plan, int segs, float *packed, unsigned short *planes, int64_t lo_plane,
+                hipStream_t stream);
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
@@ -373,6 +423,77 @@ int launch_trunk(const Tile &tile, int tiles, const float *packed, const uint4 *
   }
   NRPN_LAUNCH_CHECK("nerfmlp_trunk_kernel");
   return NRPN_OK;
+}
+
+// ---- after the trunk: the view branch of views_linears.0 and rgb_linear -----------------------------------------------------------
+// Shared by translation units that are compiled with and without FMA contraction (Makefile): every multiply-add below is an explicit
+// fmaf, every operation that rounds on its own an explicit __f*_rn, and no other expression holds a multiply next to an add.
+
+// The view direction of a ray direction d: vd = d / n with n = sqrtf((d0 d0 + d1 d1) + d2 d2), every operation rounded on its own.
+// nerf_render's head forms it so; a caller of nerf_query that wants the render's rgb bits forms its viewdirs the same way.
+__device__ __forceinline__ void unit_dir(const float *d, float (&vd)[3]) {
+  const float n = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(d[0], d[0]), __fmul_rn(d[1], d[1])), __fmul_rn(d[2], d[2])));
+#pragma unroll
+  for (int a = 0; a < 3; ++a) vd[a] = __fdiv_rn(d[a], n);
+}
+
+// embeddirs_fn of a view direction: row[0 .. 3 + 6 multires_views)
+__device__ __forceinline__ void embed_dirs(float *row, const float (&vd)[3], int multires_views) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a) row[a] = vd[a];
+  for (int l = 0; l < multires_views; ++l)
+#pragma unroll
+    for (int a = 0; a < 3; ++a) embed_freq(row, vd[a], l, a);
+}
+
+// c[j] = b[j] + sum_k W_c[j][k] cam[k] + sum_k W_d[j][k] emb[k]: what a ray adds to column j of views_linears.0 before the relu, one fmaf
+// chain: the bias, the camera columns in k order, then the view columns in k order.  w_view [128][views_ch + cam_ch]: W_d, then W_c.
+// The chain up to the first view column is the same for every ray: view_row_cam gives it, view_row_dirs continues it.
+__device__ __forceinline__ float view_row_cam(int j, const float *__restrict__ w_view, const float *__restrict__ b_view,
+                                              const float *__restrict__ cam, int views_ch, int cam_ch) {
+  float c = b_view[j];
+  for (int k = 0; k < cam_ch; ++k) c = fmaf(w_view[j * (views_ch + cam_ch) + views_ch + k], cam[k], c);
+  return c;
+}
+__device__ __forceinline__ float view_row_dirs(float c, int j, const float *__restrict__ w_view, const float *emb, int views_ch,
+                                               int cam_ch) {
+  for (int k = 0; k < views_ch; ++k) c = fmaf(w_view[j * (views_ch + cam_ch) + k], emb[k], c);
+  return c;
+}
+__device__ __forceinline__ float view_row(int j, const float *__restrict__ w_view, const float *__restrict__ b_view,
+                                          const float *__restrict__ cam, const float *emb, int views_ch, int cam_ch) {
+  return view_row_dirs(view_row_cam(j, w_view, b_view, cam, views_ch, cam_ch), j, w_view, emb, views_ch, cam_ch);
+}
+
+// Column j of views_linears.0 before the relu, the relu, and its derivative: 0 at exactly 0, as torch has it.  The mask the camera
+// optimisation stores and the mask nerfquery's backward applies are head_on of head_pre.
+__device__ __forceinline__ float head_pre(float g, float c) { return g + c; }
+__device__ __forceinline__ float head_relu(float pre) { return fmaxf(pre, 0.f); }
+__device__ __forceinline__ bool head_on(float pre) { return pre > 0.f; }
+
+// rgb_linear without its bias over v = relu(g + c) of one point: r[ch] = sum_j W_rgb[ch][j] v[j] as 128-term fmaf chains in j order.
+// g(j): the point's trunk output j, from registers or from gbuf; c[j]: the view_row of its ray; w: packed + kOffRgbW, wave-uniform, so
+// it comes through the scalar cache.  kMask: bit j of the 128 bits m[0 .. 4), zero on entry, becomes head_on; m is not touched
+// otherwise.  kUnroll: the caller's unroll factor of the j loop, kHalf for all of it.  (nerfgrid.hip's per-pose head writes this
+// loop out over head_relu(head_pre()): see there.)
+template <bool kMask, int kUnroll, class G>
+__device__ __forceinline__ void rgb_head(G &&g, const float *c, const float *__restrict__ w, float (&r)[3], uint32_t *m) {
+  r[0] = r[1] = r[2] = 0.f;
+#pragma unroll kUnroll
+  for (int j = 0; j < kHalf; ++j) {
+    const float pre = head_pre(g(j), c[j]);
+    const float v = head_relu(pre);
+    if (kMask) m[j >> 5] |= (uint32_t)head_on(pre) << (j & 31);
+    r[0] = fmaf(w[j], v, r[0]);
+    r[1] = fmaf(w[kHalf + j], v, r[1]);
+    r[2] = fmaf(w[2 * kHalf + j], v, r[2]);
+  }
+}
+
+// raw rgb of a point: the chains plus rgb_linear's bias
+__device__ __forceinline__ void rgb_store(float *o, const float (&r)[3], const float *__restrict__ packed) {
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) o[ch] = r[ch] + packed[kOffRgbB + ch];
 }
 
 }  // namespace nerfmlp

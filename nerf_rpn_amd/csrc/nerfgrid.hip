@@ -5,65 +5,38 @@
 //   trunk (one workgroup = 64 points): positional encoding into LDS, the eight pts_linears, feature_linear, alpha_linear and the
 //     feature columns W_f of views_linears.0 -- all matrix products on v_mfma_f32_32x32x2_f32 (exact fp32: a k-ordered fmaf chain), the
 //     activations in one [64][324] fp32 LDS image rewritten in place between two barriers per layer, the weights read from L2 in a
-//     packed order (nerfgrid_pack_kernel) that makes every B fragment one coalesced 16-byte load per lane.
+//     packed order (nerfmlp_pack_kernel) that makes every B fragment one coalesced 16-byte load per lane.
 //     -> sigma (written to the result) and g = W_f f, 128 floats per point, in a scratch that is bounded by the chunk size.
 //   head (one thread = one point): for the poses in order v = relu(g + c_p), rgb = W_rgb v + b_rgb, acc += sigmoid(rgb); acc / P.
+//     v comes from nerf_mlp.cuh's head_pre / head_relu, which the render's and the query's heads use through rgb_head; the chains
+//     over it are rgb_head's, written out (see the kernel).
 // No atomics; a point's arithmetic does not depend on its neighbours, its tile or its chunk.
+// This unit also holds the two pack kernels and their launcher (nerfmlp::launch_pack) for every packed layout of the library: the
+// forward's matrices here, their transposes for nerfquery.hip.  Segment descriptor and index arithmetic: nerf_mlp.cuh.
 #include "nerf_mlp.cuh"
 
 namespace {
 
 using namespace nerfmlp;
 
-// ---- pack ------------------------------------------------------------------------------------------------------------------------
-// A matrix W [n_out][ld] (torch Linear layout) becomes B fragments: the k axis is [ka columns of W, zero-padded to ka_pad][kb columns
-// of W starting at column ka]; k-group kg = 8 consecutive k; lane half h takes k = 8 kg + 4 h + j in element j, so the float4 of
-// (kg, output column o, h) sits at ((kg * n_out + o) * 2 + h) * 4.
-struct PackSeg {
-  int64_t dst, src;
-  int n_out, ld, ka, ka_pad, kb;     // n_out == 0: plain copy of kb floats
-};
-struct PackPlan {
-  PackSeg seg[16];
-};
-
-// the value of element i of a segment's fragments, kFrag (4 floats or 8 bf16) elements to a fragment: (k-group kg, o, h, j) from i as
-// laid out above, k = 2 kFrag kg + kFrag h + j on the padded k axis
-template <int kFrag>
-__device__ __forceinline__ float pack_elem(const float *__restrict__ raw, const PackSeg &s, int64_t i) {
-  constexpr int kShift = kFrag == 4 ? 2 : 3;
-  static_assert(kFrag == 1 << kShift, "fragments of 4 or 8 elements");
-  const int j = (int)(i & (kFrag - 1)), h = (int)((i >> kShift) & 1);
-  const int64_t q = i >> (kShift + 1);
-  const int o = (int)(q % s.n_out), kg = (int)(q / s.n_out);
-  const int k = 2 * kFrag * kg + kFrag * h + j;
-  float v = 0.f;
-  if (k < s.ka_pad) {
-    if (k < s.ka) v = raw[s.src + (int64_t)o * s.ld + k];
-  } else {
-    v = raw[s.src + (int64_t)o * s.ld + s.ka + (k - s.ka_pad)];
-  }
-  return v;
-}
-
-__global__ void nerfgrid_pack_kernel(const float *__restrict__ raw, float *__restrict__ packed, PackPlan plan) {
+// ---- pack (segments, pack_elem: nerf_mlp.cuh) -------------------------------------------------------------------------------------
+// The two kernels of every pack of the library: nrpn_nerfgrid_pack* below and, through launch_pack, nerfquery.hip's transposes
+__global__ void nerfmlp_pack_kernel(const float *__restrict__ raw, float *__restrict__ packed, PackPlan plan) {
   const PackSeg s = plan.seg[blockIdx.y];
   const int64_t total = s.n_out == 0 ? s.kb : (int64_t)(s.ka_pad + s.kb) * s.n_out;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x)
     packed[s.dst + i] = s.n_out == 0 ? raw[s.src + i] : pack_elem<4>(raw, s, i);
 }
 
-// The bf16x3 planes of the same ten matrices (segments with n_out > 0): k-step ks = 16 consecutive k of the k axis above; lane half h
-// takes k = 16 ks + 8 h + j in element j, so the eight bf16 of (ks, output column o, h) sit at ((ks * n_out + o) * 2 + h) * 8 of the hi
-// plane, and their residuals at the same place of the lo plane.  Padding is zero in both planes.
-__global__ void nerfgrid_pack_split_kernel(const float *__restrict__ raw, unsigned short *__restrict__ planes, PackPlan plan) {
+__global__ void nerfmlp_pack_split_kernel(const float *__restrict__ raw, unsigned short *__restrict__ planes, int64_t lo_plane,
+                                          PackPlan plan) {
   const PackSeg s = plan.seg[blockIdx.y];
   const int64_t total = (int64_t)(s.ka_pad + s.kb) * s.n_out;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const float v = pack_elem<8>(raw, s, i);
     const __bf16 hb = (__bf16)v;
     planes[s.dst + i] = __builtin_bit_cast(unsigned short, hb);
-    planes[kSplitPlane + s.dst + i] = f32_to_bf16_bits(v - (float)hb);
+    planes[lo_plane + s.dst + i] = f32_to_bf16_bits(v - (float)hb);
   }
 }
 
@@ -119,6 +92,9 @@ struct GridTile {                 // the tiles of a chunk that starts at lattice
 };
 
 // ---- head ------------------------------------------------------------------------------------------------------------------------
+// One thread per point, its 128 trunk outputs in registers; per pose the chain the render's head runs (rgb_head).  ctab
+// [pose][128] is the caller's table of view rows.  It is not view_row's: ops.nerf_grid_query forms it as a matrix product through the
+// BLAS, the extraction tests hold that table against the reference, and taking it from view_row would move its bits
 __global__ __launch_bounds__(kTile) void nerfgrid_head_kernel(GridArgs ga, const float *__restrict__ packed, int64_t point0,
                                                               const float *__restrict__ gbuf, const float *__restrict__ ctab,
                                                               int num_poses, float *__restrict__ out) {
@@ -137,10 +113,13 @@ __global__ __launch_bounds__(kTile) void nerfgrid_head_kernel(GridArgs ga, const
     int wo = 0;
     asm volatile("" : "+s"(wo));
     const float *w = packed + kOffRgbW + wo;
+    // rgb_head's chain over nerf_mlp.cuh's pre-activation, written out: through the call the optimised IR of this kernel is the same
+    // instruction for instruction, but the module then declares its intrinsics in another order and the backend allocates 174 VGPRs
+    // for 166 -- two waves per SIMD for three, and 16 % more time per pose
     float r0 = 0.f, r1 = 0.f, r2 = 0.f;
 #pragma unroll
     for (int j = 0; j < kHalf; ++j) {
-      const float v = fmaxf(g[j] + c[j], 0.f);
+      const float v = head_relu(head_pre(g[j], c[j]));
       r0 = fmaf(w[j], v, r0);
       r1 = fmaf(w[kHalf + j], v, r1);
       r2 = fmaf(w[2 * kHalf + j], v, r2);
@@ -175,8 +154,8 @@ int matrix_plan(int input_ch, PackPlan &plan, int64_t *src_end) {
     } else {
       s.ka = 0, s.ka_pad = 0, s.kb = kW;
     }
-    s.ld = s.ka + s.kb;
-    src += (int64_t)s.n_out * s.ld;
+    s.ld_o = s.ka + s.kb, s.ld_k = 1;
+    src += (int64_t)s.n_out * s.ld_o;
     plan.seg[n++] = s;
   }
   *src_end = src;
@@ -213,6 +192,16 @@ int grid_query(const float *xs, const float *ys, const float *zs, int res_x, int
 
 }  // namespace
 
+int nerfmlp::launch_pack(const float *raw, const PackPlan &plan, int segs, float *packed, unsigned short *planes, int64_t lo_plane,
+                         hipStream_t stream) {
+  if (packed)
+    nerfmlp_pack_kernel<<<dim3(64, segs), 256, 0, stream>>>(raw, packed, plan);
+  else
+    nerfmlp_pack_split_kernel<<<dim3(64, segs), 256, 0, stream>>>(raw, planes, lo_plane, plan);
+  NRPN_LAUNCH_CHECK(packed ? "nerfmlp_pack_kernel" : "nerfmlp_pack_split_kernel");
+  return NRPN_OK;
+}
+
 extern "C" {
 
 int64_t nrpn_nerfgrid_work_bytes(int what, int64_t num_points) {
@@ -238,9 +227,7 @@ int nrpn_nerfgrid_pack(const float *raw, int input_ch, float *packed, nrpn_strea
     plan.seg[n++] = s;
   }
   NRPN_HIP(hipMemsetAsync(packed, 0, kPackedFloats * 4, as_stream(stream)));
-  nerfgrid_pack_kernel<<<dim3(64, n), 256, 0, as_stream(stream)>>>(raw, packed, plan);
-  NRPN_LAUNCH_CHECK("nerfgrid_pack_kernel");
-  return NRPN_OK;
+  return launch_pack(raw, plan, n, packed, nullptr, 0, as_stream(stream));
 }
 
 int nrpn_nerfgrid_pack_bf16x3(const float *raw, int input_ch, void *planes, nrpn_stream_t stream) {
@@ -249,9 +236,7 @@ int nrpn_nerfgrid_pack_bf16x3(const float *raw, int input_ch, void *planes, nrpn
   PackPlan plan{};
   int64_t src = 0;
   const int n = matrix_plan(input_ch, plan, &src);
-  nerfgrid_pack_split_kernel<<<dim3(64, n), 256, 0, as_stream(stream)>>>(raw, static_cast<unsigned short *>(planes), plan);
-  NRPN_LAUNCH_CHECK("nerfgrid_pack_split_kernel");
-  return NRPN_OK;
+  return launch_pack(raw, plan, n, nullptr, static_cast<unsigned short *>(planes), kSplitPlane, as_stream(stream));
 }
 
 int nrpn_nerfgrid_query(const float *xs, const float *ys, const float *zs, int res_x, int res_y, int res_z, float center_x,

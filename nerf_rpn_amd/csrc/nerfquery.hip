@@ -5,11 +5,14 @@
 //   rays     one workgroup per ray: embed_dirs(viewdir), c_r = W_d embed_dirs + W_c cam + b of views_linears.0
 //   trunk    the shared MFMA trunk (nerf_mlp.cuh) over (pts - centre) * scale -> raw sigma and g = W_f f
 //   head     one thread per point: v = relu(g + c_r), raw rgb = W_rgb v + b_rgb
+// embed_dirs, c_r (view_row) and the head's chains (rgb_head) are nerf_mlp.cuh's, the ones nerfrender.hip runs: on a render's points
+// and on view directions formed as unit_dir forms them, raw is the render's bit for bit.
 // Backward, per chunk of points, for the cotangent draw [points][4] (nothing is kept between forward and backward):
 //   trunk    again, with a sink that keeps the encoding e, h_0 .. h_7 and f of every point of the chunk
 //   headbwd  one thread per point: v and dv = (W_rgb^T draw_rgb) [g + c_r > 0], the head's cotangent rows (draw_rgb, dsigma) and
 //            the point's [embed_dirs | cam] row
-//   dgrad    dX = dY W on the MFMA with W^T packed like the forward weights (nrpn_nerfquery_pack_t), one layer per launch:
+//   dgrad    dX = dY W on the MFMA with W^T packed like the forward weights (nrpn_nerfquery_pack_t: segments of the one pack of
+//            nerf_mlp.cuh, run by nerfgrid.hip's kernels), one layer per launch:
 //            df = W_f^T dv; dy_7 = (W_feat^T df + dsigma w_alpha) [h_7 > 0]; dy_{i-1} = (W_i[:, h part]^T dy_i) [h_{i-1} > 0].
 //            Each result replaces, element for element, the activation whose mask it took (df replaces f).
 //   wgrad    dW = dY^T X on the MFMA, the points of the chunk cut into kSlices slices of whole tiles; a wave owns a 64 x 64 block of
@@ -70,8 +73,8 @@ GradLayout grad_layout(const Model &m) {
 }
 
 // ---- rays ------------------------------------------------------------------------------------------------------------------------
-// One workgroup of 128 threads per ray: ctab [ray][128] = b + W_c cam + W_d embed_dirs(viewdir) in the order of nerfrender's head;
-// xv [ray][kv] = [embed_dirs | cam | 0]
+// One workgroup of 128 threads per ray: ctab [ray][128] = nerf_mlp.cuh's view_row of the given viewdir, the row nerfrender's head
+// forms; xv [ray][kv] = [embed_dirs | cam | 0]
 __global__ __launch_bounds__(kHalf) void nerfquery_rays_kernel(const float *__restrict__ viewdirs, const float *__restrict__ w_view,
                                                                const float *__restrict__ b_view, const float *__restrict__ cam,
                                                                int multires_views, int cam_ch, int kv, float *__restrict__ ctab,
@@ -80,16 +83,12 @@ __global__ __launch_bounds__(kHalf) void nerfquery_rays_kernel(const float *__re
   const int j = threadIdx.x;
   const int64_t ray = blockIdx.x;
   const int views_ch = 3 + 6 * multires_views, ldv = views_ch + cam_ch;
-  if (j < 3) {
-    const float d = viewdirs[ray * 3 + j];
-    emb[j] = d;
-    for (int l = 0; l < multires_views; ++l) embed_freq(emb, d, l, j);
+  if (j == 0) {
+    const float vd[3] = {viewdirs[ray * 3], viewdirs[ray * 3 + 1], viewdirs[ray * 3 + 2]};
+    embed_dirs(emb, vd, multires_views);
   }
   __syncthreads();
-  float c = b_view[j];
-  for (int k = 0; k < cam_ch; ++k) c = fmaf(w_view[j * ldv + views_ch + k], cam[k], c);
-  for (int k = 0; k < views_ch; ++k) c = fmaf(w_view[j * ldv + k], emb[k], c);
-  ctab[ray * kHalf + j] = c;
+  ctab[ray * kHalf + j] = view_row(j, w_view, b_view, cam, emb, views_ch, cam_ch);
   if (xv)
     for (int k = j; k < kv; k += kHalf) xv[ray * kv + k] = k < views_ch ? emb[k] : k < ldv ? cam[k - views_ch] : 0.f;
 }
@@ -163,7 +162,7 @@ struct KeepTile {
 };
 
 // ---- head ------------------------------------------------------------------------------------------------------------------------
-// One workgroup of 64 threads, one tile; rgb_linear over v = relu(g + c_ray) as 128-term fmaf chains in j order
+// One workgroup of 64 threads, one tile; nerf_mlp.cuh's rgb_head with g streamed from gbuf, eight columns in flight
 __global__ __launch_bounds__(kTile) void nerfquery_head_kernel(Points pp, const float *__restrict__ packed, const float *__restrict__ ctab,
                                                                int64_t point0, const float *__restrict__ gbuf, float *__restrict__ raw) {
   const int t = threadIdx.x;
@@ -171,21 +170,9 @@ __global__ __launch_bounds__(kTile) void nerfquery_head_kernel(Points pp, const 
   const int64_t pc = pi < pp.num_points ? pi : pp.num_points - 1;
   const float *c = ctab + (pc / pp.S) * kHalf;
   const float *gt = gbuf + (int64_t)blockIdx.x * (kTile * kHalf) + t;
-  const float *w = packed + kOffRgbW;
-  float r0 = 0.f, r1 = 0.f, r2 = 0.f;
-#pragma unroll 8
-  for (int j = 0; j < kHalf; ++j) {
-    const float v = fmaxf(gt[j * kTile] + c[j], 0.f);
-    r0 = fmaf(w[j], v, r0);
-    r1 = fmaf(w[kHalf + j], v, r1);
-    r2 = fmaf(w[2 * kHalf + j], v, r2);
-  }
-  if (pi < pp.num_points) {
-    float *o = raw + pi * 4;
-    o[0] = r0 + packed[kOffRgbB];
-    o[1] = r1 + packed[kOffRgbB + 1];
-    o[2] = r2 + packed[kOffRgbB + 2];
-  }
+  float r[3];
+  rgb_head<false, 8>([&](int j) { return gt[j * kTile]; }, c, packed + kOffRgbW, r, nullptr);
+  if (pi < pp.num_points) rgb_store(raw + pi * 4, r, packed);
 }
 
 // what headbwd writes, row = point of the chunk; the rows past the last point are zero in dv and dyhead
@@ -195,7 +182,7 @@ struct HeadOut {
   float *xvp;             // [rows][kv]: the ray's [embed_dirs | cam | 0]
 };
 
-// One workgroup of 64 threads, one tile.  The relu's derivative is 0 at exactly 0, as torch has it.
+// One workgroup of 64 threads, one tile.  v and the relu's derivative come from the head's own head_pre (nerf_mlp.cuh).
 __global__ __launch_bounds__(kTile) void nerfquery_headbwd_kernel(Points pp, const float *__restrict__ packed,
                                                                   const float *__restrict__ ctab, const float *__restrict__ xv, int kv,
                                                                   int64_t point0, const float *__restrict__ gbuf,
@@ -216,13 +203,13 @@ __global__ __launch_bounds__(kTile) void nerfquery_headbwd_kernel(Points pp, con
   for (int pass = 0; pass < 2; ++pass) {
 #pragma unroll 8
     for (int j = 0; j < kHalf; ++j) {
-      const float pre = gt[j * kTile] + c[j];
+      const float pre = head_pre(gt[j * kTile], c[j]);
       float val;
       if (pass == 0) {
-        val = fmaxf(pre, 0.f);
+        val = head_relu(pre);
       } else {
         const float s = fmaf(w[2 * kHalf + j], d2, fmaf(w[kHalf + j], d1, w[j] * d0));
-        val = pre > 0.f ? s : 0.f;
+        val = head_on(pre) ? s : 0.f;
       }
       tile[t * kLdT + j] = val;
     }
@@ -238,49 +225,6 @@ __global__ __launch_bounds__(kTile) void nerfquery_headbwd_kernel(Points pp, con
   const float4 *xs = reinterpret_cast<const float4 *>(xv + ray * kv);
   float4 *xd = reinterpret_cast<float4 *>(o.xvp + (row0 + t) * kv);
   for (int k = 0; k < kv / 4; ++k) xd[k] = xs[k];
-}
-
-// ---- pack of the transposes ----------------------------------------------------------------------------------------------------
-// raw: nrpn_nerfgrid_pack's.  Segment blockIdx.y: B fragments (nerfgrid.hip) of W^T, i.e. k runs over W's rows and the output column o
-// over W's columns from col_off: the float4 of (kg, o, h) holds W[8 kg + 4 h + j][col_off + o], j = 0 .. 3
-struct PackTSeg {
-  int64_t dst, src;
-  int ld, col_off, K;     // row stride of W, first column, rows of W
-};
-struct PackTPlan {
-  PackTSeg seg[9];
-};
-
-// the value of element i of a segment's fragments, kFrag (4 floats or 8 bf16) elements to a fragment
-template <int kFrag>
-__device__ __forceinline__ float pack_t_elem(const float *__restrict__ raw, const PackTSeg &s, int64_t i) {
-  constexpr int kShift = kFrag == 4 ? 2 : 3;
-  static_assert(kFrag == 1 << kShift, "fragments of 4 or 8 elements");
-  const int j = (int)(i & (kFrag - 1)), h = (int)((i >> kShift) & 1);
-  const int64_t q = i >> (kShift + 1);
-  const int o = (int)(q % kW), kg = (int)(q / kW);
-  return raw[s.src + (int64_t)(2 * kFrag * kg + kFrag * h + j) * s.ld + s.col_off + o];
-}
-
-__global__ void nerfquery_pack_t_kernel(const float *__restrict__ raw, float *__restrict__ packed_t, PackTPlan plan) {
-  const PackTSeg s = plan.seg[blockIdx.y];
-  const int64_t total = (int64_t)s.K * kW;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x)
-    packed_t[s.dst + i] = pack_t_elem<4>(raw, s, i);
-}
-
-// The bf16x3 planes of the same nine transposes (splitting commutes with transposing: element for element these are the values of the
-// forward's planes): k-step ks = 16 consecutive rows of W; the eight bf16 of (ks, o, h) hold W[16 ks + 8 h + j][col_off + o], j = 0 .. 7,
-// at ((ks * 256 + o) * 2 + h) * 8 of the hi plane, their residuals at the same place of the lo plane, kPackedTFloats elements on.
-__global__ void nerfquery_pack_t_split_kernel(const float *__restrict__ raw, unsigned short *__restrict__ planes_t, PackTPlan plan) {
-  const PackTSeg s = plan.seg[blockIdx.y];
-  const int64_t total = (int64_t)s.K * kW;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const float v = pack_t_elem<8>(raw, s, i);
-    const __bf16 hb = (__bf16)v;
-    planes_t[s.dst + i] = __builtin_bit_cast(unsigned short, hb);
-    planes_t[kPackedTFloats + s.dst + i] = f32_to_bf16_bits(v - (float)hb);
-  }
 }
 
 // ---- dgrad -----------------------------------------------------------------------------------------------------------------------
@@ -325,7 +269,7 @@ __global__ __launch_bounds__(256) void nerfquery_dgrad_kernel(const float *__res
 }
 
 // The same product in the bf16x3 arithmetic: dy split in registers as the forward splits its activations, wt_hi / wt_lo the planes of the
-// packed W^T (nerfquery_pack_t_split_kernel); the epilogue's arithmetic (the dsigma w_alpha fmaf, the relu mask) is the fp32 kernel's.
+// packed W^T (nrpn_nerfquery_pack_t_bf16x3); the epilogue's arithmetic (the dsigma w_alpha fmaf, the relu mask) is the fp32 kernel's.
 // Memory is walked as the trunk's keep() walks it: the tile's loads are all issued before the first is stored to the image, the
 // result goes back through the image, and a thread then takes whole float4 of a row -- its 16 mask loads first, then its 16 stores
 // (out may be mask; an element is read and written by the same thread only).
@@ -675,12 +619,16 @@ __global__ void nerfquery_finish_kernel(double *__restrict__ gacc, int64_t total
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
-PackTPlan pack_t_plan(int input_ch) {
-  PackTPlan plan{};
+// The nine transposes as segments of nerf_mlp.cuh's pack (raw: nrpn_nerfgrid_pack's): k runs over W's rows and the output column o
+// over W's 256 columns from col_off, so the fragment element of (k, o) holds W[k][col_off + o].  Splitting commutes with transposing:
+// element for element the planes hold the values of the forward's planes.
+constexpr int kPackTSegs = 9;
+PackPlan pack_t_plan(int input_ch) {
+  PackPlan plan{};
   int64_t src = (int64_t)kW * input_ch;                       // after pts_linears.0
-  for (int i = 1; i <= 9; ++i) {                              // raw order: pts_linears 1 .. 7, feature_linear, W_f
+  for (int i = 1; i <= kPackTSegs; ++i) {                     // raw order: pts_linears 1 .. 7, feature_linear, W_f
     const int ld = i == kSkipLayer ? input_ch + kW : kW, K = i == 9 ? kHalf : kW;
-    plan.seg[i - 1] = PackTSeg{(int64_t)(i - 1) * kSzT, src, ld, i == kSkipLayer ? input_ch : 0, K};
+    plan.seg[i - 1] = PackSeg{(int64_t)(i - 1) * kSzT, src, kW, 1, ld, i == kSkipLayer ? input_ch : 0, 0, 0, K};
     src += (int64_t)K * ld;
   }
   return plan;
@@ -698,11 +646,6 @@ struct QueryCall {
   const uint4 *split_t;     // the bf16x3 planes of the packed transposes: the backward's dgrads and trunk wgrads then do too (with split)
   int64_t chunk_tiles() const { return cdiv64(chunk < pp.num_points ? chunk : pp.num_points, kTile); }
 };
-
-bool sizes_ok(int64_t num_rays, int samples, int64_t chunk) {
-  return num_rays >= 1 && samples >= 1 && samples <= 65536 && num_rays < ((int64_t)1 << 31) && chunk >= 1 &&
-         num_rays * samples < ((int64_t)1 << 40);
-}
 
 struct Layout {           // of the work buffer, in bytes; every part 16-byte aligned
   int64_t ctab, xv, gbuf, fwd_end;                                             // forward
@@ -734,7 +677,7 @@ int check(const char *who, const QueryCall &c, bool backward) {
   NRPN_REQUIRE(c.pp.pts && c.viewdirs && c.packed && c.w_view && c.b_view && c.work, "%s: null pointer", who);
   NRPN_REQUIRE(c.m.ok(), "%s: multires %d / multires_views %d / input_ch_cam %d", who, c.m.multires, c.m.multires_views, c.m.cam_ch);
   NRPN_REQUIRE(c.m.cam_ch == 0 || c.cam, "%s: input_ch_cam %d without an embedded_cam", who, c.m.cam_ch);
-  NRPN_REQUIRE(sizes_ok(c.num_rays, c.pp.S, c.chunk), "%s: %lld rays of %d points in chunks of %lld", who, (long long)c.num_rays, c.pp.S,
+  NRPN_REQUIRE(query_sizes_ok(c.num_rays, c.pp.S, c.chunk), "%s: %lld rays of %d points in chunks of %lld", who, (long long)c.num_rays, c.pp.S,
                (long long)c.chunk);
   NRPN_REQUIRE(c.chunk_tiles() <= 0x7fffff, "%s: chunk too large", who);
   const Layout l = layout(c.m, c.num_rays, c.chunk_tiles());
@@ -911,7 +854,7 @@ int64_t nrpn_nerfquery_work_bytes(int what, int64_t num_rays, int num_samples, i
   const Model m{multires, multires_views, input_ch_cam};
   if (what == 2 || what == 5) return kPackedTFloats * 4;       // floats, or a hi and a lo bf16 of each
   if (what == 4) return 4 * (int64_t)(kEnc + kLayers * kW + kW + 3 * kHalf + kHeadCols + (m.ok() ? m.kv() : 0));
-  if (!m.ok() || !sizes_ok(num_rays, num_samples, chunk)) return -1;
+  if (!m.ok() || !query_sizes_ok(num_rays, num_samples, chunk)) return -1;
   if (what == 3) return grad_layout(m).total;
   const int64_t n = num_rays * num_samples;
   const Layout l = layout(m, num_rays, cdiv64(chunk < n ? chunk : n, kTile));
@@ -921,18 +864,14 @@ int64_t nrpn_nerfquery_work_bytes(int what, int64_t num_rays, int num_samples, i
 int nrpn_nerfquery_pack_t(const float *raw, int input_ch, float *packed_t, nrpn_stream_t stream) {
   NRPN_REQUIRE(raw && packed_t, "nerfquery_pack_t: null pointer");
   NRPN_REQUIRE(input_ch >= 3 && input_ch <= kEnc, "nerfquery_pack_t: input_ch %d outside 3 .. %d", input_ch, kEnc);
-  nerfquery_pack_t_kernel<<<dim3(64, 9), 256, 0, as_stream(stream)>>>(raw, packed_t, pack_t_plan(input_ch));
-  NRPN_LAUNCH_CHECK("nerfquery_pack_t_kernel");
-  return NRPN_OK;
+  return launch_pack(raw, pack_t_plan(input_ch), kPackTSegs, packed_t, nullptr, 0, as_stream(stream));
 }
 
 int nrpn_nerfquery_pack_t_bf16x3(const float *raw, int input_ch, void *planes_t, nrpn_stream_t stream) {
   NRPN_REQUIRE(raw && planes_t, "nerfquery_pack_t_bf16x3: null pointer");
   NRPN_REQUIRE(input_ch >= 3 && input_ch <= kEnc, "nerfquery_pack_t_bf16x3: input_ch %d outside 3 .. %d", input_ch, kEnc);
-  nerfquery_pack_t_split_kernel<<<dim3(64, 9), 256, 0, as_stream(stream)>>>(raw, static_cast<unsigned short *>(planes_t),
-                                                                           pack_t_plan(input_ch));
-  NRPN_LAUNCH_CHECK("nerfquery_pack_t_split_kernel");
-  return NRPN_OK;
+  return launch_pack(raw, pack_t_plan(input_ch), kPackTSegs, nullptr, static_cast<unsigned short *>(planes_t), kPackedTFloats,
+                     as_stream(stream));
 }
 
 int nrpn_nerfquery_forward(const float *pts, const float *viewdirs, int64_t num_rays, int num_samples, float center_x, float center_y,

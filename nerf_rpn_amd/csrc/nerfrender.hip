@@ -5,7 +5,8 @@
 //   rays     (frame mode) o = t, d = R [(u - cx) / fx, -(v - cy) / fy, -1] of pixel r = v W + u, float32 in the reference's order
 //   trunk    the shared MFMA trunk (nerf_mlp.cuh) over the points o_r + d_r z[r][s] -> raw sigma and g
 //   head     one thread per point: v = relu(g + c_r), raw rgb = W_rgb v + b_rgb; c_r = W_d embed_dirs(d_r / |d_r|) + W_c cam + b is
-//            computed per ray of the tile in LDS
+//            computed per ray of the tile in LDS.  unit_dir, embed_dirs, view_row and rgb_head are nerf_mlp.cuh's, the ones
+//            nerfquery.hip runs: a query of the same points and view directions gives the same raw, bit for bit
 //   sample   (two-pass) one thread per ray: weights of pass 1 -> depth, std -> clamped +-3 sigma bins -> inverse CDF at linspace(0, 1)
 //   trunk + head again over z2, then
 //   composite  one thread per ray: merge of the two non-decreasing lists, weights, rgb / depth / acc / disp / depth_std
@@ -30,6 +31,17 @@ struct RayPoints {
   int z_stride, S;
   int64_t num_points;     // rays of the chunk * S
   float cx, cy, cz, scale;
+  // The world point o + d z of point pi, the product and the sum rounded one after the other (the reference's order; it feeds
+  // sinf(2^8 p)).  A partial tile's pi past the end repeats the last point; nothing of it may be stored.
+  __device__ __forceinline__ void world(int64_t pi, float (&p)[3]) const {
+    if (pi > num_points - 1) pi = num_points - 1;
+    const int64_t ray = pi / S;
+    const int s = (int)(pi - ray * S);
+    const float zv = z[ray * z_stride + s];
+    const float *o = rays + ray * 6;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) p[a] = __fadd_rn(o[a], __fmul_rn(o[3 + a], zv));
+  }
 };
 
 // ---- rays ------------------------------------------------------------------------------------------------------------------------
@@ -45,15 +57,10 @@ struct RaySrc {
   const RayPoints &rp;
   int64_t tile0;
   __device__ __forceinline__ void point(int i, float (&p)[3]) const {
-    int64_t pi = tile0 + i;
-    if (pi > rp.num_points - 1) pi = rp.num_points - 1;       // a partial tile repeats the last point; nothing of it is stored
-    const int64_t ray = pi / rp.S;
-    const int s = (int)(pi - ray * rp.S);
-    const float zv = rp.z[ray * rp.z_stride + s];
-    const float *o = rp.rays + ray * 6;
+    rp.world(tile0 + i, p);
     const float c[3] = {rp.cx, rp.cy, rp.cz};
 #pragma unroll
-    for (int a = 0; a < 3; ++a) p[a] = __fmul_rn(__fsub_rn(__fadd_rn(o[a], __fmul_rn(o[3 + a], zv)), c[a]), rp.scale);
+    for (int a = 0; a < 3; ++a) p[a] = __fmul_rn(__fsub_rn(p[a], c[a]), rp.scale);
   }
 };
 struct RayTile {          // the tiles of one pass over a chunk's rays
@@ -65,26 +72,9 @@ struct RayTile {          // the tiles of one pass over a chunk's rays
 };
 
 // ---- head ------------------------------------------------------------------------------------------------------------------------
-// rgb_linear over v = relu(g + c) for one point: g the point's 128 trunk outputs in registers, c[j] the view part of its ray.
-// 128-term fmaf chains in j order; W_rgb is wave-uniform and comes through the scalar cache.  kMask: bit j of m is g[j] + c[j] > 0,
-// the derivative of the relu (0 at exactly 0, as torch has it), for the camera-embedding gradient.
-template <bool kMask>
-__device__ __forceinline__ void rgb_head(const float (&g)[kHalf], const float *c, const float *__restrict__ w, float &r0, float &r1,
-                                         float &r2, uint32_t (&m)[4]) {
-  r0 = r1 = r2 = 0.f;
-#pragma unroll
-  for (int j = 0; j < kHalf; ++j) {
-    const float pre = g[j] + c[j];
-    const float v = fmaxf(pre, 0.f);
-    if (kMask) m[j >> 5] |= (uint32_t)(pre > 0.f) << (j & 31);
-    r0 = fmaf(w[j], v, r0);
-    r1 = fmaf(w[kHalf + j], v, r1);
-    r2 = fmaf(w[2 * kHalf + j], v, r2);
-  }
-}
-
-// One workgroup of 64 threads, one tile of 64 points.  w_view [128][views_ch + cam_ch]: the view and camera columns of
-// views_linears.0.weight; b_view [128]; cam [cam_ch]; mask [points][4] (kMask only)
+// One workgroup of 64 threads, one tile of 64 points: nerf_mlp.cuh's view_row of the tile's rays in LDS, then its rgb_head over the
+// point's 128 trunk outputs in registers.  w_view [128][views_ch + cam_ch]: the view and camera columns of views_linears.0.weight;
+// b_view [128]; cam [cam_ch]; mask [points][4] (kMask only): the relu's derivative, for the camera-embedding gradient
 template <bool kMask>
 __device__ __forceinline__ void head_tile(const RayPoints &rp, const float *__restrict__ packed, const float *__restrict__ w_view,
                                           const float *__restrict__ b_view, const float *__restrict__ cam, int multires_views, int cam_ch,
@@ -97,27 +87,19 @@ __device__ __forceinline__ void head_tile(const RayPoints &rp, const float *__re
   const int64_t last = tile0 + kTile - 1 < rp.num_points ? tile0 + kTile - 1 : rp.num_points - 1;
   const int64_t ray_first = tile0 / rp.S;
   const int nr = (int)(last / rp.S - ray_first) + 1;          // rays with a sample in this tile: 1 .. 64
-  const int views_ch = 3 + 6 * multires_views, ldv = views_ch + cam_ch;
+  const int views_ch = 3 + 6 * multires_views;
 
-  for (int j = t; j < kHalf; j += kTile) {
-    float c = b_view[j];
-    for (int k = 0; k < cam_ch; ++k) c = fmaf(w_view[j * ldv + views_ch + k], cam[k], c);
-    cbase[j] = c;
-  }
+  // view_row of every ray of the tile, in two steps: what no ray changes, once; then each ray's view columns
+  for (int j = t; j < kHalf; j += kTile) cbase[j] = view_row_cam(j, w_view, b_view, cam, views_ch, cam_ch);
   if (t < nr) {
-    const float *d = rp.rays + (ray_first + t) * 6 + 3;
-    const float n = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(d[0], d[0]), __fmul_rn(d[1], d[1])), __fmul_rn(d[2], d[2])));
-    const float vd[3] = {__fdiv_rn(d[0], n), __fdiv_rn(d[1], n), __fdiv_rn(d[2], n)};
-    for (int a = 0; a < 3; ++a) emb[t][a] = vd[a];
-    for (int l = 0; l < multires_views; ++l)
-      for (int a = 0; a < 3; ++a) embed_freq(emb[t], vd[a], l, a);
+    float vd[3];
+    unit_dir(rp.rays + (ray_first + t) * 6 + 3, vd);
+    embed_dirs(emb[t], vd, multires_views);
   }
   __syncthreads();
   for (int idx = t; idx < nr * kHalf; idx += kTile) {
     const int ray = idx / kHalf, j = idx - ray * kHalf;
-    float c = cbase[j];
-    for (int k = 0; k < views_ch; ++k) c = fmaf(w_view[j * ldv + k], emb[ray][k], c);
-    ctile[ray * kCtileLd + j] = c;
+    ctile[ray * kCtileLd + j] = view_row_dirs(cbase[j], j, w_view, emb[ray], views_ch, cam_ch);
   }
   __syncthreads();
 
@@ -128,14 +110,11 @@ __device__ __forceinline__ void head_tile(const RayPoints &rp, const float *__re
   float g[kHalf];
 #pragma unroll
   for (int j = 0; j < kHalf; ++j) g[j] = gt[j * kTile];
-  float r0, r1, r2;
+  float r[3];
   uint32_t m[4] = {0u, 0u, 0u, 0u};
-  rgb_head<kMask>(g, crow, packed + kOffRgbW, r0, r1, r2, m);
+  rgb_head<kMask, kHalf>([&](int j) { return g[j]; }, crow, packed + kOffRgbW, r, m);
   if (pi < rp.num_points) {
-    float *o = raw + pi * 4;
-    o[0] = r0 + packed[kOffRgbB];
-    o[1] = r1 + packed[kOffRgbB + 1];
-    o[2] = r2 + packed[kOffRgbB + 2];
+    rgb_store(raw + pi * 4, r, packed);
     if (kMask) *reinterpret_cast<uint4 *>(mask + pi * 4) = make_uint4(m[0], m[1], m[2], m[3]);
   }
 }
@@ -156,8 +135,7 @@ __global__ __launch_bounds__(kTile) void nerfrender_head_kernel(RayPoints rp, co
 //   boxzero   +0 into raw of every point whose byte is 0, points of skipped tiles included
 constexpr int kMaxBoxes = 1024;
 
-// The world point of a sample is RaySrc's o + d z before the normalisation, the same float32 operations; the test is float64 and
-// closed: |R(-theta)(p - c)| <= half extent on each axis.  The box table is read through wave-uniform addresses.  A partial last
+// The world point of a sample is RayPoints::world, the point RaySrc normalises; the test is float64 and closed: |R(-theta)(p - c)| <= half extent on each axis.  The box table is read through wave-uniform addresses.  A partial last
 // tile tests only its valid points.
 __global__ __launch_bounds__(kTile) void nerfrender_boxmask_kernel(RayPoints rp, const double *__restrict__ boxes, int num_boxes,
                                                                    int remove, uint8_t *__restrict__ counted,
@@ -165,14 +143,9 @@ __global__ __launch_bounds__(kTile) void nerfrender_boxmask_kernel(RayPoints rp,
   const int t = threadIdx.x;
   const int64_t pi = (int64_t)blockIdx.x * kTile + t;
   const bool valid = pi < rp.num_points;
-  const int64_t pc = valid ? pi : rp.num_points - 1;
-  const int64_t ray = pc / rp.S;
-  const int s = (int)(pc - ray * rp.S);
-  const float zv = rp.z[ray * rp.z_stride + s];
-  const float *o = rp.rays + ray * 6;
-  double p[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) p[a] = (double)__fadd_rn(o[a], __fmul_rn(o[3 + a], zv));
+  float pf[3];
+  rp.world(pi, pf);
+  const double p[3] = {(double)pf[0], (double)pf[1], (double)pf[2]};
   bool in = false;
   for (int k = 0; k < num_boxes; ++k) {
     const double *b = boxes + (int64_t)k * 8;

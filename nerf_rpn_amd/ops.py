@@ -3183,6 +3183,11 @@ def nerf_query(params, cfg, pts, viewdirs, embedded_cam=None, bb_center=(0., 0.,
     normalisation.  Returns raw [R, S, 4] float32 on the device: rgb before the sigmoid, sigma before the relu.  pts or viewdirs that
     require grad raise NotImplementedError (no entry point of the reference differentiates them).
 
+    The view branch and the rgb head are nerf_render's own code (csrc/nerf_mlp.cuh), so raw is nerf_render's first-pass raw bit for
+    bit when pts and viewdirs are formed in float32 as it forms them from a ray (o, d) and a sample z: pts = o + d * z with the
+    product and the sum rounded one after the other, and viewdirs = d / n with n = sqrt((d0 * d0 + d1 * d1) + d2 * d2), every
+    operation rounded on its own (unit_dir) -- the products summed left to right, then one square root and three divisions.
+
     chunk (points, default 2^16, rounded up to tiles of 64) bounds the scratch: the forward keeps 512 bytes per point of a chunk and
     nothing for the backward, which re-runs the forward chunk by chunk and keeps 11264 + 4 * ceil64(views_ch + input_ch_cam) bytes
     per point (11520 for the default options), plus 512 + 4 * ceil64(views_ch + input_ch_cam) bytes per ray, 16 MiB of slice partials

@@ -90,6 +90,28 @@ def test_sigma_bit_equal_to_render():
     assert float((raw[..., :3] - out["raw1"][..., :3]).abs().max()) <= 1e-5        # the head adds the same terms; viewdirs are given here
 
 
+@pytest.mark.parametrize("name", ["plain_4x6", "views_cam_3x5"])
+def test_raw_bit_equal_to_render(name):
+    """On a render's rays and first-pass samples, with pts = o + d z formed as a separately rounded multiply and add and viewdirs
+    formed in unit_dir's order (csrc/nerf_mlp.cuh), all four channels of raw are nerf_render's: the two run one view branch and one
+    rgb head.  Tiles of 64 points hold several rays in both cases (24 and 8 samples a ray); the 15 x 8 points of views_cam_3x5 end in
+    a partial tile, and it has two view frequencies and four camera channels."""
+    c = V.case_inputs(V.CASES[V.NAMES.index(name)])
+    ref = V.render_case(c, torch.float32)
+    rays = torch.cat([ref["rays_o"], ref["rays_d"]], -1).contiguous()
+    out = ops.nerf_render(c.state, c.cfg, rays=rays, near=c.near, far=c.far, bb_center=c.bb_center, bb_scale=c.bb_scale,
+                          z_samples=c.z_samples, n_samples=c.n_samples, embedded_cam=c.embedded_cam, return_samples=True,
+                          return_stages=True)
+    raw1 = out["raw1"]
+    z =(out["z_vals"] if c.plain else c.z_samples.expand(rays.shape[0], -1)).cpu()
+    assert z.shape == raw1.shape[:2]
+    pts = rays[:, None, :3] + rays[:, None, 3:] * z[..., None]
+    d = rays[:, 3:].to(DEV)           # on the device: its float32 square root and division are the kernel's
+    viewdirs = d / torch.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])[:, None]
+    raw = ops.nerf_query(dev_state(c), c.cfg, pts, viewdirs, c.embedded_cam, c.bb_center, c.bb_scale)
+    assert torch.equal(raw, raw1)
+
+
 def test_module_matches_op_and_fills_grads(refs):
     c, _, _ = refs("tile_plus_one")
     want = run(c)

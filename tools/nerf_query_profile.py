@@ -28,7 +28,7 @@ from nerf_profile import kernel_times, timed, trunk_kernel  # noqa: E402
 RAYS, SAMPLES = 1024, 256
 KERNELS = (trunk_kernel("KeepTile"), trunk_kernel("PointTile"), "nerfquery_head_kernel", "nerfquery_headbwd_kernel",
            "nerfquery_dgrad_kernel", "nerfquery_wgrad_kernel", "nerfquery_reduce_kernel", "nerfquery_finish_kernel",
-           "nerfquery_pack_t_kernel", "nerfgrid_pack_kernel", "nerfquery_rays_kernel")
+           "nerfmlp_pack_kernel", "nerfquery_rays_kernel")
 
 
 def step_flops(points, input_ch=57, tail=7):
