@@ -175,8 +175,10 @@ def lib_flags(relu):
 @pytest.mark.parametrize("dtype,ksize,cin,cout", [(torch.float32, 3, 64, 96), (torch.bfloat16, 3, 256, 256), (torch.bfloat16, 1, 256, 128),
                                                   (torch.float32, 3, 256, 256)])
 def test_conv_rows_wgrad_matches_torch(dtype, ksize, cin, cout, dev):
-    """dW, db from the listed rows only == autograd of the dense convolution when dY is zero outside the list; the 256 x 256 bf16 case runs
-    conv_wgrad_big_kernel<ROWS>, the others conv_wgrad_kernel<ROWS>."""
+    """dW, db from the listed rows only == autograd of the dense convolution when dY is zero outside the list.  Every case here, the
+    256 x 256 bf16 one included, runs conv_wgrad_kernel<ROWS> on one slice: wgrad_plan tries k <= chunks / 16 slices of 64-row chunks and
+    takes the 256x256 form only where 27 k tiles fill half a round of the chip (k >= 5, i.e. lists of 5057 rows or more), and these lists
+    hold a few hundred rows.  conv_wgrad_big_kernel<ROWS> is tested in test_gpu_conv_rows_exact.py on a 5200-row list."""
     from nerf_rpn_amd import ops
     n = 2
     rng = np.random.default_rng(6)
